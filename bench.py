@@ -2,7 +2,7 @@
 """bench.py — BA iterations/s + ms/solve on BASELINE.json config 2 (synthetic 20 KF x 8 000 landmarks x
 40 000 reprojection factors, GN 10 iters) through the C ABI of the HIP backend.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
 
 A "step" is --solves-per-step (default 400) back-to-back complete solves (each: 10 LM step attempts, every early exit
@@ -29,6 +29,7 @@ One JSON line is printed by rank 0. Besides the contract's fields it carries
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -95,7 +96,8 @@ def self_launch(args, argv):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # RCCL across processes: the host driver only supports dmabuf IPC
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    # a fresh child, not an exec: counting the devices above has already initialised the HIP runtime in this process
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def parse_args(argv=None):
@@ -115,13 +117,55 @@ def parse_args(argv=None):
     ap.add_argument("--no-marginalize", action="store_true")
     ap.add_argument("--no-sharded", action="store_true", help="N = 1: skip the one-rank run of the sharded config-4 window (RCCL communicator of size 1)")
     ap.add_argument("--no-vio", action="store_true", help="skip the config-3 shaped VIO window leg (the profiled runs of scripts/prof_bench.sh: one k_solve variant per trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned to its caller (summaries, deltas, ids) as float64 DIR/<name>.npy, "
+                         "at most 64 MB; the inputs are seeded, so two builds can be compared output for output")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, be, sums, prefix="", budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: what a caller of the timed path receives after its last solve, one float64 .npy per array.
+    `summary` [n_windows, 8] holds the SolveSummary fields in their C order; per window w: get_deltas (w<w>_pose / _lmk / _dv /
+    _dba / _dbg) and get_ids (w<w>_kf_id / _lmk_id, exact in float64 below 2^53). When all windows do not fit the budget, a fixed seeded
+    sample of them is written; `windows` lists the ones that were. Returns the bytes written. The device's atomic reductions are
+    not bit-reproducible: two runs of one build agree to ~1e-11 in the landmark deltas, so comparisons need a tolerance."""
+    import numpy as np
+    from sadvio_amd import capi
+    n = len(sums)
+    summary = np.array([[float(getattr(s, f)) for f, _ in capi.SolveSummary._fields_] for s in sums], dtype=np.float64).reshape(n, -1)
+    hdr = 128   # an .npy header of these shapes
+    per_win = [8 * (be.windows[w].n_kf * (6 + 3 * 3 + 1) + be.windows[w].n_lmk * (3 + 1)) + 7 * hdr for w in range(n)]
+    room = budget - summary.nbytes - 8 * n - 2 * hdr
+    keep = []
+    for w in (range(n) if sum(per_win) <= room else np.random.default_rng(seed).permutation(n)):
+        if per_win[w] <= room:
+            keep.append(int(w))
+            room -= per_win[w]
+    keep.sort()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"summary": summary, "windows": np.array(keep, dtype=np.float64)}
+    for w in keep:
+        for k, v in be.get_deltas(w).items():
+            arrays[f"w{w}_{k}"] = v
+        kf_id, lmk_id = be.get_ids(w)
+        arrays[f"w{w}_kf_id"], arrays[f"w{w}_lmk_id"] = kf_id.astype(np.float64), lmk_id.astype(np.float64)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, prefix + name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        total += os.path.getsize(path)
+    return total
 
 
 def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args, sys.argv[1:])      # does not return
     rank = int(os.environ.get("RANK", "0"))
@@ -153,16 +197,18 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_solves(be, opts, steps, warmup, per_step=1):
+    def timed_solves(be, opts, steps, warmup, per_step=1, last=None):
         for _ in range(warmup * per_step):
             be.solve(opts)
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps * per_step):
-            be.solve(opts)
+            sums = be.solve(opts)
         torch.cuda.synchronize()
         barrier()
         dt = time.perf_counter() - t0
+        if last is not None:
+            last.extend(sums)   # the summaries of the last timed solve
         if dist is not None:
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -191,7 +237,11 @@ def main():
     be = capi.Backend(device=local_rank, use_graph=True)  # one hipGraph launch per solve
     be.set_windows(wins)
     sps = max(1, args.solves_per_step)
-    dt = timed_solves(be, opts, args.steps, args.warmup, sps)
+    last = []
+    dt = timed_solves(be, opts, args.steps, args.warmup, sps, last)
+    if args.dump_outputs:
+        nbytes = dump_outputs(args.dump_outputs, be, last, prefix=f"rank{rank}_" if world > 1 else "", budget=DUMP_BUDGET_BYTES // world)
+        print(f"bench.py: {nbytes / 2**20:.2f} MB of the last timed step's outputs in {args.dump_outputs}", file=sys.stderr)
     sums = be.solve(opts)
     gpu_sol = be.get_deltas(0)
     gpu_ids = be.get_ids(0)
