@@ -2,19 +2,24 @@
 """bench.py — BA iterations/s + ms/solve on BASELINE.json config 2 (synthetic 20 KF x 8 000 landmarks x
 40 000 reprojection factors, GN 10 iters) through the C ABI of the HIP backend.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
 
 A "step" is --solves-per-step (default 400) back-to-back complete solves (each: 10 LM step attempts, every early exit
 disabled, one hipGraph launch) of the windows resident on this GPU, so that the driver's 20-step run times ~5 s of GPU
-work instead of 12 ms (and a sampling `rocm-smi` sees a busy GPU); the CPU-baseline legs run BEFORE the GPU legs; `value` (BA iterations/s) does not depend on that grouping, `ms_per_step` is per step and
+work instead of 12 ms (and a sampling `rocm-smi` sees a busy GPU); `value` (BA iterations/s) does not depend on that grouping, `ms_per_step` is per step and
 `ms_per_solve` per solve. The windows are uploaded to HBM before the timed region (`upload_inclusive` reports the rate with
 set_windows + get_deltas inside, the way the reference's own timer brackets problem construction, slamBiMono.cpp:273-275).
+
 N > 1 shards independent windows (one set per GPU, weak scaling, no data-path collective — BASELINE.json north_star: "independent sub-windows / keyframe
 batches shard across the 8 GPUs"); torch.distributed (backend "nccl" = RCCL) is used only for the barriers and
 the max-over-ranks of the elapsed time.
 
-One JSON line is printed by rank 0. Besides the contract's fields it carries
+A plain run does only what the headline needs: it builds the windows, warms up, times the steps, writes --dump-outputs and prints
+the line with the contract's fields and `config`. Everything below comes with --full, which runs the CPU-baseline legs BEFORE the
+timed GPU steps and the other GPU legs after them (~1 minute more).
+
+One JSON line is printed by rank 0. With --full, besides the contract's fields it carries
   roofline      the dominant kernel's achieved algorithmic GB/s vs the 8 TB/s HBM peak; kernel durations are
                 measured live with hipEvents on the backend's stream in a separate (untimed) profiled pass
   cpu_baseline  the CPU oracle (a port of the reference's algorithm, the reference itself cannot be built
@@ -107,13 +112,17 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--solves-per-step", type=int, default=400, help="complete GN-10 solves per timed step")
     ap.add_argument("--windows", type=int, default=1, help="independent config-2 windows per GPU in the timed run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (CPU baselines and parity, roofline, batched, upload-inclusive, sharded, "
+                         "marginalize, back-end step, VIO window) and add its object to the line; the --no-* and --batch* "
+                         "options below select among them")
     ap.add_argument("--batch", type=int, default=64, help="windows per GPU of the extra batched measurement (0 = skip)")
     ap.add_argument("--batch-large", type=int, default=256, help="windows of the second batched measurement (<= --batch: skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--shard-window", action="store_true",
                     help="ONLY the sharded measurement: ONE config-4 window (100 KF x 50k landmarks) landmark-sharded "
-                         "over the ranks, reduced system all-reduced over RCCL per LM step (strong scaling). With N > 1 the "
-                         "default run reports it as the `sharded_window` object next to the independent-window line")
+                         "over the ranks, reduced system all-reduced over RCCL per LM step (strong scaling). With N > 1 a "
+                         "--full run reports it as the `sharded_window` object next to the independent-window line")
     ap.add_argument("--no-marginalize", action="store_true")
     ap.add_argument("--no-sharded", action="store_true", help="N = 1: skip the one-rank run of the sharded config-4 window (RCCL communicator of size 1)")
     ap.add_argument("--no-vio", action="store_true", help="skip the config-3 shaped VIO window leg (the profiled runs of scripts/prof_bench.sh: one k_solve variant per trace)")
@@ -215,22 +224,24 @@ def main():
             dt = float(t.item())
         return dt
 
-    if args.shard_window:
-        rec = bench_sharded_window(args, rank, local_rank, world, dist, barrier, timed_solves)
+    def finish(rec):
         if rank == 0:
             emit_record(rec)
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
+
+    if args.shard_window:
+        finish(bench_sharded_window(args, rank, local_rank, world, dist, barrier, timed_solves))
         return
 
     opts = capi.gn_options(GN_ITERS)
     # every rank owns its own windows (different seeds): weak scaling over independent sub-windows
     base_seed = 20250404 + 1000 * rank
     wins = [synthetic.make_window(seed=base_seed + i) for i in range(args.windows)]
-    # CPU legs first (rank 0 at N = 1 only): the GPU legs then run back to back at the end of the command
+    # --full: CPU legs first (rank 0 at N = 1 only): the GPU legs then run back to back at the end of the command
     cpu = marg_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg(wins[0], opts)
         if not args.no_marginalize:
             marg_cpu = marginalize_cpu_leg()
@@ -242,6 +253,31 @@ def main():
     if args.dump_outputs:
         nbytes = dump_outputs(args.dump_outputs, be, last, prefix=f"rank{rank}_" if world > 1 else "", budget=DUMP_BUDGET_BYTES // world)
         print(f"bench.py: {nbytes / 2**20:.2f} MB of the last timed step's outputs in {args.dump_outputs}", file=sys.stderr)
+    iters_per_solve = sum(s.iterations for s in last)
+    total_iters = iters_per_solve * args.steps * sps * world
+    value = total_iters / dt
+    ms_per_step = 1e3 * dt / args.steps
+    ms_per_solve = ms_per_step / sps
+    w0 = wins[0]
+    n_p = 6 * int((w0.kf_const == 0).sum())
+    out = {
+        "metric": "BA iterations/sec (ms/solve in ms_per_solve), 20-KF/8k-landmark window",
+        "value": round(value, 1), "unit": "BA iterations/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "ms_per_solve": round(ms_per_solve, 5),
+        "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "synthetic 20 KF x 8000 landmarks x 40000 reprojection factors (pixel), "
+                               f"GN {GN_ITERS} iters (LM step attempts, early exits disabled)",
+                   "solves_per_step": sps,
+                   "windows_per_gpu": args.windows, "iterations_per_solve": iters_per_solve // max(1, args.windows),
+                   "parallelism": f"independent windows x{world}" if world > 1 else "single window",
+                   "n_kf": w0.n_kf, "n_lmk": w0.n_lmk, "n_obs": w0.n_obs, "reduced_dim": n_p},
+    }
+    if not args.full:
+        be.close()
+        finish(out)
+        return
+
     sums = be.solve(opts)
     gpu_sol = be.get_deltas(0)
     gpu_ids = be.get_ids(0)
@@ -279,11 +315,6 @@ def main():
         dt_up2 = (time.perf_counter() - t0) / (2 * n_up)
         for b in bes:
             b.close()
-    iters_per_solve = sum(s.iterations for s in sums)
-    total_iters = iters_per_solve * args.steps * sps * world
-    value = total_iters / dt
-    ms_per_step = 1e3 * dt / args.steps
-    ms_per_solve = ms_per_step / sps
     # N > 1: the collective path as well (same processes, same communicator): config 4 sharded over the ranks
     # the collective path (config 4 sharded over the ranks; RCCL all-reduce of the reduced system per LM step). At N = 1 it runs
     # through the same sadvio_ba_comm_init_rccl / ncclAllReduce calls with a one-rank communicator, so that every driver record
@@ -291,10 +322,7 @@ def main():
     sharded = bench_sharded_window(args, rank, local_rank, world, dist, barrier, timed_solves) if (world > 1 or not args.no_sharded) else None
     sharded5 = bench_sharded_window(args, rank, local_rank, world, dist, barrier, timed_solves, config=5) if world > 1 else None
 
-    out = None
     if rank == 0:
-        w0 = wins[0]
-        n_p = 6 * int((w0.kf_const == 0).sum())
         # --- live per-kernel durations (hipEvents on the backend's stream), untimed profiled pass ---
         bp = capi.Backend(device=local_rank, profile_kernels=True)
         bp.set_windows(wins)
@@ -436,18 +464,7 @@ def main():
             marg = marginalize_leg(local_rank, marg_cpu)
             bstep = backend_step_leg(local_rank)
         vio = vio_window_leg(local_rank, opts) if (world == 1 and not args.no_vio) else None
-        out = {
-            "metric": "BA iterations/sec (ms/solve in ms_per_solve), 20-KF/8k-landmark window",
-            "value": round(value, 1), "unit": "BA iterations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "ms_per_solve": round(ms_per_solve, 5),
-            "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "synthetic 20 KF x 8000 landmarks x 40000 reprojection factors (pixel), "
-                                   f"GN {GN_ITERS} iters (LM step attempts, early exits disabled)",
-                       "solves_per_step": sps,
-                       "windows_per_gpu": args.windows, "iterations_per_solve": iters_per_solve // max(1, args.windows),
-                       "parallelism": f"independent windows x{world}" if world > 1 else "single window",
-                       "n_kf": w0.n_kf, "n_lmk": w0.n_lmk, "n_obs": w0.n_obs, "reduced_dim": n_p},
+        out.update({
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "batched": batched,
             "upload_inclusive": {"value": round(iters_per_solve / dt_up, 1), "unit": "BA iterations/s",
                                  "ms_per_solve": round(1e3 * dt_up, 4),
@@ -456,7 +473,7 @@ def main():
                                                  {"value": round(iters_per_solve / dt_up2, 1), "ms_per_solve": round(1e3 * dt_up2, 4),
                                                   "what": "two handles on two host threads, each set_windows + solve + get_deltas in turn: one handle's layout build runs under the other's solve"})},
             "marginalize": marg, "backend_step": bstep, "vio_window": vio, "sharded_window": sharded, "sharded_window_c5": sharded5,
-        }
+        })
         if cpu and batched and cpu.get("batched"):
             batched["speedup_vs_cpu_batched"] = round(batched["value"] / cpu["batched"]["value"], 1)
             batched["speedup_note"] = "throughput regime against throughput regime: 64 windows per GPU submission vs independent windows on all usable host cores"
@@ -464,10 +481,7 @@ def main():
             out["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 1)                              # at the reference's 4 threads
             out["speedup_vs_cpu_at_reference_threads"] = round(value / cpu["at_reference_threads"]["value"], 1)
             out["speedup_vs_cpu_best_thread_count"] = round(value / cpu["best_thread_count"]["value"], 1)
-        emit_record(out)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out)
 
 
 def cpu_baseline_leg(w0, opts):

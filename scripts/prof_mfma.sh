@@ -6,9 +6,10 @@
 TAG=$1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/mfma_$TAG
 mkdir -p $OUT
+ROOT=$(pwd)
 cd /tmp && export TMPDIR=/tmp
 PMC="SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU GRBM_GUI_ACTIVE"
-rocprofv3 --pmc $PMC --output-format csv -d $OUT/c2 -o p -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-vio --no-marginalize --batch 0 --steps 5 --warmup 1 --solves-per-step 20 > $OUT/c2.log 2>&1
+rocprofv3 --pmc $PMC --output-format csv -d $OUT/c2 -o p -- python $ROOT/bench.py --full --no-cpu-baseline --no-vio --no-marginalize --batch 0 --steps 5 --warmup 1 --solves-per-step 20 > $OUT/c2.log 2>&1
 rocprofv3 --pmc $PMC --output-format csv -d $OUT/c3dense -o p -- python $GRAFT_REPO_ROOT/scripts/gpu_time_c3.py dense > $OUT/c3dense.log 2>&1
 rocprofv3 --pmc $PMC --output-format csv -d $OUT/c4 -o p -- python $GRAFT_REPO_ROOT/scripts/gpu_time_big.py c4 > $OUT/c4.log 2>&1
 rocprofv3 --pmc $PMC --output-format csv -d $OUT/marg -o p -- python $GRAFT_REPO_ROOT/scripts/gpu_time_backend_step.py 300 1 > $OUT/marg.log 2>&1

@@ -64,6 +64,17 @@ def test_steps_must_be_positive():
     assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and r.stdout.strip() == ""
 
 
+def test_full_is_off_by_default():
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    assert bench.parse_args(["--full"]).full is True
+
+
+# what a --full run adds to the line; a plain run carries the contract's fields and `config` alone
+FULL_ONLY = ("roofline", "cpu_baseline", "parity", "batched", "upload_inclusive", "marginalize", "backend_step", "vio_window", "sharded_window",
+             "sharded_window_c5")
+
+
 class _FakeBackend:
     """The part of capi.Backend that bench.dump_outputs reads: windows' sizes, get_deltas, get_ids."""
 
@@ -153,3 +164,37 @@ def test_bench_dump_outputs_of_the_timed_path(tmp_path):
     assert abs(arrays["summary"][0, 5] - s.final_cost) <= 1e-9 * abs(s.final_cost)
     assert np.array_equal(arrays["w0_kf_id"].astype(np.int64), w.kf_id) and np.array_equal(arrays["w0_lmk_id"].astype(np.int64), w.lmk_id)
     assert np.abs(arrays["w0_pose"] - d["pose"]).max() <= 1e-9 and np.abs(arrays["w0_lmk"] - d["lmk"]).max() <= 1e-8
+
+
+@pytest.mark.gpu
+def test_plain_run_carries_the_headline_alone():
+    """A plain run times the steps and prints the contract's fields: no other leg runs, none of their objects is in the line."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--solves-per-step", "5"]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_solve", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config"):
+        assert k in rec, k
+    assert not [k for k in FULL_ONLY if k in rec]
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["dtype"] == "f64" and rec["higher_is_better"] is True
+    assert rec["config"]["solves_per_step"] == 5 and rec["config"]["iterations_per_solve"] == 10
+    assert abs(rec["value"] - 5 * 10 / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 1e-3
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_selected_legs():
+    """--full with the slow legs switched off: the roofline's profiled pass and the upload-inclusive rate are in the line, the
+    legs its options skip are null."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--solves-per-step", "5", "--full",
+           "--batch", "0", "--no-cpu-baseline", "--no-marginalize", "--no-sharded", "--no-vio"]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert set(FULL_ONLY) <= set(rec)
+    assert rec["roofline"]["kernel"] in rec["roofline"]["kernels_us"] and rec["upload_inclusive"]["value"] > 0
+    assert rec["upload_inclusive"]["two_handles"]["value"] > 0
+    for k in ("cpu_baseline", "parity", "batched", "marginalize", "backend_step", "vio_window", "sharded_window", "sharded_window_c5"):
+        assert rec[k] is None, k

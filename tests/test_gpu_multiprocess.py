@@ -72,7 +72,7 @@ def test_bench_gpus_2_runs_two_ranks_or_refuses(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--solves-per-step", "20",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     if _gpu_count() < 2:
         assert r.returncode != 0 and "needs 2 GPUs" in r.stderr and r.stdout.strip() == ""
         return
