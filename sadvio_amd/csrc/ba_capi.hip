@@ -244,8 +244,7 @@ struct EnvCfg {
     int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
     double jacobi_tol = 1e-14;
     bool marg_last_small = false, marg_eig_mm = false, marg_pivoted = false, marg_unpivoted = false, pchol_swap = false, pchol_strict = false,
-         jacobi_b4 = false, jacobi_plain = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, wd_old = false, wd_nola = false, wd_r3 = false,
-         wd_back1 = false, imu_items = false;
+         jacobi_b4 = false, jacobi_plain = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false;
     void read() {
         auto on = [](const char* k) { return getenv(k) != nullptr; };
         auto num = [](const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; };
@@ -255,7 +254,7 @@ struct EnvCfg {
         marg_last_small = on("SADVIO_MARG_LAST_SMALL"); marg_eig_mm = on("SADVIO_MARG_EIG_MM"); marg_pivoted = on("SADVIO_MARG_PIVOTED");
         marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_swap = on("SADVIO_PCHOL_SWAP"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         jacobi_b4 = on("SADVIO_JACOBI_B4"); jacobi_plain = on("SADVIO_JACOBI_PLAIN"); no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
-        no_bcr = on("SADVIO_NO_BCR"); wd_old = on("SADVIO_WD_OLD"); wd_nola = on("SADVIO_WD_NOLA"); wd_r3 = on("SADVIO_WD_R3"); wd_back1 = on("SADVIO_WD_BACK1");
+        no_bcr = on("SADVIO_NO_BCR");
         imu_items = on("SADVIO_IMU_ITEMS");   // A/B: the IMU pairs' entries through k_solve's item loop (the pre-0.5 path) on one device too
     }
 };
@@ -1717,9 +1716,29 @@ double pchol_tau(int n, int eig_cut_mode) {
     return eig_cut_mode == SADVIO_EIG_CUT_NOISE_FLOOR ? 4.0 * n * 2.220446049250313e-16 : -1e-12 / std::max(n, 1);
 }
 
+// Wide-panel factorisation (dense_chol.h): k_wchol_diag16 on the first 96 columns, then one k_wchol_step per further 96. The lower
+// triangle of the N x N matrix A (leading dimension ld) is destroyed, y rides along as its right-hand side (-> L^-1 y). Lx (N x N,
+// leading dimension ld): the panels below the diagonal blocks, out of place; Ltw: ceil(N / 96) * WD_LT doubles, the diagonal blocks'
+// tiles; M: ceil(N / 96) 96 x 96 inverses of the diagonal blocks for k_wchol_backstep (null: factor only). dbg: phase stamps of the
+// second k_wchol_step (SADVIO_DEBUG & 4096).
+void launch_wfac(sadvio_ba_handle* h, double* A, long long ld, int N, double* y, double* Lx, double* Ltw, double* M, int* info, const int* skip, long long* dbg) {
+    const int nsteps = (N + WD - 1) / WD;
+    const size_t lds_d = sizeof(double) * wd16_lds_doubles() + 64, lds_st = sizeof(double) * wdstep_lds_doubles() + 64;
+    (void)hipFuncSetAttribute((const void*)k_wchol_diag16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
+    (void)hipFuncSetAttribute((const void*)k_wchol_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_st);
+    hipLaunchKernelGGL(k_wchol_diag16, dim3(1), dim3(SOLVE_THREADS), lds_d, h->stream, A, ld, y, (double*)nullptr, N, 0, info, skip, Ltw);
+    for (int st = 0; st + 1 < nsteps; st++) {
+        const int c0 = st * WD, m = N - (c0 + WD);
+        const int nt = (m + CH_TS - 1) / CH_TS;
+        hipLaunchKernelGGL(k_wchol_step, dim3(nt * (nt + 1) / 2 + 2), dim3(SOLVE_THREADS), lds_st, h->stream, A, ld, Lx, y,
+                           Ltw + (size_t)st * WD_LT, Ltw + (size_t)(st + 1) * WD_LT, M ? M + (size_t)st * WD * WD : nullptr,
+                           M ? M + (size_t)(st + 1) * WD * WD : nullptr, N, c0, info, skip, st == 1 ? dbg : nullptr);
+    }
+}
+
 // Unpivoted Cholesky of the symmetric positive definite n x n matrix whose lower triangle sits in V (leading dimension n; destroyed)
-// by the wide-panel solver of the dense reduced systems (dense_chol.h: k_wchol_diag16 + k_wchol_step, one launch per 96 columns), the
-// vector y riding along as its right-hand side (-> L^-1 y). Lx (n x n): the panels; Ltw: ceil(n / 96) * (WD_LT + 6 * 256) doubles for
+// by the wide-panel solver of the dense reduced systems (launch_wfac), the vector y riding along as its right-hand side (-> L^-1 y).
+// Lx (n x n): the panels; Ltw: ceil(n / 96) * (WD_LT + 6 * 256) doubles for
 // the diagonal blocks' tiles and their re-inverted diagonal tiles; A0 (leading dimension ld0): the original matrix, for the pivot test
 // (k_wfac_diag). Returns 1 = every pivot is safely positive (the factor is in Lx / Ltw, packed by k_wfac_pack), 0 = not (the caller
 // takes the rank-revealing route), -1 = HIP error. One host synchronisation.
@@ -1727,16 +1746,7 @@ int run_wfac(sadvio_ba_handle* h, double* V, int n, double* y, double* Lx, doubl
     const int nsteps = (n + WD - 1) / WD;
     double* Ld = Ltw + (size_t)nsteps * WD_LT;
     if (hipMemsetAsync(info, 0, sizeof(int) * 2, h->stream) != hipSuccess) return -1;
-    const size_t lds_st = sizeof(double) * wdstep_lds_doubles() + 64;
-    (void)hipFuncSetAttribute((const void*)k_wchol_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_st);
-    (void)hipFuncSetAttribute((const void*)k_wchol_diag16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * wd16_lds_doubles() + 64));
-    hipLaunchKernelGGL(k_wchol_diag16, dim3(1), dim3(SOLVE_THREADS), sizeof(double) * wd16_lds_doubles() + 64, h->stream, V, (long long)n, y, (double*)nullptr, n, 0, info, (const int*)nullptr, Ltw);
-    for (int st = 0; st + 1 < nsteps; st++) {
-        const int c0 = st * WD, mrem = n - (c0 + WD);
-        const int nt = (mrem + CH_TS - 1) / CH_TS;
-        hipLaunchKernelGGL(k_wchol_step, dim3(nt * (nt + 1) / 2 + 2), dim3(SOLVE_THREADS), lds_st, h->stream, V, (long long)n, Lx, y, Ltw + (size_t)st * WD_LT, Ltw + (size_t)(st + 1) * WD_LT,
-                           (double*)nullptr, (double*)nullptr, n, c0, info, (const int*)nullptr, (long long*)nullptr);
-    }
+    launch_wfac(h, V, (long long)n, n, y, Lx, Ltw, nullptr, info, nullptr, nullptr);
     hipLaunchKernelGGL(k_diag_max, dim3(1), dim3(256), 0, h->stream, A0, ld0, n, dmax);
     hipLaunchKernelGGL(k_wfac_diag, dim3(nsteps * WD_T), dim3(64), 0, h->stream, Ltw, n, A0, ld0, tau_rel, dmax, 1024.0 * n * 2.220446049250313e-16, Ld, info + 1);
     int st2[2] = {0, 0};
@@ -2730,6 +2740,154 @@ int sadvio_ba_comm_info(sadvio_ba_handle* h, int32_t* nranks, int32_t* rank, int
     return SADVIO_OK;
 }
 
+namespace {
+// The reduced system of an out-of-LDS window (N_p > MAX_LDS_NP) is factored and solved in HBM by one of five routes (dense_chol.h),
+// chosen once per solve call (BigPlan::choose).
+enum class BigRoute {
+    band,           // block-banded: one workgroup slides an LDS window down the band (k_band_solve)
+    band_twisted,   // long band: the twisted factorisation, both ends at once (k_band_solve x 2 + k_band_mid)
+    bcr,            // very long band of one window: block cyclic reduction over the bw x bw blocks (k_bcr_*)
+    wide,           // not banded, N >= 2 * WD: 96-column panels on the matrix cores (launch_wfac + k_wchol_backstep)
+    panel,          // not banded, N < 2 * WD: 32-column panels (k_chol_panel / k_chol_update / k_chol_backsolve)
+};
+struct BigPlan {
+    BigRoute route = BigRoute::panel;
+    int bw = 0;                   // rows below a block column of S that can be non-zero (block half-bandwidth + 1) * dpf
+    int C = 0;                    // band window of the band routes
+    long long linv_off = 0, mid_off = 0, M_off = 0, Lx_off = 0;   // the window's share of d_big_linv / d_big_mid / d_big_M / d_big_Lx
+    bool banded() const { return route == BigRoute::band || route == BigRoute::band_twisted || route == BigRoute::bcr; }
+    // route and C from bw; on a sharded window bw is the all-reduced one, so every rank takes the same route
+    void choose(const WinDev& d, int n_win, const EnvCfg& env) {
+        const int N = d.Np, nb = d.dpf == 6 ? 6 : 5;
+        if (!(bw < N && bw + nb <= MAX_LDS_NP)) {
+            route = N >= 2 * WD ? BigRoute::wide : BigRoute::panel;
+            return;
+        }
+        // with the update trimmed to the band a step costs the same in any window: the largest window that fits amortises the
+        // per-window carry / load / store best (SADVIO_BAND_C overrides, for measurements)
+        C = std::max(nb, (MAX_LDS_NP - bw) / nb * nb);
+        if (env.band_c > 0) C = std::max(nb, std::min(C, env.band_c / nb * nb));
+        const int Kb = (N + bw - 1) / bw;
+        if (nb == 6 && Kb >= 22 && 2 * bw <= MAX_LDS_NP - 1 && n_win == 1 && !env.no_bcr) route = BigRoute::bcr;   // below ~22 blocks the twisted solver wins (measured)
+        else if (N - bw >= 4 * C) route = BigRoute::band_twisted;
+        else route = BigRoute::band;
+    }
+};
+
+// LDS of the band kernels (k_band_solve, k_band_mid, k_bcr_elim / root): the in-LDS solver's window of R rows (pivot strip, packed
+// triangle + rhs row, two vectors) and `blocks` inverse pivot blocks of nb x nb
+size_t band_lds_bytes(int R, int nb, int blocks) {
+    return sizeof(double) * ((size_t)(R + 2) * 6 + (size_t)(R + 1) * (R + 2) / 2 + 2 * (size_t)R + (size_t)blocks * nb * nb) + 64;
+}
+
+// The routes: S (leading dimension d.ld) and y = gred of window d in place; dbg: SADVIO_DEBUG & 4096 stamps of this slot
+void solve_band(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
+    const int N = d.Np, bw = p.bw, C = p.C, nb = d.dpf == 6 ? 6 : 5;
+    const int Rmax = bw + C;
+    const size_t lds = band_lds_bytes(Rmax, nb, Rmax / nb + 1);
+    auto kbs = d.dpf == 6 ? k_band_solve<6> : k_band_solve<5>;
+    (void)hipFuncSetAttribute((const void*)kbs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    long long* ts = dbg ? h->d_dbg.p + 44 : nullptr;
+    double* lv = h->d_big_linv.p + p.linv_off;
+    if (p.route == BigRoute::band) {
+        hipLaunchKernelGGL(kbs, dim3(1), dim3(SOLVE_THREADS), lds, h->stream, S, (long long)d.ld, y, lv, N, bw, C, info, skip, ts, -1, 0, (double*)nullptr);
+        return;
+    }
+    const int M = (N - bw) / 2 / nb * nb;
+    double* md = h->d_big_mid.p + p.mid_off;
+    auto kbm = d.dpf == 6 ? k_band_mid<6> : k_band_mid<5>;
+    const size_t lds_m = band_lds_bytes(bw, nb, bw / nb + 1);
+    (void)hipFuncSetAttribute((const void*)kbm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
+    if (dbg) fprintf(stderr, "[sadvio dbg] twisted band solve N %d bw %d C %d M %d\n", N, bw, C, M);
+    hipLaunchKernelGGL(kbs, dim3(2), dim3(SOLVE_THREADS), lds, h->stream, S, (long long)d.ld, y, lv, N, bw, C, info, skip, ts, M, 0, md);
+    hipLaunchKernelGGL(kbm, dim3(1), dim3(SOLVE_THREADS), lds_m, h->stream, S, (long long)d.ld, y, N, bw, M, md, info, skip);
+    hipLaunchKernelGGL(kbs, dim3(2), dim3(SOLVE_THREADS), lds, h->stream, S, (long long)d.ld, y, lv, N, bw, C, info, skip, ts, M, 1, md);
+}
+
+size_t bcr_doubles(int N, int bw) {
+    const size_t b = (size_t)bw, K = ((size_t)N + b - 1) / b;
+    return K * (8 * b * b + b * (b + 1) / 2 + (b / 6) * 36 + 5 * b);
+}
+
+void solve_bcr(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
+    const int N = d.Np, bw = p.bw, Kb = (N + bw - 1) / bw;
+    const size_t b = (size_t)bw, bb = b * b, K = (size_t)Kb;
+    BcrPtrs B{};
+    double* q = h->d_bcr.p;
+    B.D = q; q += K * bb; B.E = q; q += K * bb; B.Wp = q; q += K * bb; B.Wn = q; q += K * bb;
+    B.Ul = q; q += K * bb; B.Ur = q; q += K * bb;
+    B.Lp = q; q += K * (b * (b + 1) / 2); B.linv = q; q += K * (b / 6) * 36;
+    B.g = q; q += K * b; B.yv = q; q += K * b; B.gl = q; q += K * b; B.gr = q; q += K * b; B.X = q; q += K * b;
+    B.K = Kb; B.b = bw; B.N = N;
+    const size_t lds_e = band_lds_bytes(2 * bw, 6, bw / 6 + 1);
+    const size_t lds_c = sizeof(double) * 2 * b * (b + 1);
+    const size_t lds_r = band_lds_bytes(2 * bw, 6, 2 * (bw / 6 + 1));   // up to two blocks, all 2 b / 6 pivot blocks kept
+    const size_t lds_b = sizeof(double) * (b * (b + 1) / 2 + 4 * b + (b / 6) * 36);
+    (void)hipFuncSetAttribute((const void*)k_bcr_elim<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e);
+    (void)hipFuncSetAttribute((const void*)k_bcr_combine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
+    (void)hipFuncSetAttribute((const void*)k_bcr_root<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
+    (void)hipFuncSetAttribute((const void*)k_bcr_back<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+    hipLaunchKernelGGL(k_bcr_extract, dim3(Kb), dim3(256), 0, h->stream, S, (long long)d.ld, y, B, skip, info);
+    int smax = 0, s_root = 0;
+    for (int sst = 1; sst < Kb; sst *= 2) {
+        const int na = (Kb + sst - 1) / sst;
+        if (na == 2) { s_root = sst; break; }   // two blocks left: solved together by k_bcr_root
+        hipLaunchKernelGGL(k_bcr_elim<6>, dim3(na / 2, 2), dim3(SOLVE_THREADS), lds_e, h->stream, B, sst, info, skip);
+        hipLaunchKernelGGL(k_bcr_combine, dim3(na), dim3(512), lds_c, h->stream, B, sst, info, skip);
+        smax = sst;
+    }
+    hipLaunchKernelGGL(k_bcr_root<6>, dim3(1), dim3(SOLVE_THREADS), lds_r, h->stream, B, s_root, info, skip);
+    for (int sst = smax; sst >= 1; sst /= 2) {
+        const int na = (Kb + sst - 1) / sst;
+        hipLaunchKernelGGL(k_bcr_back<6>, dim3(na / 2), dim3(256), lds_b, h->stream, B, sst, info, skip);
+    }
+    hipLaunchKernelGGL(k_bcr_writeback, dim3((N + 255) / 256), dim3(256), 0, h->stream, B, y, info, skip);
+    if (dbg) fprintf(stderr, "[sadvio dbg] block cyclic reduction N %d bw %d K %d\n", N, bw, Kb);
+}
+
+void solve_wide(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
+    const int N = d.Np, nsteps = (N + WD - 1) / WD;
+    double* M = h->d_big_M.p + p.M_off;
+    double* Ltw = M + (size_t)nsteps * WD * WD;
+    (void)hipFuncSetAttribute((const void*)k_wchol_backstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * WD * WDS));
+    launch_wfac(h, S, (long long)d.ld, N, y, h->d_big_Lx.p + p.Lx_off, Ltw, M, info, skip, dbg ? h->d_dbg.p + 106 : nullptr);
+    for (int bs = nsteps - 1; bs >= 0; bs--)
+        hipLaunchKernelGGL(k_wchol_backstep, dim3(1 + (bs + 1 < nsteps ? (bs * WD + 63) / 64 : 0)), dim3(SOLVE_THREADS), sizeof(double) * WD * WDS, h->stream,
+                           h->d_big_Lx.p + p.Lx_off, (long long)d.ld, y, M, N, bs, info, skip);
+}
+
+void solve_panel(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
+    const int N = d.Np;
+    for (int k0 = 0; k0 < N; k0 += CH_NB) {
+        const int nb = std::min(CH_NB, N - k0), s0 = k0 + nb;
+        const int rows_end = std::min(N, s0 + p.bw), m = rows_end - s0;
+        hipLaunchKernelGGL(k_chol_panel, dim3((m + 1 + CH_THREADS - 1) / CH_THREADS), dim3(CH_THREADS), 0, h->stream,
+                           S, (long long)d.ld, y, N, k0, rows_end, info, skip, dbg && k0 == 64 ? h->d_dbg.p + 44 : nullptr);
+        if (m > 0) {
+            const int nt = (m + CH_TS - 1) / CH_TS;
+            hipLaunchKernelGGL(k_chol_update, dim3(nt * (nt + 1) / 2 + (m + CH_THREADS - 1) / CH_THREADS), dim3(CH_THREADS), 0,
+                               h->stream, S, (long long)d.ld, y, N, k0, rows_end, info, skip);
+        }
+    }
+    hipLaunchKernelGGL(k_chol_backsolve, dim3(1), dim3(CH_THREADS), 0, h->stream, S, (long long)d.ld, y, N, p.bw, info, skip);
+}
+
+// Cholesky + solve of the reduced system of out-of-LDS window w at slot s by the route of its plan
+void solve_big(sadvio_ba_handle* h, const BigPlan& p, int w, int s, int stride, bool dbg) {
+    const WinDev& d = h->wins[w].d;
+    double* S = h->d_S.p + d.S_off;
+    double* y = h->d_gred.p + d.red_off;
+    int* info = h->d_big_info.p + w;
+    const int* skip = (const int*)((const char*)(h->d_states.p + (size_t)w * stride + s) + offsetof(LmState, done));
+    switch (p.route) {
+        case BigRoute::band: case BigRoute::band_twisted: solve_band(h, d, p, S, y, info, skip, dbg); break;
+        case BigRoute::bcr: solve_bcr(h, d, p, S, y, info, skip, dbg); break;
+        case BigRoute::wide: solve_wide(h, d, p, S, y, info, skip, dbg); break;
+        case BigRoute::panel: solve_panel(h, d, p, S, y, info, skip, dbg); break;
+    }
+}
+}  // namespace
+
 int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvio_solve_summary* summaries) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "solve before set_windows"; return SADVIO_E_STATE; }
@@ -2852,7 +3010,7 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
     const int reset_blocks = (int)std::min<long long>(1024, std::max<long long>(1, (P.n_xl + P.n_xp + 255) / 256));
     // rows below a block column of S that can be non-zero: (block half-bandwidth + 1) * dpf from the co-visibility
     // structure and the IMU pairs; a dense prior fills the kept-landmark block, so those windows are dense
-    std::vector<int> big_bw(n_win, 0);
+    std::vector<BigPlan> big(n_win);
     for (int w = 0; w < n_win; w++) {
         const WinDev& d = h->wins[w].d;
         if (!d.ld) continue;
@@ -2867,44 +3025,40 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
                     const int fi = h->h_kf_fidx[d.kf_base + sp.kf], fj = h->h_kf_fidx[d.kf_base + sp.kf_b];
                     if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
                 }
-        big_bw[w] = (d.n_red > 0 || d.dp_n_full > 0 || d.line_end > d.line_begin) ? d.Np : std::min(d.Np, (hb + 1) * d.dpf);
+        big[w].bw = (d.n_red > 0 || d.dp_n_full > 0 || d.line_end > d.line_begin) ? d.Np : std::min(d.Np, (hb + 1) * d.dpf);
     }
     if (h->coll_fn && h->world > 1 && h->n_big) {
         // every rank must factor the all-reduced S with the same (largest) bandwidth: gather the local ones
         std::vector<double> slots((size_t)n_win * h->world * 4, 0.0);
-        for (int w = 0; w < n_win; w++) slots[((size_t)w * h->world + h->rank) * 4] = (double)big_bw[w];
+        for (int w = 0; w < n_win; w++) slots[((size_t)w * h->world + h->rank) * 4] = (double)big[w].bw;
         HIP_TRY(hipMemcpyAsync(h->d_rank_s.p, slots.data(), slots.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         if (h->coll_fn(h->coll_ctx, h->d_rank_s.p, (int64_t)slots.size(), (void*)h->stream) != 0) { h->err = "solve: all-reduce failed"; return SADVIO_E_RCCL; }
         HIP_TRY(hipMemcpyAsync(slots.data(), h->d_rank_s.p, slots.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         for (int w = 0; w < n_win; w++)
-            for (int r = 0; r < h->world; r++) big_bw[w] = std::max(big_bw[w], (int)slots[((size_t)w * h->world + r) * 4]);
+            for (int r = 0; r < h->world; r++) big[w].bw = std::max(big[w].bw, (int)slots[((size_t)w * h->world + r) * 4]);
     }
-    std::vector<long long> big_linv_off(n_win, 0), big_M_off(n_win, 0), big_mid_off(n_win, 0), big_Lx_off(n_win, 0);
     {
-        long long totm = 0;
-        for (int w = 0; w < n_win; w++)
-            if (h->wins[w].d.ld) { const long long b = std::min(big_bw[w], MAX_LDS_NP); big_mid_off[w] = totm; totm += 2 * (b * (b + 1) / 2 + b); }
-        HIP_TRY(h->d_big_mid.alloc((size_t)std::max<long long>(totm, 1)));
-        // workspace of the block cyclic reduction (one banded window with >= 22 diagonal blocks): allocated here, never
-        // inside the (possibly captured) launch sequence
-        if (n_win == 1 && h->wins[0].d.ld && h->wins[0].d.dpf == 6) {
-            const size_t b = (size_t)big_bw[0], K = ((size_t)h->wins[0].d.Np + b - 1) / std::max<size_t>(b, 1);
-            if (b > 0 && K >= 22 && 2 * b <= (size_t)MAX_LDS_NP - 1) HIP_TRY(h->d_bcr.alloc(K * (8 * b * b + b * (b + 1) / 2 + (b / 6) * 36 + 5 * b)));
-        }
-        long long totM = 0;
-        for (int w = 0; w < n_win; w++) if (h->wins[w].d.ld) { big_M_off[w] = totM; totM += (long long)((h->wins[w].d.Np + WD - 1) / WD) * (WD * WD + WD_LT); }   // M | the factors' tiles
-        HIP_TRY(h->d_big_M.alloc((size_t)std::max<long long>(totM, 1)));
-        long long totL = 0;      // out-of-place panels of the dense wide-panel solver (k_wchol_step)
+        // the route of every out-of-LDS window and the workspace it needs, allocated here, never inside the (possibly captured) launch sequence
+        long long totv = 0, totm = 0, totM = 0, totL = 0;
         for (int w = 0; w < n_win; w++) {
             const WinDev& d = h->wins[w].d;
-            const int nbp = d.dpf == 6 ? 6 : 5;
-            if (d.ld && !(big_bw[w] < d.Np && big_bw[w] + nbp <= MAX_LDS_NP) && d.Np >= 2 * WD) { big_Lx_off[w] = totL; totL += (long long)d.Np * d.ld; }
+            if (!d.ld) continue;
+            BigPlan& p = big[w];
+            p.choose(d, n_win, h->env);
+            const long long b = p.bw;
+            if (p.route == BigRoute::band || p.route == BigRoute::band_twisted) { p.linv_off = totv; totv += 6LL * d.Np; }
+            if (p.route == BigRoute::band_twisted) { p.mid_off = totm; totm += 2 * (b * (b + 1) / 2 + b); }
+            if (p.route == BigRoute::bcr) HIP_TRY(h->d_bcr.alloc(bcr_doubles(d.Np, p.bw)));   // (one window only)
+            if (p.route == BigRoute::wide) {
+                p.M_off = totM; totM += (long long)((d.Np + WD - 1) / WD) * (WD * WD + WD_LT);   // M | the factors' tiles
+                p.Lx_off = totL; totL += (long long)d.Np * d.ld;                              // the out-of-place panels
+            }
         }
+        HIP_TRY(h->d_big_linv.alloc((size_t)std::max<long long>(totv, 1)));
+        HIP_TRY(h->d_big_mid.alloc((size_t)std::max<long long>(totm, 1)));
+        HIP_TRY(h->d_big_M.alloc((size_t)std::max<long long>(totM, 1)));
         HIP_TRY(h->d_big_Lx.alloc((size_t)std::max<long long>(totL, 1)));
-        long long tot = 0;
-        for (int w = 0; w < n_win; w++) if (h->wins[w].d.ld) { big_linv_off[w] = tot; tot += 6LL * h->wins[w].d.Np; }
-        HIP_TRY(h->d_big_linv.alloc((size_t)std::max<long long>(tot, 1)));
     }
     int dp_max_nf = 0, dp_max_n = 0;
     for (int w = 0; w < n_win; w++) { dp_max_nf = std::max(dp_max_nf, h->wins[w].d.dp_n_full); dp_max_n = std::max(dp_max_n, h->wins[w].d.dp_n); }
@@ -2949,15 +3103,15 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
                 { ScopedTimer t(h, "k_rank_partials"); hipLaunchKernelGGL(k_rank_partials, dim3(n_win), dim3(64), 0, h->stream, P, s, 0); }
                 ScopedTimer t(h, "allreduce_reduced_system");
                 const WinDev& d0 = h->wins[0].d;
-                if (n_win == 1 && d0.ld && big_bw[0] < d0.Np && d0.S_off == 0) {
+                if (n_win == 1 && d0.ld && big[0].bw < d0.Np && d0.S_off == 0) {
                     // one banded window spanning the devices: only the band of S travels (dense_chol.h: k_band_pack)
-                    const long long nbd = (long long)d0.Np * big_bw[0], tail = h->red_total - (long long)d0.Np * d0.ld;
+                    const long long nbd = (long long)d0.Np * big[0].bw, tail = h->red_total - (long long)d0.Np * d0.ld;
                     if (h->d_coll_band.alloc((size_t)(nbd + tail)) != hipSuccess) coll_failed = true;
                     else {
                         const int pb = (int)std::min<long long>((nbd + tail + 255) / 256, 2048);
-                        hipLaunchKernelGGL(k_band_pack, dim3(pb), dim3(256), 0, h->stream, h->d_S.p, (long long)d0.ld, d0.Np, big_bw[0], tail, h->d_coll_band.p, 0);
+                        hipLaunchKernelGGL(k_band_pack, dim3(pb), dim3(256), 0, h->stream, h->d_S.p, (long long)d0.ld, d0.Np, big[0].bw, tail, h->d_coll_band.p, 0);
                         if (h->coll_fn(h->coll_ctx, h->d_coll_band.p, (int64_t)(nbd + tail), (void*)h->stream) != 0) coll_failed = true;
-                        hipLaunchKernelGGL(k_band_pack, dim3(pb), dim3(256), 0, h->stream, h->d_S.p, (long long)d0.ld, d0.Np, big_bw[0], tail, h->d_coll_band.p, 1);
+                        hipLaunchKernelGGL(k_band_pack, dim3(pb), dim3(256), 0, h->stream, h->d_S.p, (long long)d0.ld, d0.Np, big[0].bw, tail, h->d_coll_band.p, 1);
                     }
                 } else if (h->coll_fn(h->coll_ctx, h->d_S.p, (int64_t)h->red_total, (void*)h->stream) != 0) coll_failed = true;
             }
@@ -2969,177 +3123,17 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
             if (h->n_big) {
                 { ScopedTimer t(h, "k_solve_front"); hipLaunchKernelGGL(ks1, dim3(n_win), dim3(SOLVE_THREADS), 64, h->stream, P, s); }
                 {
-                    // Cholesky + solve of S, gred in place (dense_chol.h): banded systems by one sliding-window launch,
-                    // dense ones (a dense prior fills the kept-landmark block) by two launches per 32 columns
                     ScopedTimer t(h, "reduced_cholesky_solve");
-                    for (int w = 0; w < n_win; w++) {
-                        const WinDev& d = h->wins[w].d;
-                        if (!d.ld) continue;
-                        double* Sw = h->d_S.p + d.S_off;
-                        double* yw = h->d_gred.p + d.red_off;
-                        int* info = h->d_big_info.p + w;
-                        const int* skip = (const int*)((const char*)(h->d_states.p + (size_t)w * stride + s) + offsetof(LmState, done));
-                        const int N = d.Np, bw = big_bw[w];
-                        const int nb = d.dpf == 6 ? 6 : 5;
-                        if (bw < N && bw + nb <= MAX_LDS_NP) {
-                            // block-banded system: one workgroup slides an LDS window down the band (dense_chol.h)
-                            // with the update trimmed to the band a step costs the same in any window: the largest window that fits
-                            // amortises the per-window carry / load / store best (SADVIO_BAND_C overrides, for measurements)
-                            int C = std::max(nb, (MAX_LDS_NP - bw) / nb * nb);
-                            if (h->env.band_c > 0) C = std::max(nb, std::min(C, h->env.band_c / nb * nb));
-                            const int Rmax = bw + C;
-                            const size_t lds = sizeof(double) * ((size_t)(Rmax + 2) * 6 + (size_t)(Rmax + 1) * (Rmax + 2) / 2 + 2 * (size_t)Rmax +
-                                                                 (size_t)(Rmax / nb + 1) * nb * nb) + 64;
-                            auto kbs = d.dpf == 6 ? k_band_solve<6> : k_band_solve<5>;
-                            (void)hipFuncSetAttribute((const void*)kbs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                            long long* dbg = (P.debug & 4096) && s == 3 ? h->d_dbg.p + 44 : nullptr;
-                            double* lv = h->d_big_linv.p + big_linv_off[w];
-                            const int Kb = (N + bw - 1) / bw;
-                            if (nb == 6 && Kb >= 22 && 2 * bw <= MAX_LDS_NP - 1 && n_win == 1 && !h->env.no_bcr) {   // below ~22 blocks the twisted solver wins (measured)
-                                // very long band: block cyclic reduction over the bw x bw blocks, log2(K) levels (dense_chol.h)
-                                const size_t b = (size_t)bw, bb = b * b, K = (size_t)Kb;
-                                const size_t per = 8 * bb + b * (b + 1) / 2 + (b / 6) * 36 + 5 * b;
-                                BcrPtrs B{};
-                                double* q = h->d_bcr.p;
-                                B.D = q; q += K * bb; B.E = q; q += K * bb; B.Wp = q; q += K * bb; B.Wn = q; q += K * bb;
-                                B.Ul = q; q += K * bb; B.Ur = q; q += K * bb;
-                                B.Lp = q; q += K * (b * (b + 1) / 2); B.linv = q; q += K * (b / 6) * 36;
-                                B.g = q; q += K * b; B.yv = q; q += K * b; B.gl = q; q += K * b; B.gr = q; q += K * b; B.X = q; q += K * b;
-                                B.K = Kb; B.b = bw; B.N = N;
-                                const int R2 = 2 * bw;
-                                const size_t lds_e = sizeof(double) * ((size_t)(R2 + 2) * 6 + (size_t)(R2 + 1) * (R2 + 2) / 2 + 2 * (size_t)R2 + (size_t)(bw / 6 + 1) * 36) + 64;
-                                const size_t lds_c = sizeof(double) * 2 * b * (b + 1);
-                                const size_t lds_r = lds_e + sizeof(double) * (size_t)(bw / 6 + 1) * 36;   // up to two blocks, all 2 b / 6 pivot blocks kept
-                                const size_t lds_b = sizeof(double) * (b * (b + 1) / 2 + 4 * b + (b / 6) * 36);
-                                (void)hipFuncSetAttribute((const void*)k_bcr_elim<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e);
-                                (void)hipFuncSetAttribute((const void*)k_bcr_combine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-                                (void)hipFuncSetAttribute((const void*)k_bcr_root<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-                                (void)hipFuncSetAttribute((const void*)k_bcr_back<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-                                hipLaunchKernelGGL(k_bcr_extract, dim3(Kb), dim3(256), 0, h->stream, Sw, (long long)d.ld, yw, B, skip, info);
-                                int smax = 0, s_root = 0;
-                                for (int sst = 1; sst < Kb; sst *= 2) {
-                                    const int na = (Kb + sst - 1) / sst;
-                                    if (na == 2) { s_root = sst; break; }   // two blocks left: solved together by k_bcr_root
-                                    hipLaunchKernelGGL(k_bcr_elim<6>, dim3(na / 2, 2), dim3(SOLVE_THREADS), lds_e, h->stream, B, sst, info, skip);
-                                    hipLaunchKernelGGL(k_bcr_combine, dim3(na), dim3(512), lds_c, h->stream, B, sst, info, skip);
-                                    smax = sst;
-                                }
-                                hipLaunchKernelGGL(k_bcr_root<6>, dim3(1), dim3(SOLVE_THREADS), lds_r, h->stream, B, s_root, info, skip);
-                                for (int sst = smax; sst >= 1; sst /= 2) {
-                                    const int na = (Kb + sst - 1) / sst;
-                                    hipLaunchKernelGGL(k_bcr_back<6>, dim3(na / 2), dim3(256), lds_b, h->stream, B, sst, info, skip);
-                                }
-                                hipLaunchKernelGGL(k_bcr_writeback, dim3((N + 255) / 256), dim3(256), 0, h->stream, B, yw, info, skip);
-                                if (dbg) fprintf(stderr, "[sadvio dbg] block cyclic reduction N %d bw %d K %d\n", N, bw, Kb);
-                            } else if (N - bw >= 4 * C) {
-                                // long band: twisted factorisation, both ends at once (dense_chol.h)
-                                const int M = (N - bw) / 2 / nb * nb;
-                                double* md = h->d_big_mid.p + big_mid_off[w];
-                                auto kbm = d.dpf == 6 ? k_band_mid<6> : k_band_mid<5>;
-                                const size_t lds_m = sizeof(double) * ((size_t)(bw + 2) * 6 + (size_t)(bw + 1) * (bw + 2) / 2 + 2 * (size_t)bw + (size_t)(bw / nb + 1) * nb * nb) + 64;
-                                (void)hipFuncSetAttribute((const void*)kbm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
-                                if (dbg) fprintf(stderr, "[sadvio dbg] twisted band solve N %d bw %d C %d M %d\n", N, bw, C, M);
-                                hipLaunchKernelGGL(kbs, dim3(2), dim3(SOLVE_THREADS), lds, h->stream, Sw, (long long)d.ld, yw, lv, N, bw, C, info, skip, dbg, M, 0, md);
-                                hipLaunchKernelGGL(kbm, dim3(1), dim3(SOLVE_THREADS), lds_m, h->stream, Sw, (long long)d.ld, yw, N, bw, M, md, info, skip);
-                                hipLaunchKernelGGL(kbs, dim3(2), dim3(SOLVE_THREADS), lds, h->stream, Sw, (long long)d.ld, yw, lv, N, bw, C, info, skip, dbg, M, 1, md);
-                            } else {
-                                hipLaunchKernelGGL(kbs, dim3(1), dim3(SOLVE_THREADS), lds, h->stream, Sw, (long long)d.ld, yw, lv, N, bw, C, info, skip, dbg, -1, 0, (double*)nullptr);
-                            }
-                            continue;
-                        }
-                        if (N >= 2 * WD) {
-                            // dense system: 96-column panels through the LDS solver + MFMA panel / update kernels
-                            double* Mw = h->d_big_M.p + big_M_off[w];
-                            const size_t lds_d = sizeof(double) * ((size_t)(WD + 2) * 6 + (size_t)(WD + 1) * (WD + 2) / 2 + 2 * WD + 2 * WD_NBK * 36 + (size_t)WD * (WD + 1)) + 64;
-                            const size_t lds_t = sizeof(double) * (size_t)(CH_TS + WD) * WDS;
-                            const size_t lds_s = sizeof(double) * 2 * (size_t)CH_TS * WDS;
-                            (void)hipFuncSetAttribute((const void*)k_wchol_diag, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-                            (void)hipFuncSetAttribute((const void*)k_wchol_diag16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * wd16_lds_doubles() + 64));
-                            const bool wd16 = !h->env.wd_old;   // the 96 x 96 diagonal blocks on 16 x 16 MFMA tiles (chol16.h); the 6-column LDS solver for A/B runs
-                            (void)hipFuncSetAttribute((const void*)k_wchol_trsm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-                            (void)hipFuncSetAttribute((const void*)k_wchol_syrk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-                            (void)hipFuncSetAttribute((const void*)k_wchol_backsolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * WD * WDS));
-                            const bool wdla = wd16 && !h->env.wd_nola;   // look-ahead: the next diagonal block inside the trailing-update launch
-                            const size_t lds_la = std::max(sizeof(double) * wdla_lds_doubles() + 64, lds_s);
-                            (void)hipFuncSetAttribute((const void*)k_wchol_syrk_la, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_la);
-                            (void)hipFuncSetAttribute((const void*)k_wchol_trsm8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-                            const bool wdstep = wdla && !h->env.wd_r3;     // one launch per panel (round 4); SADVIO_WD_R3 = the trsm8 + syrk_la loop
-                            if (wdstep) {
-                                const int nsteps = (N + WD - 1) / WD;
-                                double* Ltw = Mw + (size_t)nsteps * WD * WD;
-                                double* Lx = h->d_big_Lx.p + big_Lx_off[w];
-                                const size_t lds_st = sizeof(double) * wdstep_lds_doubles() + 64;
-                                (void)hipFuncSetAttribute((const void*)k_wchol_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_st);
-                                (void)hipFuncSetAttribute((const void*)k_wchol_backstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * WD * WDS));
-                                hipLaunchKernelGGL(k_wchol_diag16, dim3(1), dim3(SOLVE_THREADS), sizeof(double) * wd16_lds_doubles() + 64, h->stream, Sw, (long long)d.ld, yw, (double*)nullptr, N, 0, info, skip, Ltw);
-                                for (int st = 0; st + 1 < nsteps; st++) {
-                                    const int c0 = st * WD, m = N - (c0 + WD);
-                                    const int nt = (m + CH_TS - 1) / CH_TS;
-                                    hipLaunchKernelGGL(k_wchol_step, dim3(nt * (nt + 1) / 2 + 2), dim3(SOLVE_THREADS), lds_st, h->stream, Sw, (long long)d.ld, Lx, yw,
-                                                       Ltw + (size_t)st * WD_LT, Ltw + (size_t)(st + 1) * WD_LT, Mw + (size_t)st * WD * WD, Mw + (size_t)(st + 1) * WD * WD, N, c0, info, skip,
-                                                       (P.debug & 4096) && s == 3 && st == 1 ? h->d_dbg.p + 106 : (long long*)nullptr);
-                                }
-                                for (int bs = nsteps - 1; bs >= 0; bs--)
-                                    hipLaunchKernelGGL(k_wchol_backstep, dim3(1 + (bs + 1 < nsteps ? (bs * WD + 63) / 64 : 0)), dim3(SOLVE_THREADS), sizeof(double) * WD * WDS, h->stream,
-                                                       Lx, (long long)d.ld, yw, Mw, N, bs, info, skip);
-                                continue;
-                            }
-                            int st = 0;
-                            for (int c0 = 0; c0 < N; c0 += WD, st++) {
-                                if (wdla) {
-                                    if (c0 == 0) hipLaunchKernelGGL(k_wchol_diag16, dim3(1), dim3(SOLVE_THREADS), sizeof(double) * wd16_lds_doubles() + 64, h->stream, Sw, (long long)d.ld, yw, Mw, N, 0, info, skip);
-                                    const int m = N - (c0 + WD);
-                                    if (m > 0) {
-                                        const int nt = (m + CH_TS - 1) / CH_TS;
-                                        hipLaunchKernelGGL(k_wchol_trsm8, dim3(nt), dim3(SOLVE_THREADS), lds_t, h->stream, Sw, (long long)d.ld, Mw + (size_t)st * WD * WD, N, c0, info, skip);
-                                        hipLaunchKernelGGL(k_wchol_syrk_la, dim3(nt * (nt + 1) / 2 + (m + SOLVE_THREADS - 1) / SOLVE_THREADS + 1), dim3(SOLVE_THREADS), lds_la, h->stream,
-                                                           Sw, (long long)d.ld, yw, Mw + (size_t)(st + 1) * WD * WD, N, c0, info, skip,
-                                                           (P.debug & 4096) && s == 3 && c0 == WD ? h->d_dbg.p + 90 : (long long*)nullptr);
-                                    }
-                                    continue;
-                                }
-                                if (wd16) hipLaunchKernelGGL(k_wchol_diag16, dim3(1), dim3(SOLVE_THREADS), sizeof(double) * wd16_lds_doubles() + 64, h->stream, Sw, (long long)d.ld, yw, Mw + (size_t)st * WD * WD, N, c0, info, skip);
-                                else
-                                hipLaunchKernelGGL(k_wchol_diag, dim3(1), dim3(SOLVE_THREADS), lds_d, h->stream, Sw, (long long)d.ld, yw, Mw + (size_t)st * WD * WD, N, c0, info, skip);
-                                const int m = N - (c0 + WD);
-                                if (m > 0) {
-                                    const int nt = (m + CH_TS - 1) / CH_TS;
-                                    hipLaunchKernelGGL(k_wchol_trsm, dim3(nt), dim3(CH_THREADS), lds_t, h->stream, Sw, (long long)d.ld, Mw + (size_t)st * WD * WD, N, c0, info, skip);
-                                    hipLaunchKernelGGL(k_wchol_syrk, dim3(nt * (nt + 1) / 2 + (m + CH_THREADS - 1) / CH_THREADS), dim3(CH_THREADS), lds_s, h->stream, Sw, (long long)d.ld, yw, N, c0, info, skip);
-                                }
-                            }
-                            if (wdla && !h->env.wd_back1) {
-                                // back-substitution: one launch per super-step (dense_chol.h: k_wchol_backstep)
-                                (void)hipFuncSetAttribute((const void*)k_wchol_backstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * WD * WDS));
-                                const int nsteps = (N + WD - 1) / WD;
-                                for (int bs = nsteps - 1; bs >= 0; bs--)
-                                    hipLaunchKernelGGL(k_wchol_backstep, dim3(1 + (bs + 1 < nsteps ? (bs * WD + 63) / 64 : 0)), dim3(SOLVE_THREADS), sizeof(double) * WD * WDS, h->stream,
-                                                       Sw, (long long)d.ld, yw, Mw, N, bs, info, skip);
-                            } else
-                            hipLaunchKernelGGL(k_wchol_backsolve, dim3(1), dim3(SOLVE_THREADS), sizeof(double) * WD * WDS, h->stream, Sw, (long long)d.ld, yw, Mw, N, info, skip);
-                            continue;
-                        }
-                        for (int k0 = 0; k0 < N; k0 += CH_NB) {
-                            const int nb = std::min(CH_NB, N - k0), s0 = k0 + nb;
-                            const int rows_end = std::min(N, s0 + bw), m = rows_end - s0;
-                            hipLaunchKernelGGL(k_chol_panel, dim3((m + 1 + CH_THREADS - 1) / CH_THREADS), dim3(CH_THREADS), 0, h->stream,
-                                               Sw, (long long)d.ld, yw, N, k0, rows_end, info, skip, (P.debug & 4096) && s == 3 && k0 == 64 ? h->d_dbg.p + 44 : nullptr);
-                            if (m > 0) {
-                                const int nt = (m + CH_TS - 1) / CH_TS;
-                                hipLaunchKernelGGL(k_chol_update, dim3(nt * (nt + 1) / 2 + (m + CH_THREADS - 1) / CH_THREADS), dim3(CH_THREADS), 0,
-                                                   h->stream, Sw, (long long)d.ld, yw, N, k0, rows_end, info, skip);
-                            }
-                        }
-                        hipLaunchKernelGGL(k_chol_backsolve, dim3(1), dim3(CH_THREADS), 0, h->stream, Sw, (long long)d.ld, yw, N, bw, info, skip);
-                    }
+                    for (int w = 0; w < n_win; w++)
+                        if (h->wins[w].d.ld) solve_big(h, big[w], w, s, stride, (P.debug & 4096) && s == 3);
                 }
                 { ScopedTimer t(h, "k_solve_back"); hipLaunchKernelGGL(ks2, dim3(n_win), dim3(SOLVE_THREADS), 64, h->stream, P, s); }
                 for (int w = 0; w < n_win; w++) {
                     const WinDev& d = h->wins[w].d;
                     if (!d.ld) continue;
-                    if (big_bw[w] < d.Np && big_bw[w] + (d.dpf == 6 ? 6 : 5) <= MAX_LDS_NP)   // banded: only the band was written
-                        hipLaunchKernelGGL(k_band_zero, dim3((unsigned)std::min<long long>(((long long)d.Np * big_bw[w] + 255) / 256, 4096)), dim3(256), 0, h->stream,
-                                           h->d_S.p + d.S_off, (long long)d.ld, d.Np, big_bw[w]);
+                    if (big[w].banded())   // only the band was written
+                        hipLaunchKernelGGL(k_band_zero, dim3((unsigned)std::min<long long>(((long long)d.Np * big[w].bw + 255) / 256, 4096)), dim3(256), 0, h->stream,
+                                           h->d_S.p + d.S_off, (long long)d.ld, d.Np, big[w].bw);
                     else (void)hipMemsetAsync(h->d_S.p + d.S_off, 0, sizeof(double) * (size_t)d.Np * d.Np, h->stream);
                 }
             }
@@ -3171,7 +3165,7 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
     if (h->cfg.use_graph && !h->cfg.profile_kernels && !h->coll_fn) {
         // the whole <= 20-iteration solve is one graph launch; the key covers every kernel argument
         std::vector<int> lay;  // layout-dependent launch parameters of the out-of-LDS windows
-        for (int w = 0; w < n_win; w++) { lay.push_back(h->wins[w].d.Np); lay.push_back(h->wins[w].d.ld); lay.push_back(big_bw[w]); }
+        for (int w = 0; w < n_win; w++) { lay.push_back(h->wins[w].d.Np); lay.push_back(h->wins[w].d.ld); lay.push_back(big[w].bw); }
         lay.push_back(h->n_kept); lay.push_back(h->lm_sub_obs); lay.push_back(h->lm_n_sub); lay.push_back(h->lm_max_cam); lay.push_back(h->n_lobs_tot); lay.push_back(h->n_line_tot); lay.push_back(h->n_big); lay.push_back(dp_max_nf); lay.push_back(dp_max_n);
         std::vector<unsigned char> key(sizeof(DevPtrs) + 8 * sizeof(int) + 3 * sizeof(size_t) + lay.size() * sizeof(int));
         unsigned char* kp = key.data();
@@ -3179,9 +3173,7 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
         memcpy(kp, &P, sizeof(DevPtrs)); kp += sizeof(DevPtrs);
         // launch-shape switches read from the environment inside enqueue() are part of the key too: a handle that already captured a
         // graph must not replay it when an A/B switch changes
-        const int env_bits = (int)with_imu + 2 * (int)h->env.no_fork + 4 * (int)h->env.wd_nola + 8 * (int)h->env.wd_back1 +
-                             16 * (int)h->env.wd_old + 32 * (int)h->env.no_bcr + 128 * (int)h->env.no_lpt +
-                             256 * (int)h->env.wd_r3;
+        const int env_bits = (int)with_imu + 2 * (int)h->env.no_fork + 32 * (int)h->env.no_bcr + 128 * (int)h->env.no_lpt;
         const int ints[8] = {slots, n_tiles, n_win, mtk, strip_doubles, Rp, h->n_kf_tot, h->factor_type + 2 * (int)extras + 4 * (int)rare + 8 * (int)use_lm + 16 * env_bits};  // P (incl. decide_kernel) is part of the key
         memcpy(kp, ints, sizeof(ints)); kp += sizeof(ints);
         const size_t szs[3] = {lds_build, lds_back, lds_solve};
@@ -3213,9 +3205,6 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
             for (int i = 33; i < 43; i++) fprintf(stderr, " %d:%.2f", i, (ts[i] - ts[32]) * 0.01);
             fprintf(stderr, "\n[sadvio dbg] first IMU pair of k_build, us since its start (residual + Jacobian on lane 0 | decision | W J | entries + adds): %.2f %.2f %.2f %.2f, start %.2f us after tile 0",
                     (ts[57] - ts[56]) * 0.01, (ts[58] - ts[56]) * 0.01, (ts[59] - ts[56]) * 0.01, (ts[60] - ts[56]) * 0.01, (ts[56] - ts[32]) * 0.01);
-            fprintf(stderr, "\n[sadvio dbg] look-ahead workgroup of k_wchol_syrk_la, us since its start (loads landed, X slab in LDS | tiles updated | factored + inverted):");
-            fprintf(stderr, " %.2f %.2f %.2f", (ts[91] - ts[90]) * 0.01, (ts[94] - ts[90]) * 0.01, (ts[95] - ts[90]) * 0.01);
-            fprintf(stderr, " | waves after their tiles:"); for (int i = 98; i < 106; i++) fprintf(stderr, " %.2f", (ts[i] - ts[90]) * 0.01);
             fprintf(stderr, "\n[sadvio dbg] k_wchol_step (panel 1), us since the workgroup's start: look-ahead (operands in LDS | substituted | block updated | factored) %.2f %.2f %.2f %.2f",
                     (ts[107] - ts[106]) * 0.01, (ts[108] - ts[106]) * 0.01, (ts[109] - ts[106]) * 0.01, (ts[110] - ts[106]) * 0.01);
             fprintf(stderr, " | tile workgroup 7, %.2f us after it (operands | substituted | end) %.2f %.2f %.2f | inverse workgroup, %.2f us after it: %.2f",

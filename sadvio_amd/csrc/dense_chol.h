@@ -748,115 +748,14 @@ __global__ void k_bcr_writeback(BcrPtrs B, double* __restrict__ y, const int* in
     if (e < B.N) y[e] = B.X[e];   // X blocks are contiguous b-vectors: block k, row r sits at k * b + r
 }
 
-// ---- dense systems: wide panels built on the in-LDS factorisation -------------------------------------------------
+// ---- dense systems: wide panels on the FP64 matrix cores --------------------------------------------------------------
 // A dense reduced system (a dense prior couples the kept landmarks; N_p ~ 1 000) is factorised 96 columns at a time:
-//   k_wchol_diag   one workgroup: the 96 x 96 diagonal block (+ its rhs entries) goes through the tuned LDS solver
-//                  (chol_solve_packed<6, PARTIAL>, identity padding beyond N), then M = L_dd^-1 is formed from the
-//                  inverse pivot blocks by block anti-diagonals and stored; z = L_dd^-1 y_d
-//   k_wchol_trsm   X = A_panel M^T: one (rows x 96) x (96 x 96) product per 64-row tile on the FP64 matrix cores
-//   k_wchol_syrk   A_trailing -= X X^T on 64 x 64 tiles with K = 96 (FP64 MFMA), rhs row y -= X z
-//   k_wchol_backsolve   x_d = M^T (z_d - X_p^T x_p), super-steps in reverse, one workgroup
-// 3 launches per 96 columns instead of 2 per 32, and the panel / update work runs on MFMA instead of per-thread
-// substitution chains.
+//   k_wchol_diag16     one workgroup: the first 96 x 96 diagonal block (+ its rhs entries) on 16 x 16 MFMA tiles (chol16.h)
+//   k_wchol_step       one launch per further 96 columns: the next diagonal block (look-ahead), the panel substitution, the
+//                      trailing update on 64 x 64 tiles with K = 96, and M = L_dd^-1 of the finished block
+//   k_wchol_backstep   x_d = M^T (z_d - X_p^T x_p), one launch per super-step in reverse
 constexpr int WD = 96;
-constexpr int WD_NBK = WD / 6;
 constexpr int WDS = WD + 4;  // LDS row stride: (lane & 15) * 100 + (lane >> 4) hits every bank pair exactly twice
-
-// stage `rows` x WD doubles from global (row stride ld) into an LDS slab [..][WDS]; rows beyond `valid` are zero.
-// Eight independent loads are in flight per thread before the first LDS store.
-__device__ __forceinline__ void stage_slab(double (*dst)[WDS], const double* __restrict__ src, long long ld, int rows, int valid) {
-    const int total = rows * WD;
-    for (int eb = threadIdx.x; eb < total; eb += 8 * blockDim.x) {
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int e = eb + u * blockDim.x;
-            const int r = e / WD, cc = e - r * WD;
-            v[u] = (e < total && r < valid) ? src[(long long)r * ld + cc] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int e = eb + u * blockDim.x;
-            if (e < total) dst[e / WD][e - (e / WD) * WD] = v[u];
-        }
-    }
-}
-
-__global__ __launch_bounds__(SOLVE_THREADS) void k_wchol_diag(double* __restrict__ A, long long ld, double* __restrict__ y,
-                                                              double* __restrict__ Mg, int N, int c0, int* info, const int* skip) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (skip && *skip) return;
-    if (*info != 0) return;
-    constexpr int NB = 6;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    double* LpT = (double*)smem;                         // [NBP][WD + 2]
-    double* Pk = LpT + (size_t)(WD + 2) * NBP;           // packed window incl. rhs row
-    double* xv = Pk + (size_t)(WD + 1) * (WD + 2) / 2;
-    double* xs = xv + WD;
-    double* linvTab = xs + WD;                           // [WD_NBK][36]
-    double* Ml = linvTab + WD_NBK * 36;                  // [WD][WD + 1] inverse of the block factor
-    double* Tt = Ml + (size_t)WD * (WD + 1);             // [WD_NBK][36] temporaries of one anti-diagonal
-    // load (identity padding beyond N)
-    for (int gb = tid; gb < tri(WD, 0); gb += 5 * nt) {   // five independent loads in flight per thread
-        double v[5];
-#pragma unroll
-        for (int u = 0; u < 5; u++) {
-            const int g = gb + u * nt;
-            if (g < tri(WD, 0)) {
-                int i, j;
-                tri_decode(g, i, j);
-                v[u] = (c0 + i < N) ? A[(long long)(c0 + i) * ld + c0 + j] : (i == j ? 1.0 : 0.0);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 5; u++) {
-            const int g = gb + u * nt;
-            if (g < tri(WD, 0)) Pk[g] = v[u];
-        }
-    }
-    for (int j = tid; j < WD; j += nt) Pk[tri(WD, j)] = (c0 + j < N) ? y[c0 + j] : 0.0;
-    if (tid == 0) Pk[tri(WD, WD)] = 0.0;
-    __syncthreads();
-    const bool ok = chol_solve_packed<NB, true>(Pk, WD, xv, xs, LpT, linvTab, nullptr, WD_NBK);
-    __syncthreads();
-    if (!ok) { if (tid == 0) *info = c0 + 1; return; }
-    for (int j = tid; j < WD && c0 + j < N; j += nt) y[c0 + j] = Pk[tri(WD, j)];
-    // M = L^-1 by block anti-diagonals: M_kk = Linv_k; M_kj = -Linv_k sum_{i=j}^{k-1} L_ki M_ij
-    for (int e = tid; e < WD * (WD + 1); e += nt) Ml[e] = 0.0;
-    __syncthreads();
-    for (int e = tid; e < WD_NBK * 36; e += nt) {
-        const int k = e / 36, a = (e % 36) / 6, b = e % 6;
-        Ml[(6 * k + a) * (WD + 1) + 6 * k + b] = linvTab[k * 36 + a * 6 + b];
-    }
-    __syncthreads();
-    for (int d = 1; d < WD_NBK; d++) {
-        const int nblk = WD_NBK - d;
-        for (int e = tid; e < nblk * 36; e += nt) {
-            const int j = e / 36, a = (e % 36) / 6, b = e % 6, k = j + d;
-            // row 6k+a of L left of its pivot block is contiguous in the packed layout: columns 6j .. 6k-1
-            const double* lrow = Pk + tri(6 * k + a, 6 * j);
-            const double* mcol = Ml + (size_t)(6 * j) * (WD + 1) + 6 * j + b;
-            double t0 = 0.0, t1 = 0.0;
-            const int len = 6 * d;
-#pragma unroll 6
-            for (int q = 0; q < len; q += 2) {
-                t0 += lrow[q] * mcol[(size_t)q * (WD + 1)];
-                t1 += lrow[q + 1] * mcol[(size_t)(q + 1) * (WD + 1)];
-            }
-            Tt[e] = t0 + t1;
-        }
-        __syncthreads();
-        for (int e = tid; e < nblk * 36; e += nt) {
-            const int j = e / 36, a = (e % 36) / 6, b = e % 6, k = j + d;
-            double t = 0.0;
-#pragma unroll
-            for (int q = 0; q < 6; q++) t += linvTab[k * 36 + a * 6 + q] * Tt[j * 36 + q * 6 + b];
-            Ml[(6 * k + a) * (WD + 1) + 6 * j + b] = -t;
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < WD * WD; e += nt) Mg[e] = Ml[(e / WD) * (WD + 1) + (e % WD)];
-}
 
 // ---- the 96 x 96 diagonal block on 16 x 16 MFMA tiles (chol16.h) -------------------------------------------------------
 // C(16 x 16) = sum over the listed (A, B) tile pairs of A B, tiles column-major in LDS (element (r, c) at c * 16 + r); the
@@ -987,168 +886,8 @@ __device__ __forceinline__ void wd16_factor_and_invert(double* Im, double* __res
     if (Mg) wd16_invert(Im, Mi, scr, Mg, c0, info);
 }
 
-// X = A[s .. N, c0 .. c0 + WD) * M^T, 64 rows per workgroup
-__global__ __launch_bounds__(CH_THREADS) void k_wchol_trsm(double* __restrict__ A, long long ld, const double* __restrict__ Mg,
-                                                           int N, int c0, const int* info, const int* skip) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (skip && *skip) return;
-    if (*info != 0) return;
-    const int s = c0 + WD;
-    const int r0 = s + blockIdx.x * CH_TS;
-    if (r0 >= N) return;
-    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
-    double (*Xa)[WDS] = (double (*)[WDS])smem;
-    double (*Ms)[WDS] = (double (*)[WDS])(smem + sizeof(double) * CH_TS * WDS);
-    stage_slab(Xa, A + (long long)r0 * ld + c0, ld, CH_TS, N - r0);
-    stage_slab(Ms, Mg, WD, WD, WD);
-    __syncthreads();
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    const int lr = ln & 15, lk = ln >> 4;
-    d4 acc[WD / 16];
-#pragma unroll
-    for (int cb = 0; cb < WD / 16; cb++) {
-        d4 c4 = {0.0, 0.0, 0.0, 0.0};
-        for (int kk = 0; kk < 16 * (cb + 1); kk += 16) {   // M is lower triangular: k <= column; 4 k-steps per batch of loads
-            double av[4], bv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { av[u] = Xa[16 * wv + lr][kk + 4 * u + lk]; bv[u] = Ms[16 * cb + lr][kk + 4 * u + lk]; }
-#pragma unroll
-            for (int u = 0; u < 4; u++) c4 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], c4, 0, 0, 0);
-        }
-        acc[cb] = c4;
-    }
-#pragma unroll
-    for (int cb = 0; cb < WD / 16; cb++)
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++) {
-            const int row = r0 + 16 * wv + lk + 4 * rg;
-            if (row < N) A[(long long)row * ld + c0 + 16 * cb + lr] = acc[cb][rg];
-        }
-}
-
-// The same with 512-thread workgroups for the look-ahead loop, where this kernel sits between two diagonal blocks: every global load of
-// the two slabs (30 per thread) is in flight before the first wait, and a wave takes three of the six column blocks of its 16 rows.
-__global__ __launch_bounds__(SOLVE_THREADS) void k_wchol_trsm8(double* __restrict__ A, long long ld, const double* __restrict__ Mg,
-                                                               int N, int c0, const int* info, const int* skip) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (skip && *skip) return;
-    if (*info != 0) return;
-    const int s = c0 + WD;
-    const int r0 = s + blockIdx.x * CH_TS;
-    if (r0 >= N) return;
-    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
-    double (*Xa)[WDS] = (double (*)[WDS])smem;
-    double (*Ms)[WDS] = (double (*)[WDS])(smem + sizeof(double) * CH_TS * WDS);
-    {
-        constexpr int NXA = CH_TS * WD / SOLVE_THREADS, NM = WD * WD / SOLVE_THREADS;   // 12, 18
-        double vx[NXA], vm[NM];
-        const int valid = N - r0;
-#pragma unroll
-        for (int u = 0; u < NXA; u++) {
-            const int e = tid + u * SOLVE_THREADS;
-            const int r = e / WD, cc = e - r * WD;
-            vx[u] = r < valid ? A[(long long)(r0 + r) * ld + c0 + cc] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < NM; u++) vm[u] = Mg[tid + u * SOLVE_THREADS];
-#pragma unroll
-        for (int u = 0; u < NXA; u++) { const int e = tid + u * SOLVE_THREADS; Xa[e / WD][e - (e / WD) * WD] = vx[u]; }
-#pragma unroll
-        for (int u = 0; u < NM; u++) { const int e = tid + u * SOLVE_THREADS; Ms[e / WD][e - (e / WD) * WD] = vm[u]; }
-    }
-    __syncthreads();
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    const int lr = ln & 15, lk = ln >> 4;
-    const int rb = wv & 3, cb0 = 3 * (wv >> 2);
-    d4 acc[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const int cb = cb0 + q;
-        d4 c4 = {0.0, 0.0, 0.0, 0.0}, c5 = {0.0, 0.0, 0.0, 0.0};
-        for (int kk = 0; kk < 16 * (cb + 1); kk += 16) {   // M is lower triangular: k <= column; 4 k-steps per batch of loads
-            double av[4], bv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { av[u] = Xa[16 * rb + lr][kk + 4 * u + lk]; bv[u] = Ms[16 * cb + lr][kk + 4 * u + lk]; }
-            c4 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0], bv[0], c4, 0, 0, 0);
-            c5 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[1], bv[1], c5, 0, 0, 0);
-            c4 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[2], bv[2], c4, 0, 0, 0);
-            c5 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[3], bv[3], c5, 0, 0, 0);
-        }
-        acc[q] = c4 + c5;
-    }
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++) {
-            const int row = r0 + 16 * rb + lk + 4 * rg;
-            if (row < N) A[(long long)row * ld + c0 + 16 * (cb0 + q) + lr] = acc[q][rg];
-        }
-}
-
-// trailing update by the WD-wide panel X and rhs row; K = WD
-__global__ __launch_bounds__(CH_THREADS) void k_wchol_syrk(double* __restrict__ A, long long ld, double* __restrict__ y, int N, int c0,
-                                                           const int* info, const int* skip) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (skip && *skip) return;
-    if (*info != 0) return;
-    const int s = c0 + WD;
-    const int m = N - s;
-    if (m <= 0) return;
-    const int nt = (m + CH_TS - 1) / CH_TS;
-    const int npair = nt * (nt + 1) / 2;
-    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
-    if ((int)blockIdx.x >= npair) {
-        const int j = (blockIdx.x - npair) * CH_THREADS + tid;
-        if (j < m) {
-            const double* xrow = A + (long long)(s + j) * ld + c0;
-            double acc = 0.0;
-#pragma unroll 8
-            for (int cc = 0; cc < WD; cc++) acc += y[c0 + cc] * xrow[cc];
-            y[s + j] -= acc;
-        }
-        return;
-    }
-    double (*Pi)[WDS] = (double (*)[WDS])smem;
-    double (*Pj)[WDS] = (double (*)[WDS])(smem + sizeof(double) * CH_TS * WDS);
-    int ti = 0, rem = blockIdx.x;
-    while (rem >= ti + 1) { rem -= ti + 1; ti++; }
-    const int tj = rem;
-    const int i0 = ti * CH_TS, j0 = tj * CH_TS;
-    stage_slab(Pi, A + (long long)(s + i0) * ld + c0, ld, CH_TS, m - i0);
-    stage_slab(Pj, A + (long long)(s + j0) * ld + c0, ld, CH_TS, m - j0);
-    __syncthreads();
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    const int lr = ln & 15, lk = ln >> 4;
-    const int ib = wv;
-    for (int jb = 0; jb < 4; jb++) {
-        if (ti == tj && jb > ib) continue;
-        const int rbase = i0 + 16 * ib, cbase = j0 + 16 * jb;
-        if (rbase >= m || cbase >= m) continue;
-        d4 c;
-        long long addr[4];
-        bool ok[4];
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++) {
-            const int row = rbase + lk + 4 * rg, col = cbase + lr;
-            ok[rg] = row < m && col < m && col <= row;
-            addr[rg] = (long long)(s + (row < m ? row : m - 1)) * ld + s + (col < m ? col : m - 1);
-            c[rg] = ok[rg] ? A[addr[rg]] : 0.0;
-        }
-        for (int kk = 0; kk < WD; kk += 24) {   // 6 k-steps per batch of LDS loads
-            double a[6], b[6];
-#pragma unroll
-            for (int u = 0; u < 6; u++) { a[u] = -Pi[16 * ib + lr][kk + 4 * u + lk]; b[u] = Pj[16 * jb + lr][kk + 4 * u + lk]; }
-#pragma unroll
-            for (int u = 0; u < 6; u++) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], c, 0, 0, 0);
-        }
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++)
-            if (ok[rg]) A[addr[rg]] = c[rg];
-    }
-}
-
-// ---- the same back-substitution, one LAUNCH per super-step ------------------------------------------------------------------
-// k_wchol_backsolve streams every panel of L through one CU (4.9 MB at N = 1 065: 8.5 us per step). Here step st is a launch of its
+// ---- the back-substitution, one LAUNCH per super-step -----------------------------------------------------------------------------
+// One workgroup streaming every panel of L through its CU costs 8.5 us per step at N = 1 065 (4.9 MB). Here step st is a launch of its
 // own: workgroup 0 finishes block st - it applies the step before it, x_{st+1}, to its own 96 right-hand-side entries (one
 // 96 x 96 block of L) and multiplies by M_st^T - while the other workgroups apply x_{st+1} to all EARLIER columns, 64 columns each.
 // The updates of x_{st+2}, x_{st+3}, ... were applied by the launches before. Twelve launches of ~3.5 us instead of 102 us.
@@ -1223,159 +962,11 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_wchol_backstep(const double* 
     if (tid < nr) y[c0 + tid] = (p4[0][tid] + p4[1][tid]) + (p4[2][tid] + p4[3][tid]);
 }
 
-// ---- trailing update + LOOK-AHEAD: the next diagonal block is factored inside the same launch ---------------------------------
-// The panel loop diag -> trsm -> syrk is a chain of single-workgroup diagonal kernels (33 us each, half of the solve) with two wide
-// kernels between them. Here the last workgroup of the trailing update takes the NEXT diagonal block: it applies this panel's update to
-// it itself (X_next X_next^T from the panel rows the preceding k_wchol_trsm left, 96 x 96 x 96 on the matrix cores, and the right-hand
-// side), then factors and inverts it (wd16_factor_and_invert) while the other workgroups update the rest of the trailing matrix;
-// they leave the elements of that block and its right-hand-side rows alone. 512-thread workgroups: a 64 x 64 tile is 8 waves x 2
-// sub-tiles. LDS: max(two 64 x 96 slabs, the image + the 96 x 96 slab of X_next, over which M is built later).
-constexpr int WXS = 113;   // row stride of the transposed X_next slab of the look-ahead workgroup (see there)
-__host__ __device__ constexpr size_t wdla_lds_doubles() { return wd16_lds_doubles() + (size_t)WD * WXS - (size_t)(WD_T * (WD_T + 1) / 2 + SOLVE_THREADS / 64) * 256; }
-__global__ __launch_bounds__(SOLVE_THREADS) void k_wchol_syrk_la(double* __restrict__ A, long long ld, double* __restrict__ y, double* __restrict__ Mg_next,
-                                                                 int N, int c0, int* info, const int* skip, long long* dbg) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (skip && *skip) return;
-    if (*info != 0) return;
-    const int s = c0 + WD;
-    const int m = N - s;
-    if (m <= 0) return;
-    const int nt = (m + CH_TS - 1) / CH_TS;
-    const int npair = nt * (nt + 1) / 2;
-    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    const int lr = ln & 15, lk = ln >> 4;
-    const int bid = (int)blockIdx.x - 1;   // workgroup 0 is dispatched first: the look-ahead block, the longest chain of the launch
-    if (bid < 0) {
-        // ---- the next diagonal block [s, s + WD) ----
-        double* Im = (double*)smem;
-        // X_next TRANSPOSED, XT[panel column][block row], with the panel's right-hand side as block row WD (rows WD + 1 .. WD + 15 zero):
-        // the MFMA fragments (16 consecutive block rows of one column per 16-lane group) are contiguous 128-byte reads, and the
-        // right-hand-side update is the seventh tile row of the same product - as in chol16. Row stride WXS = 113 doubles: 16 consecutive
-        // columns of one block row (what a wave stores from its unit-stride HBM reads) fall into 16 different bank pairs. (Row-major with
-        // the stride of the trsm / syrk slabs the compiler's ds_read2_b64 pairs hit four bank pairs per 16 lanes: 9.4 us for the tile
-        // updates.) M and the scratch tiles reuse the area later.
-        double (*XT)[WXS] = (double (*)[WXS])(Im + c16_size(WD) + WD + C16_WORK + 16 * (WD_T + 1));
-        if (dbg && tid == 0) dbg[0] = wall_clock64();
-        // every global load of the prologue is issued before the first wait: X_next = the panel rows s .. s + WD (18 per thread, unit
-        // stride), the panel's right-hand side, and this wave's tiles of the block itself straight in the accumulator layout (register q of
-        // lane (lr, lk) = element (lk + 4 q, lr): 128-byte row segments), which spares a staging pass through LDS. Addresses are clamped
-        // into the stored triangle and the values selected afterwards: no branch around a load.
-        constexpr int NX = WD * WD / SOLVE_THREADS, NTL = WD_T * (WD_T + 1) / 2 + WD_T, NW = SOLVE_THREADS / 64, TPW = (NTL + NW - 1) / NW;
-        double vx[NX];
-#pragma unroll
-        for (int u = 0; u < NX; u++) {
-            const int e = tid + u * SOLVE_THREADS;
-            const int r = e / WD, c = e - r * WD;
-            const double v = A[(long long)min(s + r, N - 1) * ld + c0 + c];
-            vx[u] = (s + r < N) ? v : 0.0;
-        }
-        const double vy = y[c0 + min(tid, WD - 1)];
-        d4 acc0[TPW];
-#pragma unroll
-        for (int w = 0; w < TPW; w++) {
-            const int t = min(wv + w * NW, NTL - 1);
-            int I = 0, r = t;
-            while (r >= I + 1) { r -= I + 1; I++; }          // t < 21: lower tile (I, J) of the block; t = 21 + J: the right-hand-side tile (WD_T, J)
-            const int J = r;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int i = 16 * I + lk + 4 * q, j = 16 * J + lr;
-                const double v = A[(long long)min(s + i, N - 1) * ld + min(s + min(j, i), N - 1)];
-                const double vr = y[min(s + j, N - 1)];
-                acc0[w][q] = I == WD_T ? ((lk + 4 * q == 0 && s + j < N) ? vr : 0.0) : (j <= i ? ((s + i < N) ? v : (i == j ? 1.0 : 0.0)) : 0.0);
-            }
-        }
-        for (int e = tid; e < 256; e += SOLVE_THREADS) Im[(c16_tile(WD_T, WD_T) << 8) + e] = 0.0;   // the tile behind the right-hand side's last column block
-        for (int e = tid; e < 15 * WD; e += SOLVE_THREADS) XT[e / 15][WD + 1 + e % 15] = 0.0;
-#pragma unroll
-        for (int u = 0; u < NX; u++) { const int e = tid + u * SOLVE_THREADS; XT[e - (e / WD) * WD][e / WD] = vx[u]; }
-        if (tid < WD) XT[tid][WD] = vy;
-        __syncthreads();
-        if (dbg && tid == 0) dbg[1] = wall_clock64();
-        // image tile (I, J) = block tile (right-hand-side tile) - sum_K X(I, K) X(J, K)^T: the 48 operand fragments of a tile are fetched
-        // before its 24 MFMAs (two chains)
-#pragma unroll
-        for (int w = 0; w < TPW; w++) {
-            const int t = wv + w * NW;
-            if (t >= NTL) break;
-            int I = 0, r = t;
-            while (r >= I + 1) { r -= I + 1; I++; }
-            const int J = r;
-            double a[4 * WD_T], b[4 * WD_T];
-#pragma unroll
-            for (int k4 = 0; k4 < 4 * WD_T; k4++) { a[k4] = -XT[4 * k4 + lk][16 * I + lr]; b[k4] = XT[4 * k4 + lk][16 * J + lr]; }
-            d4 acc = acc0[w], acc2 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int k4 = 0; k4 < 4 * WD_T; k4 += 2) {
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[k4], b[k4], acc, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[k4 + 1], b[k4 + 1], acc2, 0, 0, 0);
-            }
-            double* ct = Im + (c16_tile(I, J) << 8);
-#pragma unroll
-            for (int q = 0; q < 4; q++) ct[lr * 16 + lk + 4 * q] = acc[q] + acc2[q];   // register q of lane (lr, lk) = C[lk + 4 q][lr]
-        }
-        if (dbg && ln == 0) dbg[8 + wv] = wall_clock64();
-        __syncthreads();
-        if (dbg && tid == 0) dbg[4] = wall_clock64();
-        wd16_factor_and_invert(Im, y, Mg_next, N, s, info);
-        if (dbg && tid == 0) dbg[5] = wall_clock64();
-        return;
-    }
-    if (bid >= npair) {
-        const int j = (bid - npair) * SOLVE_THREADS + tid;
-        if (j < m && j >= WD) {          // the first WD rows belong to the look-ahead workgroup
-            const double* xrow = A + (long long)(s + j) * ld + c0;
-            double acc = 0.0;
-#pragma unroll 8
-            for (int cc = 0; cc < WD; cc++) acc += y[c0 + cc] * xrow[cc];
-            y[s + j] -= acc;
-        }
-        return;
-    }
-    double (*Pi)[WDS] = (double (*)[WDS])smem;
-    double (*Pj)[WDS] = (double (*)[WDS])(smem + sizeof(double) * CH_TS * WDS);
-    int ti = 0, rem = bid;
-    while (rem >= ti + 1) { rem -= ti + 1; ti++; }
-    const int tj = rem;
-    const int i0 = ti * CH_TS, j0 = tj * CH_TS;
-    stage_slab(Pi, A + (long long)(s + i0) * ld + c0, ld, CH_TS, m - i0);
-    stage_slab(Pj, A + (long long)(s + j0) * ld + c0, ld, CH_TS, m - j0);
-    __syncthreads();
-    const int ib = wv & 3;
-    for (int jb = 2 * (wv >> 2); jb < 2 * (wv >> 2) + 2; jb++) {
-        if (ti == tj && jb > ib) continue;
-        const int rbase = i0 + 16 * ib, cbase = j0 + 16 * jb;
-        if (rbase >= m || cbase >= m) continue;
-        d4 c;
-        long long addr[4];
-        bool ok[4];
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++) {
-            const int row = rbase + lk + 4 * rg, col = cbase + lr;
-            ok[rg] = row < m && col < m && col <= row && !(row < WD && col < WD);   // (the look-ahead workgroup's block)
-            addr[rg] = (long long)(s + (row < m ? row : m - 1)) * ld + s + (col < m ? col : m - 1);
-            c[rg] = ok[rg] ? A[addr[rg]] : 0.0;
-        }
-        for (int kk = 0; kk < WD; kk += 24) {   // 6 k-steps per batch of LDS loads
-            double a[6], b[6];
-#pragma unroll
-            for (int u = 0; u < 6; u++) { a[u] = -Pi[16 * ib + lr][kk + 4 * u + lk]; b[u] = Pj[16 * jb + lr][kk + 4 * u + lk]; }
-#pragma unroll
-            for (int u = 0; u < 6; u++) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], c, 0, 0, 0);
-        }
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++)
-            if (ok[rg]) A[addr[rg]] = c[rg];
-    }
-}
-
-// ---- round 4: ONE launch per 96 columns ---------------------------------------------------------------------------------------------
-// The round-3 loop was trsm8 -> syrk_la per panel: two dependent launches, and the look-ahead workgroup's chain was
-// factor (13.7 us) + M = L^-1 (12 us) because the NEXT launch's panel product X = A M^T needed the explicit inverse. Here the panel
-// solve is a block SUBSTITUTION against the factor's own tiles (wd_subst_strip: X_j = (A_j - sum_{q<j} X_q L_jq^T) L_jj^-T on 16 x 16
-// MFMA tiles, L_jj^-T being what chol16 leaves in the diagonal tile), so
-//   * the inverse leaves the chain: M (which only the back-substitution reads) is built by a spare workgroup of the FOLLOWING launch,
+// ---- ONE launch per 96 columns -------------------------------------------------------------------------------------------------------
+// The panel solve is a block SUBSTITUTION against the factor's own tiles (wd_subst_strip: X_j = (A_j - sum_{q<j} X_q L_jq^T) L_jj^-T on
+// 16 x 16 MFMA tiles, L_jj^-T being what chol16 leaves in the diagonal tile), not a product X = A M^T with the explicit inverse, so
+//   * the inverse leaves the chain of the look-ahead workgroup: M (which only the back-substitution reads) is built by a spare workgroup
+//     of the FOLLOWING launch,
 //   * the panel solve needs no launch of its own: every tile workgroup substitutes the two 64-row strips of the panel it is about to
 //     contract (redundantly - 136 workgroups on 256 CUs - instead of waiting for a launch that does it once),
 //   * the substituted panel goes OUT of place (Lx), because other workgroups still read the unsubstituted rows.
@@ -1420,6 +1011,14 @@ __device__ __forceinline__ void wd_subst_strip(const double* Lt, At at, int lr, 
     }
 }
 
+// The look-ahead workgroup keeps the next block's 96 panel rows X_next TRANSPOSED in LDS, XT[panel column][block row], with the panel's
+// right-hand side as block row WD (rows WD + 1 .. WD + 15 zero): the MFMA fragments (16 consecutive block rows of one column per 16-lane
+// group) are contiguous 128-byte reads. Row stride WXS = 113 doubles: 16 consecutive columns of one block row (what a wave stores from its
+// unit-stride HBM reads) fall into 16 different bank pairs; row-major with the stride WDS of the tile slabs, the compiler's ds_read2_b64
+// pairs hit four bank pairs per 16 lanes (9.4 us for the tile updates). M and the scratch tiles of wd16_factor_and_invert reuse the area
+// later. LDS: max(the image + the slab, two 64 x 96 slabs + the factor's tiles).
+constexpr int WXS = 113;
+__host__ __device__ constexpr size_t wdla_lds_doubles() { return wd16_lds_doubles() + (size_t)WD * WXS - (size_t)(WD_T * (WD_T + 1) / 2 + SOLVE_THREADS / 64) * 256; }
 __host__ __device__ constexpr size_t wdstep_lds_doubles() {
     return wdla_lds_doubles() > (size_t)2 * CH_TS * WDS + WD_LT ? wdla_lds_doubles() : (size_t)2 * CH_TS * WDS + WD_LT;
 }
@@ -1444,7 +1043,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_wchol_step(double* __restrict
     if (bid < 0) {
         // ---- the next diagonal block [s, s + WD) ----
         double* Im = (double*)smem;
-        double (*XT)[WXS] = (double (*)[WXS])(Im + c16_size(WD) + WD + C16_WORK + 16 * (WD_T + 1));   // transposed slab, see k_wchol_syrk_la
+        double (*XT)[WXS] = (double (*)[WXS])(Im + c16_size(WD) + WD + C16_WORK + 16 * (WD_T + 1));   // transposed slab, see above
         // NTL: the block's 21 lower tiles, updated on the matrix cores. The right-hand side's tile row (one useful row of 16 per tile: 144 of
         // 648 MFMAs when it rode the same product) is 96 dot products on the VALU, by the last 96 threads - waves that hold two tiles
         // where the others hold three.
@@ -1617,73 +1216,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_wchol_step(double* __restrict
         if (part == 0 && i0 + r < m && i0 + r >= WD) y[s + i0 + r] -= acc;
     }
     if (dts) dts[3] = wall_clock64();
-}
-
-// x = L^-T z in place: super-steps in reverse, one workgroup. Right-looking: once the 96 unknowns x_d of a step are
-// known (x_d = M^T t_d), every earlier right-hand-side entry is updated, y[c] -= sum_r X[d rows r][c] x_d[r] -- row
-// reads of X, unit stride across the threads.
-__global__ __launch_bounds__(SOLVE_THREADS) void k_wchol_backsolve(const double* __restrict__ A, long long ld, double* __restrict__ y,
-                                                                   const double* __restrict__ Mg_all, int N, const int* info,
-                                                                   const int* skip) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (skip && *skip) return;
-    if (*info != 0) return;
-    double (*Ms)[WDS] = (double (*)[WDS])smem;
-    __shared__ double tv[WD], xd[WD], part[4][WD];
-    const int tid = threadIdx.x;
-    const int nsteps = (N + WD - 1) / WD;
-    // M of a step is fetched into registers while the previous step's update streams its panel (18 loads per thread, issued
-    // before the update loop, stored to LDS behind it); the 96-long dot products of x_d = M^T t_d are split over four threads;
-    // the update keeps 24 panel rows in flight per thread instead of 8 (the kernel is one workgroup: its speed is the number
-    // of loads it keeps outstanding).
-    constexpr int MV = (WD * WD + SOLVE_THREADS - 1) / SOLVE_THREADS;
-    double mreg[MV];
-    auto fetch_m = [&](int st) {
-        const double* Mg = Mg_all + (size_t)st * WD * WD;
-#pragma unroll
-        for (int q = 0; q < MV; q++) { const int e = tid + q * SOLVE_THREADS; mreg[q] = e < WD * WD ? Mg[e] : 0.0; }
-    };
-    auto store_m = [&]() {
-#pragma unroll
-        for (int q = 0; q < MV; q++) { const int e = tid + q * SOLVE_THREADS; if (e < WD * WD) Ms[e / WD][e % WD] = mreg[q]; }
-    };
-    fetch_m(nsteps - 1);
-    for (int st = nsteps - 1; st >= 0; st--) {
-        const int c0 = st * WD;
-        const int nr = min(WD, N - c0);
-        store_m();
-        if (tid < WD) tv[tid] = tid < nr ? y[c0 + tid] : 0.0;
-        __syncthreads();
-        if (st > 0) fetch_m(st - 1);       // in flight under the dot products and the update below
-        if (tid < 4 * WD) {
-            const int c = tid % WD, q4 = tid / WD;      // (M^T t)_c = sum_{k >= c} M[k][c] t_k, k = q4, q4 + 4, ...
-            double x = 0.0;
-            for (int k = c + ((q4 - c) & 3); k < WD; k += 4) x += Ms[k][c] * tv[k];
-            part[q4][c] = x;
-        }
-        __syncthreads();
-        if (tid < WD) {
-            const double x = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
-            xd[tid] = x;
-            if (tid < nr) y[c0 + tid] = x;
-        }
-        __syncthreads();
-        for (int cc = tid; cc < c0; cc += SOLVE_THREADS) {
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-            const double* col = A + (long long)c0 * ld + cc;
-            int r = 0;
-            for (; r + 24 <= nr; r += 24) {
-                double v[24];
-#pragma unroll
-                for (int u = 0; u < 24; u++) v[u] = col[(long long)(r + u) * ld];
-#pragma unroll
-                for (int u = 0; u < 24; u += 3) { a0 += v[u] * xd[r + u]; a1 += v[u + 1] * xd[r + u + 1]; a2 += v[u + 2] * xd[r + u + 2]; }
-            }
-            for (; r < nr; r++) a0 += col[(long long)r * ld] * xd[r];
-            y[cc] -= (a0 + a1) + a2;
-        }
-        __syncthreads();
-    }
 }
 
 // ---- the wide-panel factor as a prior (sadvio_ba_marginalize, Cholesky form, full-rank Ak) ------------------------------------------

@@ -116,39 +116,20 @@ def test_vo_prior_hbm_path(backend_cls, oracle_lib):
     compare(backend_cls, oracle_lib, w, capi.reference_options())
 
 
-@pytest.mark.parametrize("n_keep", [39, 70, 71, 72, 103])
+@pytest.mark.parametrize("n_keep", [36, 39, 70, 71, 72, 103])
 def test_dense_reduced_system_edge_sizes(backend_cls, oracle_lib, n_keep):
     """The wide-panel dense solver (look-ahead panel loop, per-step back-substitution) at N_p = 75 + 3 n_keep = 192 (two panels
     exactly), 285 / 288 / 291 (three short of / exactly / three beyond a multiple of the 96-column panel) and 384: the last
-    block's clamped loads sit at the end of the matrix (a fault found on a window at the end of the S allocation)."""
+    block's clamped loads sit at the end of the matrix (a fault found on a window at the end of the S allocation). N_p = 183,
+    below two panels, takes the 32-column panel solver (k_chol_panel / k_chol_update / k_chol_backsolve)."""
     w = make_vio_window(n_kf=6, n_lmk=900, seed=100 + n_keep)
     w.dense_prior = random_prior(w, n_keep, w.n_kf - 2, np.random.default_rng(n_keep), rank_deficit=3)
     compare(backend_cls, oracle_lib, w, capi.reference_options(), vio=True)
 
 
-def test_one_launch_per_panel_equals_the_round3_panel_loop(backend_cls, oracle_lib):
+def test_one_launch_per_panel_matches_the_oracle(backend_cls, oracle_lib):
     """k_wchol_step (one launch per 96 columns: block substitution against the factor's tiles, M = L^-1 off the chain, out-of-place
-    panels) against the round-3 loop it replaced (SADVIO_WD_R3: trsm8 + syrk_la with the explicit inverse) on a 3-panel-and-a-bit
-    system: same iterations, same accepted steps, solutions equal far below the parity bar."""
-    import os
+    panels) on a 3-panel-and-a-bit system with a rank-deficient prior: iterate-by-iterate parity with the oracle."""
     w = make_vio_window(n_kf=6, n_lmk=900, seed=171)
     w.dense_prior = random_prior(w, 80, w.n_kf - 2, np.random.default_rng(80), rank_deficit=2)    # N_p = 75 + 240 = 315
-    out = {}
-    for name, val in (("step", None), ("r3", "1")):
-        old = os.environ.pop("SADVIO_WD_R3", None)
-        if val is not None:
-            os.environ["SADVIO_WD_R3"] = val
-        try:
-            be = backend_cls(device=0)
-            be.set_windows([w])
-            s = be.solve(capi.reference_options())[0]
-            out[name] = (s, be.get_deltas(0))
-            be.close()
-        finally:
-            os.environ.pop("SADVIO_WD_R3", None)
-            if old is not None:
-                os.environ["SADVIO_WD_R3"] = old
-    (sa, da), (sb, db) = out["step"], out["r3"]
-    assert (sa.iterations, sa.termination, sa.num_successful_steps) == (sb.iterations, sb.termination, sb.num_successful_steps)
-    assert np.isclose(sa.final_cost, sb.final_cost, rtol=1e-11)
-    assert np.abs(da["pose"] - db["pose"]).max() <= 1e-9 and np.abs(da["lmk"] - db["lmk"]).max() <= 1e-8
+    compare(backend_cls, oracle_lib, w, capi.reference_options(), vio=True)
