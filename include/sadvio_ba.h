@@ -520,6 +520,53 @@ typedef struct sadvio_viinit_result {
 int sadvio_ba_vi_init(sadvio_ba_handle *h, const sadvio_viinit_problem *prob, const sadvio_solve_options *opts,
                       sadvio_solve_summary *summary, sadvio_viinit_result *res, double *dv3);
 
+/* ---- metric scale of a non-overlapping rig: AngularAdjustmentCERESAnalytic::landmarkOptimizationNoFov
+ *      (AngularAdjustmentCERESAnalytic.cpp:741-907, declared virtual in AOptimizer.h:34) ----
+ * Unknowns: the scale lambda of T_cam0_cam0p's translation (a plain value starting at 1.0, :755-757) and one additive delta
+ * per landmark (:802-804); every pose is constant (:760-762, :836-841). Residuals per landmark, all under
+ * HuberLoss(opts->huber_a) (:753): AngularErrorScaleCam0 on fp's feature (…Analytic.h:122-194, weight 1 / sigma^2,
+ * sigma = 1, :806-817) and AngularErrCeres_pointxd_dx on f's feature and on every other key-frame's feature (:819-849,
+ * sigma = 1); plus scalePrior(info_scale) on lambda (residuals.hpp:702-717, no loss, :853-854). LM with the Ceres-2.2 rules
+ * of the window solves (:857-868: 20 iterations, f_tol 1e-3); Ceres' x_norm includes lambda's value. The landmark selection
+ * (:775-851) is the caller's: see nofov_flatten in sadvio_optimizer.hpp. */
+typedef struct sadvio_nofov_problem {
+    int32_t n_lmk;                /* landmarks with both feat and featp (:820) */
+    int32_t n_obs;                /* fixed-pose angular factors, all landmarks */
+    int32_t n_frames;             /* key-frames the factors read; frame 0 is f */
+    int32_t n_cam;
+    int32_t cam0;                 /* f's sensor 0 (:767): index into cam_T_s_f */
+    int32_t fix_scale;            /* -1: the reference's rule, |log_so3(R)| < 0.05 or |t| < 0.01 (:769-772); 0 / 1: force */
+    const double *frame_T_f_w;    /* [n_frames][12] getWorld2FrameTransform (:827, :845); T_cam0_w = T_s_f[cam0] * T_f_w[0] (:813) */
+    const double *cam_T_s_f;      /* [n_cam][12] getFrame2SensorTransform (:809-810, :826, :844) */
+    const double *T_cam0_cam0p;   /* [12] the motion whose translation is scaled (:814) */
+    double info_scale;            /* scalePrior's sqrt information (:853) */
+    double gate;                  /* 2 / focal of f's sensor 0 (:890, Camera.h:46) */
+    const double *lmk_p;          /* [n_lmk][3] lmk->getPose().translation() (:812) */
+    const double *scale_bearing;  /* [n_lmk][3] featp's bearing (:811) */
+    const int32_t *scale_cam;     /* [n_lmk] featp's sensor: T_cam_cam0 = T_s_f[scale_cam] * T_s_f[cam0]^-1 (:808-810) */
+    const int32_t *lmk_obs_ptr;   /* [n_lmk + 1] CSR of the fixed-pose angular factors of each landmark (f's first, then feats) */
+    const int32_t *obs_frame;     /* [n_obs] frame of the factor's feature */
+    const int32_t *obs_cam;       /* [n_obs] sensor of the factor's feature: index into cam_T_s_f */
+    const double *obs_bearing;    /* [n_obs][3] getBearingVectors().at(0) (:826, :843) */
+} sadvio_nofov_problem;
+
+typedef struct sadvio_nofov_result {
+    double lambda;       /* the solved scale (:872) */
+    int32_t usable;      /* IsSolutionUsable && 0.5 <= lambda <= 1.5 (:870-871) */
+    int32_t scale_fixed; /* lambda was held constant (:769-772) */
+    int32_t n_inliers;   /* landmarks that pass the gate (:889-899) */
+    int32_t pad;
+} sadvio_nofov_result;
+
+/* lmk_delta3: [n_lmk][3] solved deltas; gate_norm: [n_lmk] |r| of the scale factor at the solution without loss (:884-887);
+ * inlier: [n_lmk] 1 iff !(gate_norm > gate). Any output may be NULL. Returns SADVIO_E_NOT_USABLE when the solution is not
+ * usable or lambda is out of [0.5, 1.5] (the reference then returns false and changes nothing); the outputs are filled anyway.
+ * At most 65 536 landmarks and 16 angular factors per landmark (one workgroup solves the whole problem);
+ * n_lmk = 0 with lambda constant is SADVIO_E_INVALID_ARG. opts->huber_a applies to the visual factors only. */
+int sadvio_ba_nofov_scale(sadvio_ba_handle *h, const sadvio_nofov_problem *prob, const sadvio_solve_options *opts,
+                          sadvio_solve_summary *summary, sadvio_nofov_result *res, double *lmk_delta3, double *gate_norm,
+                          int32_t *inlier);
+
 /* Average device time in microseconds per kernel class since the last set_windows, measured
  * with hipEvents on the handle's stream (cfg.profile_kernels = 1). `names` receives pointers
  * to static strings. Returns the number of classes written (<= cap). */

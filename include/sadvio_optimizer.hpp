@@ -147,6 +147,107 @@ struct LocalMapSnapshot {     // LocalMap::getLastNFramesIn (newest first, amap.
     std::vector<LineLandmarkState> lines;   // getLandmarks()["linexd"]
 };
 
+inline Pose pose_mul(const Pose& a, const Pose& b) {   // a * b
+    Pose c;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) c.R[3 * i + j] = a.R[3 * i] * b.R[j] + a.R[3 * i + 1] * b.R[3 + j] + a.R[3 * i + 2] * b.R[6 + j];
+        c.t[i] = a.R[3 * i] * b.t[0] + a.R[3 * i + 1] * b.t[1] + a.R[3 * i + 2] * b.t[2] + a.t[i];
+    }
+    return c;
+}
+inline Pose pose_inv(const Pose& a) {
+    Pose c;
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) c.R[3 * i + j] = a.R[3 * j + i];
+    for (int i = 0; i < 3; i++) c.t[i] = -(c.R[3 * i] * a.t[0] + c.R[3 * i + 1] * a.t[1] + c.R[3 * i + 2] * a.t[2]);
+    return c;
+}
+
+// The problem of AngularAdjustmentCERESAnalytic::landmarkOptimizationNoFov (AngularAdjustmentCERESAnalytic.cpp:775-851) in the
+// layout of sadvio_nofov_problem. Selection: a landmark that is initialised and not an outlier (:778); of its features, only
+// those of key-frames count (:788); the one on f is `feat`, the one on fp is `featp` (the last one wins, :792-800), every other
+// one goes to `feats` (:802); the landmark enters only with both feat and featp (:806). Problem frame 0 is f, the others
+// follow in order of first use; cameras are (frame, sensor) pairs in order of first use, f's sensor 0 first. Bearings come
+// from each camera model (getRayCamera). A feature whose frame or sensor does not exist is ignored.
+struct NoFovFlat {
+    std::vector<double> frame_T, cam_T, lmk_p, scale_bearing, obs_bearing;
+    std::vector<int32_t> scale_cam, ptr{0}, obs_frame, obs_cam;
+    std::vector<int> lmk_src;     // snapshot landmark of each problem landmark
+    std::vector<int> frame_src;   // snapshot frame of each problem frame (frame_src[0] = f)
+    std::vector<int> cam_frame, cam_sensor;
+    double gate = 0.0;            // 2 / focal of f's sensor 0 (:890, Camera.h:46)
+    double T_cam0_cam0p[12] = {};
+    sadvio_nofov_problem pb{};    // points into the members above: fill in place, do not copy
+};
+
+inline bool nofov_flatten(const LocalMapSnapshot& map, int f, int fp, const Pose& T_cam0_cam0p, double info_scale, NoFovFlat& F) {
+    const int nf = (int)map.frames.size();
+    F = NoFovFlat();
+    if (f < 0 || f >= nf || fp < 0 || fp >= nf || f == fp || map.frames[f].cameras.empty()) return false;
+    std::vector<int> frame_of(nf, -1);
+    std::vector<std::vector<int>> cam_of(nf);
+    for (int k = 0; k < nf; k++) cam_of[k].assign(map.frames[k].cameras.size(), -1);
+    auto frame_idx = [&](int k) {
+        if (frame_of[k] < 0) {
+            frame_of[k] = (int)F.frame_src.size(); F.frame_src.push_back(k);
+            F.frame_T.insert(F.frame_T.end(), map.frames[k].T_f_w.R, map.frames[k].T_f_w.R + 9);
+            F.frame_T.insert(F.frame_T.end(), map.frames[k].T_f_w.t, map.frames[k].T_f_w.t + 3);
+        }
+        return frame_of[k];
+    };
+    auto cam_idx = [&](int k, int c) {
+        if (cam_of[k][c] < 0) {
+            const Pose& T = map.frames[k].cameras[c].T_s_f;
+            cam_of[k][c] = (int)F.cam_frame.size(); F.cam_frame.push_back(k); F.cam_sensor.push_back(c);
+            F.cam_T.insert(F.cam_T.end(), T.R, T.R + 9); F.cam_T.insert(F.cam_T.end(), T.t, T.t + 3);
+        }
+        return cam_of[k][c];
+    };
+    auto bearing = [&](const Feature& ft, std::vector<double>& out) {
+        double b[3] = {0.0, 0.0, 1.0};
+        ray_camera(map.frames[ft.frame].cameras[ft.camera].intrinsics(), ft.u, ft.v, b);
+        out.insert(out.end(), {b[0], b[1], b[2]});
+    };
+    frame_idx(f);
+    cam_idx(f, 0);
+    const CameraModel& c0 = map.frames[f].cameras[0];
+    F.gate = 2.0 / ((c0.fx + c0.fy) / 2.0);
+    for (int l = 0; l < (int)map.landmarks.size(); l++) {
+        const LandmarkState& L = map.landmarks[l];
+        if (!L.initialized || L.outlier) continue;                                        // :778-779
+        const Feature* feat = nullptr; const Feature* featp = nullptr;
+        std::vector<const Feature*> feats;
+        for (const Feature& ft : L.features) {
+            if (ft.frame < 0 || ft.frame >= nf || ft.camera < 0 || ft.camera >= (int)map.frames[ft.frame].cameras.size()) continue;
+            if (!map.frames[ft.frame].is_keyframe) continue;                              // :788-790
+            if (ft.frame == f) feat = &ft;                                                // :792-795
+            else if (ft.frame == fp) featp = &ft;                                         // :797-800
+            else feats.push_back(&ft);                                                    // :802
+        }
+        if (!feat || !featp) continue;                                                    // :806
+        F.lmk_src.push_back(l);
+        F.lmk_p.insert(F.lmk_p.end(), L.p, L.p + 3);
+        bearing(*featp, F.scale_bearing);
+        F.scale_cam.push_back(cam_idx(featp->frame, featp->camera));
+        for (const Feature* ft : {feat}) {                                                // f's factor first (:819-831), then feats (:833-849)
+            F.obs_frame.push_back(frame_idx(ft->frame)); F.obs_cam.push_back(cam_idx(ft->frame, ft->camera)); bearing(*ft, F.obs_bearing);
+        }
+        for (const Feature* ft : feats) {
+            F.obs_frame.push_back(frame_idx(ft->frame)); F.obs_cam.push_back(cam_idx(ft->frame, ft->camera)); bearing(*ft, F.obs_bearing);
+        }
+        F.ptr.push_back((int32_t)F.obs_frame.size());
+    }
+    sadvio_nofov_problem& p = F.pb;
+    p.n_lmk = (int32_t)F.lmk_src.size(); p.n_obs = (int32_t)F.obs_frame.size(); p.n_frames = (int32_t)F.frame_src.size();
+    p.n_cam = (int32_t)F.cam_frame.size(); p.cam0 = 0; p.fix_scale = -1;
+    p.frame_T_f_w = F.frame_T.data(); p.cam_T_s_f = F.cam_T.data();
+    std::memcpy(F.T_cam0_cam0p, T_cam0_cam0p.R, 72); std::memcpy(F.T_cam0_cam0p + 9, T_cam0_cam0p.t, 24);
+    p.T_cam0_cam0p = F.T_cam0_cam0p;
+    p.info_scale = info_scale; p.gate = F.gate;
+    p.lmk_p = F.lmk_p.data(); p.scale_bearing = F.scale_bearing.data(); p.scale_cam = F.scale_cam.data();
+    p.lmk_obs_ptr = F.ptr.data(); p.obs_frame = F.obs_frame.data(); p.obs_cam = F.obs_cam.data(); p.obs_bearing = F.obs_bearing.data();
+    return true;
+}
+
 class HipOptimizer {
   public:
     explicit HipOptimizer(int device = 0, bool angular = false) : _angular(angular) {
@@ -242,6 +343,37 @@ class HipOptimizer {
             std::memcpy(L.p, q, sizeof(q));
         }
         return s;
+    }
+
+    // AngularAdjustmentCERESAnalytic::landmarkOptimizationNoFov (AngularAdjustmentCERESAnalytic.cpp:741-907): the metric scale
+    // of T_cam0_cam0p from the landmarks f and fp share (nofov_flatten), Huber(sqrt(1.345)), 20 iterations (:857-868). Returns
+    // false and changes nothing when the solution is not usable or lambda is outside [0.5, 1.5] (:870-871). Otherwise
+    // T_cam0_cam0p.t *= lambda, fp's T_f_w = (f's T_w_f * T_f_s0 * T_cam0_cam0p * T_s0_f)^-1 (:874-877), and every landmark of the
+    // problem is flagged outlier if its scale factor at the solution exceeds 2 / focal, else moved by its delta (:880-899).
+    bool landmarkOptimizationNoFov(LocalMapSnapshot& map, int f, int fp, Pose& T_cam0_cam0p, double info_scale) {
+        NoFovFlat F;
+        if (!nofov_flatten(map, f, fp, T_cam0_cam0p, info_scale, F)) { _err = "landmarkOptimizationNoFov: bad frame index"; return false; }
+        sadvio_solve_options o; sadvio_ba_default_options(&o);
+        o.huber_a = std::sqrt(1.345);                                                     // :753
+        const int n = F.pb.n_lmk;
+        std::vector<double> dl(3 * (size_t)std::max(n, 1)), gn(std::max(n, 1));
+        std::vector<int32_t> inl(std::max(n, 1), 1);
+        sadvio_nofov_result r{};
+        r.lambda = 1.0;
+        const int rc = sadvio_ba_nofov_scale(_h, &F.pb, &o, &_sum, &r, dl.data(), gn.data(), inl.data());
+        // no landmark and a constant scale: nothing to solve, Ceres returns the start point (lambda = 1)
+        if (rc == SADVIO_E_INVALID_ARG && n == 0) r.lambda = 1.0;
+        else if (rc != SADVIO_OK) { _err = sadvio_ba_last_error(_h); return false; }
+        for (double& x : T_cam0_cam0p.t) x *= r.lambda;                                   // :874
+        const Pose& Ts0 = map.frames[f].cameras[0].T_s_f;
+        const Pose T_f0_f0p = pose_mul(pose_mul(pose_inv(Ts0), T_cam0_cam0p), Ts0);      // :875-876
+        map.frames[fp].T_f_w = pose_inv(pose_mul(pose_inv(map.frames[f].T_f_w), T_f0_f0p));   // :877
+        for (int k = 0; k < n; k++) {                                                     // :880-899
+            LandmarkState& L = map.landmarks[F.lmk_src[k]];
+            if (!inl[k]) { L.outlier = true; continue; }
+            for (int a = 0; a < 3; a++) L.p[a] += dl[3 * (size_t)k + a];
+        }
+        return true;
     }
 
     // BundleAdjustmentCERESAnalytic::marginalize (…Analytic.cpp:431-663) with Marginalization::preMarginalize

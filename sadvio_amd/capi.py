@@ -71,6 +71,18 @@ class ViInitResultC(C.Structure):
                 ("R_w_i", C.c_double * 9), ("scale", C.c_double)]
 
 
+class NoFovProblemC(C.Structure):
+    _fields_ = [("n_lmk", C.c_int32), ("n_obs", C.c_int32), ("n_frames", C.c_int32), ("n_cam", C.c_int32), ("cam0", C.c_int32),
+                ("fix_scale", C.c_int32), ("frame_T_f_w", _dp), ("cam_T_s_f", _dp), ("T_cam0_cam0p", _dp), ("info_scale", C.c_double),
+                ("gate", C.c_double), ("lmk_p", _dp), ("scale_bearing", _dp), ("scale_cam", _ip), ("lmk_obs_ptr", _ip),
+                ("obs_frame", _ip), ("obs_cam", _ip), ("obs_bearing", _dp)]
+
+
+class NoFovResultC(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("usable", C.c_int32), ("scale_fixed", C.c_int32), ("n_inliers", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 class LineSetC(C.Structure):
     _fields_ = [("n_line", C.c_int32), ("n_obs", C.c_int32), ("line_id", _lp), ("line_T_w_l", _dp), ("line_model", _dp),
                 ("line_const", _bp), ("line_obs_ptr", _ip), ("obs_kf", _ip), ("obs_cam", _ip), ("obs_meas", _dp)]
@@ -199,6 +211,28 @@ def make_viinit_problem(T_f_w, vel, factors, optim_scale=False, optim_bias=False
 def viinit_result_to_dict(rc, s, r: ViInitResultC, dv) -> dict:
     return {"rc": rc, "summary": s, "r_wi": np.array(r.r_wi[:]), "lambda": float(r.lambda_), "dba": np.array(r.dba[:]),
             "dbg": np.array(r.dbg[:]), "R_w_i": np.array(r.R_w_i[:]).reshape(3, 3), "scale": float(r.scale), "dv": dv}
+
+
+def nofov_options() -> SolveOptions:
+    """landmarkOptimizationNoFov (AngularAdjustmentCERESAnalytic.cpp:753, :857-868): LM, 20 iterations, function_tolerance
+    1e-3, HuberLoss(sqrt(1.345)) on the visual factors (never on the scale prior)."""
+    o = reference_options()
+    o.huber_a = 1.345 ** 0.5
+    return o
+
+
+def make_nofov_problem(frame_T_f_w, cam_T_s_f, T_cam0_cam0p, lmk_p, scale_bearing, scale_cam, lmk_obs_ptr, obs_frame, obs_cam,
+                       obs_bearing, cam0=0, fix_scale=-1, info_scale=0.0, gate=0.02):
+    """(NoFovProblemC, keep-alive tuple) from arrays; see sadvio_nofov_problem in include/sadvio_ba.h."""
+    d = lambda a, m: np.ascontiguousarray(a, dtype=np.float64).reshape(-1, m)
+    i = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    T = d(frame_T_f_w, 12); Ts = d(cam_T_s_f, 12); Tm = d(T_cam0_cam0p, 12)
+    lp = d(lmk_p, 3); sb = d(scale_bearing, 3); sc = i(scale_cam); ptr = i(lmk_obs_ptr); of = i(obs_frame); oc = i(obs_cam)
+    ob = d(obs_bearing, 3)
+    ip = lambda a: a.ctypes.data_as(_ip)
+    P = NoFovProblemC(lp.shape[0], of.shape[0], T.shape[0], Ts.shape[0], int(cam0), int(fix_scale), _ptr(T), _ptr(Ts), _ptr(Tm),
+                      float(info_scale), float(gate), _ptr(lp), _ptr(sb), ip(sc), ip(ptr), ip(of), ip(oc), _ptr(ob))
+    return P, (T, Ts, Tm, lp, sb, sc, ptr, of, oc, ob)
 
 
 def gn_options(iters: int = 10) -> SolveOptions:
@@ -371,6 +405,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.sadvio_ba_linearize.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp]
     lib.sadvio_ba_vi_init.argtypes = [C.c_void_p, C.POINTER(ViInitProblemC), C.POINTER(SolveOptions), C.POINTER(SolveSummary),
                                       C.POINTER(ViInitResultC), _dp]
+    lib.sadvio_ba_nofov_scale.argtypes = [C.c_void_p, C.POINTER(NoFovProblemC), C.POINTER(SolveOptions), C.POINTER(SolveSummary),
+                                          C.POINTER(NoFovResultC), _dp, _dp, _ip]
     lib.sadvio_ba_landmark_chi2.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, _dp, _ip]
     lib.sadvio_ba_get_kernel_times.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), _dp, _lp]
     lib.sadvio_ba_last_error.argtypes = [C.c_void_p]
@@ -688,6 +724,21 @@ class Backend:
         if rc not in (0, E_NOT_USABLE):
             self._check(rc, "vi_init")
         return viinit_result_to_dict(rc, s, r, dv)
+
+    def nofov_scale(self, opts: SolveOptions = None, raw_rc: bool = False, **kw):
+        """AngularAdjustmentCERESAnalytic::landmarkOptimizationNoFov (AngularAdjustmentCERESAnalytic.cpp:741-907) on the device;
+        see make_nofov_problem for the arguments. rc SADVIO_E_NOT_USABLE is returned in the dict (the outputs are filled);
+        raw_rc=True also returns SADVIO_E_INVALID_ARG there instead of raising."""
+        P, keep = make_nofov_problem(**kw)
+        n = P.n_lmk
+        s = SolveSummary(); r = NoFovResultC()
+        dl = np.zeros((n, 3)); gn = np.zeros(n); inl = np.zeros(n, dtype=np.int32)
+        rc = self.lib.sadvio_ba_nofov_scale(self.h, C.byref(P), C.byref(opts or nofov_options()), C.byref(s), C.byref(r), _ptr(dl),
+                                            _ptr(gn), inl.ctypes.data_as(_ip))
+        if rc not in (0, E_NOT_USABLE) and not (raw_rc and rc == E_INVALID_ARG):
+            self._check(rc, "nofov_scale")
+        return {"rc": rc, "summary": s, "lambda": float(r.lambda_), "usable": bool(r.usable), "scale_fixed": bool(r.scale_fixed),
+                "n_inliers": int(r.n_inliers), "lmk_delta": dl, "gate_norm": gn, "inlier": inl}
 
     def kernel_times(self):
         cap = 32

@@ -24,6 +24,7 @@
 #include "marg_kernels.h"
 #include "lm_kernels.h"
 #include "viinit_kernels.h"
+#include "nofov_kernels.h"
 
 using namespace sadvio;
 
@@ -3411,6 +3412,142 @@ int sadvio_ba_vi_init(sadvio_ba_handle* h, const sadvio_viinit_problem* pb, cons
         for (int i = 0; i < n; i++)
             for (int a = 0; a < 3; a++) dv3[3 * i + a] = vcol[i] >= 0 ? out[vcol[i] + a] : 0.0;
     return S.termination == SADVIO_TERM_FAILURE ? SADVIO_E_NOT_USABLE : SADVIO_OK;
+}
+
+// landmarkOptimizationNoFov (AngularAdjustmentCERESAnalytic.cpp:741-907): validation and the constant tables on the host,
+// the whole LM solve and the gate in one launch of k_nofov (nofov_kernels.h)
+int sadvio_ba_nofov_scale(sadvio_ba_handle* h, const sadvio_nofov_problem* pb, const sadvio_solve_options* opts, sadvio_solve_summary* sum,
+                          sadvio_nofov_result* res, double* lmk_delta3, double* gate_norm, int32_t* inlier) {
+    if (!h) return SADVIO_E_INVALID_ARG;
+    if (!pb || !opts || pb->n_lmk < 0 || pb->n_obs < 0 || pb->n_frames < 1 || pb->n_cam < 1 || !pb->frame_T_f_w || !pb->cam_T_s_f ||
+        !pb->T_cam0_cam0p || pb->cam0 < 0 || pb->cam0 >= pb->n_cam || pb->fix_scale < -1 || pb->fix_scale > 1 ||
+        (pb->n_lmk > 0 && (!pb->lmk_p || !pb->scale_bearing || !pb->scale_cam || !pb->lmk_obs_ptr)) ||
+        (pb->n_obs > 0 && (!pb->obs_frame || !pb->obs_cam || !pb->obs_bearing || !pb->lmk_obs_ptr))) {
+        h->err = "nofov_scale: bad argument"; return SADVIO_E_INVALID_ARG;
+    }
+    const int n = pb->n_lmk, no = pb->n_obs, nfr = pb->n_frames, nc = pb->n_cam;
+    if (n > NOFOV_MAX_LMK) { h->err = "nofov_scale: more than 65536 landmarks"; return SADVIO_E_INVALID_ARG; }
+    if (n > 0) {
+        if (pb->lmk_obs_ptr[0] != 0 || pb->lmk_obs_ptr[n] != no) { h->err = "nofov_scale: lmk_obs_ptr does not span n_obs"; return SADVIO_E_INVALID_ARG; }
+        for (int l = 0; l < n; l++) {
+            const int c = pb->lmk_obs_ptr[l + 1] - pb->lmk_obs_ptr[l];
+            if (c < 0) { h->err = "nofov_scale: lmk_obs_ptr is not monotone"; return SADVIO_E_INVALID_ARG; }
+            if (c > NOFOV_MAX_OBS_PER_LMK) { h->err = "nofov_scale: more than 16 angular factors on a landmark"; return SADVIO_E_INVALID_ARG; }
+            if (pb->scale_cam[l] < 0 || pb->scale_cam[l] >= nc) { h->err = "nofov_scale: scale_cam out of range"; return SADVIO_E_INVALID_ARG; }
+        }
+    } else if (no != 0) { h->err = "nofov_scale: observations without landmarks"; return SADVIO_E_INVALID_ARG; }
+    for (int o = 0; o < no; o++)
+        if (pb->obs_frame[o] < 0 || pb->obs_frame[o] >= nfr || pb->obs_cam[o] < 0 || pb->obs_cam[o] >= nc) {
+            h->err = "nofov_scale: observation index out of range"; return SADVIO_E_INVALID_ARG;
+        }
+    const double* Tm = pb->T_cam0_cam0p;
+    int fixed = pb->fix_scale;
+    if (fixed < 0) {   // :769-772: geometry::log_so3 (geometry.h:149-166) of the rotation, norm of the translation
+        double c = (Tm[0] + Tm[4] + Tm[8]) / 2.0 - 0.5;
+        c = std::min(std::max(c, -1.0), 1.0);
+        const double ang = std::acos(c);
+        const double d[3] = {Tm[7] - Tm[5], Tm[2] - Tm[6], Tm[3] - Tm[1]};
+        const double f = (std::fabs(std::sin(ang)) < 1e-9 || ang < 1e-9) ? 0.5 : ang / (2.0 * std::sin(ang));
+        const double rot = f * std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        const double tn = std::sqrt(Tm[9] * Tm[9] + Tm[10] * Tm[10] + Tm[11] * Tm[11]);
+        fixed = (rot < 0.05 || tn < 0.01) ? 1 : 0;
+    }
+    if (n == 0 && fixed) { h->err = "nofov_scale: no landmark and a constant scale: nothing to solve"; return SADVIO_E_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(h->device));
+    // constant tables: a zero-delta pose table per frame (angular_factor), A | b0 | v per camera (scale factor)
+    std::vector<double> ftab(NOFOV_FTAB * (size_t)nfr), ctab(NOFOV_CTAB * (size_t)nc);
+    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int k = 0; k < nfr; k++) {
+        const double* T = pb->frame_T_f_w + 12 * (size_t)k;
+        double* o = &ftab[NOFOV_FTAB * (size_t)k];
+        memcpy(o, T, 96); memcpy(o + 12, I3, 72); memcpy(o + 21, T, 72); memcpy(o + 30, I3, 72);
+    }
+    auto mul = [](const double* A, const double* B, double* C) {   // C = A B (3 x 3 row-major)
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+    };
+    auto mv = [](const double* A, const double* x, double* y) { for (int i = 0; i < 3; i++) y[i] = A[3 * i] * x[0] + A[3 * i + 1] * x[1] + A[3 * i + 2] * x[2]; };
+    const double* T0 = pb->cam_T_s_f + 12 * (size_t)pb->cam0;
+    const double* Tf = pb->frame_T_f_w;
+    double Rcw[9], tcw[3], R0t[9], Rt[9];
+    mul(T0, Tf, Rcw); mv(T0, Tf + 9, tcw);
+    for (int a = 0; a < 3; a++) tcw[a] += T0[9 + a];                               // T_cam0_w = T_s_f(cam0) T_f_w(f)
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { R0t[3 * i + j] = T0[3 * j + i]; Rt[3 * i + j] = Tm[3 * j + i]; }
+    for (int c = 0; c < nc; c++) {
+        const double* Ts = pb->cam_T_s_f + 12 * (size_t)c;
+        double Rc[9], tc[3], q[3], B[9];
+        mul(Ts, R0t, Rc); mv(Rc, T0 + 9, q);
+        for (int a = 0; a < 3; a++) tc[a] = Ts[9 + a] - q[a];                         // T_cam_cam0 = T_s_f(c) T_s_f(cam0)^-1
+        mul(Rc, Rt, B);                                                               // Rc R^T
+        double* o = &ctab[NOFOV_CTAB * (size_t)c];
+        mul(B, Rcw, o);
+        mv(B, tcw, o + 9);
+        for (int a = 0; a < 3; a++) o[9 + a] += tc[a];
+        mv(B, Tm + 9, o + 12);
+    }
+    NoFovDev P{};
+    P.n_lmk = n; P.fixed = fixed; P.info = pb->info_scale; P.gate = pb->gate; P.huber_a = opts->huber_a;
+    P.o.max_num_iterations = opts->max_num_iterations; P.o.jacobi_scaling = opts->jacobi_scaling;
+    P.o.max_num_consecutive_invalid_steps = opts->max_num_consecutive_invalid_steps;
+    P.o.function_tolerance = opts->function_tolerance; P.o.gradient_tolerance = opts->gradient_tolerance;
+    P.o.parameter_tolerance = opts->parameter_tolerance; P.o.initial_radius = opts->initial_trust_region_radius;
+    P.o.max_radius = opts->max_trust_region_radius; P.o.min_radius = opts->min_trust_region_radius;
+    P.o.min_lm_diagonal = opts->min_lm_diagonal; P.o.max_lm_diagonal = opts->max_lm_diagonal; P.o.min_relative_decrease = opts->min_relative_decrease;
+    // one allocation: header | ftab | ftsf | ctab | lmk_p | sbear | obear | out | scratch | scam | optr | ofr | ocam
+    const size_t n_out = NOFOV_OUT * (size_t)n + NOFOV_SUM;
+    const size_t n_d = ftab.size() + 12 * (size_t)nc + ctab.size() + 6 * (size_t)n + 3 * (size_t)no + n_out + NOFOV_LS * (size_t)n;
+    const size_t n_i = (size_t)n + (size_t)n + 1 + 2 * (size_t)no;
+    const size_t hdr = (sizeof(NoFovDev) + 15) & ~(size_t)15;
+    DevBuf<char> buf;
+    HIP_TRY(buf.alloc(hdr + 8 * n_d + 4 * n_i + 64));
+    char* base = buf.p;
+    double* dft = (double*)(base + hdr); double* dts = dft + ftab.size(); double* dct = dts + 12 * (size_t)nc;
+    double* dlp = dct + ctab.size(); double* dsb = dlp + 3 * (size_t)n; double* dob = dsb + 3 * (size_t)n;
+    double* dout = dob + 3 * (size_t)no; double* dscr = dout + n_out;
+    int* dsc = (int*)(dscr + NOFOV_LS * (size_t)n); int* dptr = dsc + n; int* dofr = dptr + n + 1; int* docam = dofr + no;
+    P.ftab = dft; P.ftsf = dts; P.ctab = dct; P.lmk_p = dlp; P.sbear = dsb; P.obear = dob; P.out = dout; P.scratch = dscr;
+    P.scam = dsc; P.optr = dptr; P.ofr = dofr; P.ocam = docam;
+    std::vector<int> zero_ptr(1, 0);
+    HIP_TRY(hipMemcpyAsync(base, &P, sizeof(P), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dft, ftab.data(), 8 * ftab.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dts, pb->cam_T_s_f, 96 * (size_t)nc, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dct, ctab.data(), 8 * ctab.size(), hipMemcpyHostToDevice, h->stream));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(dlp, pb->lmk_p, 24 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dsb, pb->scale_bearing, 24 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dsc, pb->scale_cam, 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dptr, pb->lmk_obs_ptr, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    } else HIP_TRY(hipMemcpyAsync(dptr, zero_ptr.data(), 4, hipMemcpyHostToDevice, h->stream));
+    if (no) {
+        HIP_TRY(hipMemcpyAsync(dob, pb->obs_bearing, 24 * (size_t)no, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dofr, pb->obs_frame, 4 * (size_t)no, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(docam, pb->obs_cam, 4 * (size_t)no, hipMemcpyHostToDevice, h->stream));
+    }
+    hipLaunchKernelGGL(k_nofov, dim3(1), dim3(NOFOV_THREADS), 0, h->stream, (const NoFovDev*)base);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> out(n_out);
+    HIP_TRY(hipMemcpyAsync(out.data(), dout, 8 * n_out, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const double* s = out.data() + NOFOV_OUT * (size_t)n;
+    sadvio_solve_summary S{};
+    S.initial_cost = s[0]; S.final_cost = s[1]; S.final_radius = s[2]; S.iterations = (int)s[3]; S.termination = (int)s[4];
+    S.num_successful_steps = (int)s[5]; S.num_unsuccessful_steps = (int)s[6];
+    const double lam = s[7];
+    const bool usable = S.termination != SADVIO_TERM_FAILURE && lam >= 0.5 && lam <= 1.5;   // :870-871
+    int n_in = 0;
+    for (int l = 0; l < n; l++) {
+        const double* o = out.data() + NOFOV_OUT * (size_t)l;
+        if (lmk_delta3) memcpy(lmk_delta3 + 3 * (size_t)l, o, 24);
+        if (gate_norm) gate_norm[l] = o[3];
+        if (inlier) inlier[l] = o[4] != 0.0 ? 1 : 0;
+        n_in += o[4] != 0.0 ? 1 : 0;
+    }
+    if (sum) *sum = S;
+    if (res) {
+        memset(res, 0, sizeof(*res));
+        res->lambda = lam; res->usable = usable ? 1 : 0; res->scale_fixed = fixed; res->n_inliers = n_in;
+    }
+    if (!usable) h->err = S.termination == SADVIO_TERM_FAILURE ? "nofov_scale: no usable solution" : "nofov_scale: lambda outside [0.5, 1.5]";
+    return usable ? SADVIO_OK : SADVIO_E_NOT_USABLE;
 }
 
 int sadvio_ba_set_window(sadvio_ba_handle* h, const sadvio_flat_window* window) { return sadvio_ba_set_windows(h, 1, window); }
