@@ -109,9 +109,11 @@ static void accumulate(double *A, double *b, int N, const double *J, const doubl
     }
 }
 
-int oracle_marginalize(const oracle_marg_request *rq, oracle_marg_result *res, int32_t *lmk_col_out, double *A_full,
-                       double *b_full, double *Ak_out, double *bk_out, double *U_out, double *Lambda_out, double *J_out,
-                       double *r0_out) {
+/* computeInformationAndGradient (marginalization.cpp:145-211) over the block list of marginalize(): the index layout
+ * (res, lmk_col_out) and, unless n < 4 (SADVIO_E_REFUSED, nothing allocated), *A_out [(m+n)^2] and *b_out [m+n], which the
+ * caller frees. */
+static int marg_information(const oracle_marg_request *rq, oracle_marg_result *res, int32_t *lmk_col_out, double **A_out,
+                            double **b_out) {
     const sadvio_flat_window *w = rq->win;
     /* index layout, marginalization.cpp:38-113 */
     int m = 6 + (rq->marg_has_imu ? 9 : 0) + 3 * rq->n_marg;
@@ -231,6 +233,34 @@ int oracle_marginalize(const oracle_marg_request *rq, oracle_marg_result *res, i
         for (int a = 0; a < 6; a++) col[a] = base + a;
         accumulate(A, b, N, J, r, 6, 6, col);
     }
+    free(lcol);
+    *A_out = A; *b_out = b;
+    return SADVIO_OK;
+}
+
+int oracle_marg_information(const oracle_marg_request *rq, oracle_marg_result *res, int32_t *lmk_col_out, double *A_full,
+                            double *b_full) {
+    oracle_marg_result r_ = {0, 0, 0, -1};
+    if (!res) res = &r_;
+    double *A, *b;
+    const int rc = marg_information(rq, res, lmk_col_out, &A, &b);
+    if (rc != SADVIO_OK) return rc;
+    const int N = res->m + res->n;
+    if (A_full) memcpy(A_full, A, sizeof(double) * (size_t)N * N);
+    if (b_full) memcpy(b_full, b, sizeof(double) * (size_t)N);
+    free(A); free(b);
+    return SADVIO_OK;
+}
+
+int oracle_marginalize(const oracle_marg_request *rq, oracle_marg_result *res, int32_t *lmk_col_out, double *A_full,
+                       double *b_full, double *Ak_out, double *bk_out, double *U_out, double *Lambda_out, double *J_out,
+                       double *r0_out) {
+    oracle_marg_result r_ = {0, 0, 0, -1};
+    if (!res) res = &r_;
+    double *A, *b;
+    const int rc = marg_information(rq, res, lmk_col_out, &A, &b);
+    if (rc != SADVIO_OK) return rc;
+    const int m = res->m, n = res->n, N = m + n;
     if (A_full) memcpy(A_full, A, sizeof(double) * (size_t)N * N);
     if (b_full) memcpy(b_full, b, sizeof(double) * (size_t)N);
 
@@ -280,7 +310,7 @@ int oracle_marginalize(const oracle_marg_request *rq, oracle_marg_result *res, i
     double cut_n = marg_cut(ev2, n, rq->eig_cut_mode);
     for (int k = 0; k < n; k++)
         if (ev2[k] > cut_n) nf++;
-    if (res) res->n_full = nf;
+    res->n_full = nf;
     int c = 0;
     for (int k = 0; k < n; k++) {
         if (!(ev2[k] > cut_n)) continue;
@@ -295,7 +325,7 @@ int oracle_marginalize(const oracle_marg_request *rq, oracle_marg_result *res, i
         if (r0_out) r0_out[c] = -sqrt(1.0 / lam) * dot;                             /* :526-527 */
         c++;
     }
-    free(A); free(b); free(lcol); free(Amm); free(ev); free(V); free(Ainv); free(T); free(Ak); free(bk);
+    free(A); free(b); free(Amm); free(ev); free(V); free(Ainv); free(T); free(Ak); free(bk);
     free(Aks); free(ev2); free(V2);
     return SADVIO_OK;
 }

@@ -91,6 +91,7 @@ def lib():
         _lib.oracle_factor_imu_bias.argtypes = [C.POINTER(ImuFactorC), _dp, _dp, _dp, _dp, _dp, _dp, _dp]
         _lib.oracle_marginalize.argtypes = [C.POINTER(MargRequest), C.POINTER(MargResult), _ip, _dp, _dp, _dp, _dp,
                                             _dp, _dp, _dp, _dp]
+        _lib.oracle_marg_information.argtypes = [C.POINTER(MargRequest), C.POINTER(MargResult), _ip, _dp, _dp]
         _lib.oracle_sym_eig.argtypes = [_dp, C.c_int32, _dp, _dp]
     return _lib
 
@@ -216,6 +217,46 @@ def marginalize(w: FlatWindow, kf_marg, lmk_marg, lmk_keep, kf_keep=-1, marg_has
                 eig_cut="noise_floor"):
     """oracle_marginalize with the same calling convention as capi.Backend.marginalize. Returns None when refused.
     want_full: also return A_full [(m+n)^2], b_full [m+n] (the un-reduced information / gradient, computeInformationAndGradient)."""
+    rq, keep, kp, mk = _marg_request(w, kf_marg, lmk_marg, lmk_keep, kf_keep, marg_has_imu, imu, priors, last, eig_cut)
+    n = (15 if kf_keep >= 0 else 0) + 3 * len(kp)
+    res = MargResult()
+    lmk_col = np.zeros(max(len(kp), 1), dtype=np.int32); Jo = np.zeros(max(n * n, 1)); r0o = np.zeros(max(n, 1))
+    Ak = np.zeros((max(n, 1), max(n, 1))); bk = np.zeros(max(n, 1))
+    m_max = (15 if marg_has_imu else 6) + 3 * len(mk)
+    Af = np.zeros((m_max + n) ** 2) if want_full else None
+    bf = np.zeros(m_max + n) if want_full else None
+    rc = lib().oracle_marginalize(C.byref(rq), C.byref(res), lmk_col.ctypes.data_as(_ip), _p(Af) if want_full else _dp(), _p(bf) if want_full else _dp(),
+                                  _p(Ak), _p(bk), _dp(), _dp(), _p(Jo), _p(r0o))
+    if rc != 0:
+        return None
+    nf = res.n_full
+    extra = {}
+    if want_full:
+        N = res.m + res.n
+        extra = {"A_full": Af[: N * N].reshape(N, N).copy(), "b_full": bf[:N].copy()}
+    return {**extra, "J": Jo[: nf * n].reshape(nf, n).copy(), "r0": r0o[:nf].copy(), "kf_keep": kf_keep, "kf_col": res.kf_col,
+            "lmk_index": kp.copy(), "lmk_col": lmk_col[: len(kp)].copy(), "m": res.m, "n": res.n, "n_full": nf, "Ak": Ak, "bk": bk}
+
+
+def marg_information(w: FlatWindow, kf_marg, lmk_marg, lmk_keep, kf_keep=-1, marg_has_imu=False, imu=None, priors=(), last=None):
+    """oracle_marg_information: marginalize()'s A_full [(m+n)^2] / b_full [m+n] and index layout (m, n, kf_col, lmk_col),
+    without the Schur complement and eigen-decompositions. Returns None when refused (n < 4)."""
+    rq, keep, kp, mk = _marg_request(w, kf_marg, lmk_marg, lmk_keep, kf_keep, marg_has_imu, imu, priors, last, "noise_floor")
+    n = (15 if kf_keep >= 0 else 0) + 3 * len(kp)
+    N = (15 if marg_has_imu else 6) + 3 * len(mk) + n
+    res = MargResult()
+    lmk_col = np.zeros(max(len(kp), 1), dtype=np.int32)
+    Af = np.zeros((N, N)); bf = np.zeros(N)
+    rc = lib().oracle_marg_information(C.byref(rq), C.byref(res), lmk_col.ctypes.data_as(_ip), _p(Af), _p(bf))
+    if rc != 0:
+        return None
+    assert res.m + res.n == N
+    return {"A_full": Af, "b_full": bf, "m": res.m, "n": res.n, "kf_keep": kf_keep, "kf_col": res.kf_col, "lmk_index": kp.copy(),
+            "lmk_col": lmk_col[: len(kp)].copy()}
+
+
+def _marg_request(w, kf_marg, lmk_marg, lmk_keep, kf_keep, marg_has_imu, imu, priors, last, eig_cut):
+    """The oracle_marg_request of marginalize() / marg_information() and the arrays it points into (keep them alive)."""
     wc, wkeep = S.window_to_c(w)
     rq = MargRequest()
     rq.win = C.pointer(wc)
@@ -242,24 +283,7 @@ def marginalize(w: FlatWindow, kf_marg, lmk_marg, lmk_keep, kf_keep=-1, marg_has
         rq.last_kf, rq.last_kf_col = int(last.get("kf_keep", -1)), int(last.get("kf_col", 0))
         rq.last_n_keep, rq.last_lmk_index, rq.last_lmk_col = len(li), li.ctypes.data_as(_ip), lc.ctypes.data_as(_ip)
         keep += [J, r0, li, lc]
-    n = (15 if kf_keep >= 0 else 0) + 3 * len(kp)
-    res = MargResult()
-    lmk_col = np.zeros(max(len(kp), 1), dtype=np.int32); Jo = np.zeros(max(n * n, 1)); r0o = np.zeros(max(n, 1))
-    Ak = np.zeros((max(n, 1), max(n, 1))); bk = np.zeros(max(n, 1))
-    m_max = (15 if marg_has_imu else 6) + 3 * len(mk)
-    Af = np.zeros((m_max + n) ** 2) if want_full else None
-    bf = np.zeros(m_max + n) if want_full else None
-    rc = lib().oracle_marginalize(C.byref(rq), C.byref(res), lmk_col.ctypes.data_as(_ip), _p(Af) if want_full else _dp(), _p(bf) if want_full else _dp(),
-                                  _p(Ak), _p(bk), _dp(), _dp(), _p(Jo), _p(r0o))
-    if rc != 0:
-        return None
-    nf = res.n_full
-    extra = {}
-    if want_full:
-        N = res.m + res.n
-        extra = {"A_full": Af[: N * N].reshape(N, N).copy(), "b_full": bf[:N].copy()}
-    return {**extra, "J": Jo[: nf * n].reshape(nf, n).copy(), "r0": r0o[:nf].copy(), "kf_keep": kf_keep, "kf_col": res.kf_col,
-            "lmk_index": kp.copy(), "lmk_col": lmk_col[: len(kp)].copy(), "m": res.m, "n": res.n, "n_full": nf, "Ak": Ak, "bk": bk}
+    return rq, keep, kp, mk
 
 
 def marginalize_relative(w: FlatWindow, kf_a: int, kf_b: int, eig_cut="noise_floor"):

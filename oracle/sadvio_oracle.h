@@ -146,6 +146,10 @@ typedef struct oracle_marg_result {
  * Lambda[n], J[n*n] (n_full x n packed row-major), r0[n]. */
 int oracle_marginalize(const oracle_marg_request *rq, oracle_marg_result *res, int32_t *lmk_col, double *A_full,
                        double *b_full, double *Ak, double *bk, double *U, double *Lambda, double *J, double *r0);
+/* oracle_marginalize stopped after computeInformationAndGradient (marginalization.cpp:145-211): the same index layout
+ * (res->n_full stays 0), lmk_col[n_keep], A_full[(m+n)^2], b_full[m+n] (any may be NULL). SADVIO_E_REFUSED when n < 4. */
+int oracle_marg_information(const oracle_marg_request *rq, oracle_marg_result *res, int32_t *lmk_col, double *A_full,
+                            double *b_full);
 
 /* NFR sparsification of a dense prior into the sparse-branch factor list (sparsifyVIO / sparsifyVO,
  * marginalization.cpp:362-514). out has room for n_keep + 1 factors. */

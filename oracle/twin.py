@@ -25,6 +25,8 @@ tests/golden/make_golden.py generates the committed golden vectors from THIS mod
 """
 from __future__ import annotations
 
+import inspect
+
 import numpy as np
 
 try:
@@ -545,19 +547,25 @@ def sym_eig(B, A):
 def schur_prior(B, A, b, m, cut=1e-12):
     """computeSchurComplement + rankReveallingDecomposition + computeJacobiansAndResiduals on A = sum J^T J, b = sum J^T r
     (first m columns marginalised). `cut`: the eigenvalue threshold — the reference's absolute _eps = 1e-12, or a callable
-    lambda_max -> threshold for the documented relative floor of oracle/marg.c. Returns Ak, bk, U, Lambda, J, r0, n_full."""
+    lambda_max -> threshold, or (lambda_max, dim) -> threshold with dim the size of the decomposed matrix (m for Amm, n for
+    Ak), for the documented relative floor of oracle/marg.c. Returns Ak, bk, U, Lambda, J, r0, n_full."""
     A = B.a(A); b = B.a(b)
-    thr = (lambda lmax: cut(lmax)) if callable(cut) else (lambda lmax: cut)
+    if not callable(cut):
+        thr = lambda lmax, dim: cut                                  # noqa: E731
+    elif len(inspect.signature(cut).parameters) >= 2:
+        thr = cut
+    else:
+        thr = lambda lmax, dim: cut(lmax)                            # noqa: E731
     Amm = (A[:m, :m] + A[:m, :m].T) / 2                             # :232
     lam, V = sym_eig(B, Amm)
-    t = thr(max(abs(x) for x in lam))
+    t = thr(max(abs(x) for x in lam), m)
     inv = np.array([1 / x if x > t else B.s(0) for x in lam], dtype=B.dtype)   # :234-238
     Ammi = (V * inv[None, :]) @ V.T
     Arm = A[m:, :m]; Arr = A[m:, m:]
     Ak = Arr - Arm @ Ammi @ Arm.T                                   # :245
     bk = b[m:] - Arm @ Ammi @ b[:m]                                 # :246
     lk, Uf = sym_eig(B, (Ak + Ak.T) / 2)                            # rankReveallingDecomposition (:318-342)
-    t = thr(max(abs(x) for x in lk))
+    t = thr(max(abs(x) for x in lk), len(lk))
     keep = [i for i in range(len(lk)) if lk[i] > t]
     U = Uf[:, keep]; Lam = lk[keep]
     sq = np.array([B.sqrt(x) for x in Lam], dtype=B.dtype)

@@ -36,7 +36,7 @@ def random_prior(w, n_keep, kf_keep, rng, scale=3.0, rank_deficit=2):
     return {"J": J, "r0": r0, "kf_keep": kf_keep, "kf_col": kf_col, "lmk_index": lmk_index, "lmk_col": lmk_col}
 
 
-def compare(backend_cls, oracle_lib, w, opts, vio=False, golden=None):
+def compare(backend_cls, oracle_lib, w, opts, vio=False, golden=None, n_threads=1):
     be = backend_cls(device=0)
     try:
         be.set_windows([w])
@@ -46,7 +46,13 @@ def compare(backend_cls, oracle_lib, w, opts, vio=False, golden=None):
     finally:
         be.close()
     ref = (cached_oracle_solve(golden, oracle_lib, w, opts, dense_prior=w.dense_prior) if golden
-           else oracle_lib.solve(w, opts, dense_prior=w.dense_prior))
+           else oracle_lib.solve(w, opts, dense_prior=w.dense_prior, n_threads=n_threads))
+    check_solve(s, d, trace, ref, vio)
+    return s, d, ref
+
+
+def check_solve(s, d, trace, ref, vio=False):
+    """A device solve (summary, deltas, trace) against the oracle's."""
     rs = ref["summary"]
     assert np.isclose(s.initial_cost, rs.initial_cost, rtol=1e-10)
     assert np.isclose(s.final_cost, rs.final_cost, rtol=1e-9)
@@ -58,7 +64,6 @@ def compare(backend_cls, oracle_lib, w, opts, vio=False, golden=None):
     if vio:
         for k in ("dv", "dba", "dbg"):
             assert np.abs(d[k] - ref[k]).max() <= POSE_TOL
-    return s, d, ref
 
 
 @pytest.mark.parametrize("factor", [capi.FACTOR_PIXEL, capi.FACTOR_ANGULAR])

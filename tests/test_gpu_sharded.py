@@ -254,3 +254,105 @@ def test_sharded_vio_window_with_the_dense_prior(backend_cls, oracle_lib, world)
         assert np.array_equal(out[r][1]["lmk"][n_own:], out[0][1]["lmk"][shards[0].n_own:])   # the kept landmarks too
     lmk = sharding.gather_landmarks(w, shards, [o[1]["lmk"] for o in out])
     assert lmk_err(lmk, ref["lmk"]) <= LMK_TOL
+
+
+def _solve_sharded_batch(backend_cls, windows, opts, world):
+    """Every window of the batch sharded over `world` emulated ranks, one set_windows per rank."""
+    coll = HostAllReduce(world)
+    shards = [[sharding.shard_window(w, r, world) for w in windows] for r in range(world)]
+    out = [None] * world
+
+    def run(rank):
+        be = backend_cls(device=0)
+        try:
+            be.set_collective(rank, world, coll.fn(rank))
+            be.set_windows(shards[rank])
+            sums = be.solve(opts)
+            out[rank] = [(sums[i], be.get_deltas(i)) for i in range(len(windows))]
+        except Exception as e:
+            out[rank] = e
+            coll.barrier.abort()
+        finally:
+            be.close()
+
+    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    for o in out:
+        if isinstance(o, Exception):
+            raise o
+    return out, shards
+
+
+def test_sharded_batch_with_dense_priors_of_different_row_counts(backend_cls, oracle_lib):
+    """Two windows in one sharded batch (2 emulated ranks) whose dense priors have n_full = 133 and 283 rows: k_prior_r / k_prior_m run
+    one grid sized by the batch's largest prior, and the guarded partial-sum store must keep the shorter window's blocks past its rows
+    out of the cost. Every rank must leave with the same bits, and each window must match its own oracle solve."""
+    from test_gpu_prior import random_prior
+    from vio_helpers import make_vio_window
+    ws = [make_vio_window(n_kf=6, n_lmk=900, seed=s) for s in (174, 175)]
+    for w, n_keep, s in zip(ws, (40, 90), (62, 63)):
+        w.dense_prior = random_prior(w, n_keep, w.n_kf - 2, np.random.default_rng(s), rank_deficit=2)
+    assert [w.dense_prior["J"].shape[0] for w in ws] == [133, 283]
+    opts = capi.reference_options()
+    out, shards = _solve_sharded_batch(backend_cls, ws, opts, 2)
+    for i, w in enumerate(ws):
+        ref = oracle_lib.solve(w, opts, dense_prior=w.dense_prior)
+        rs = ref["summary"]
+        assert rs.num_successful_steps > 0
+        for r in range(2):
+            s, d = out[r][i]
+            assert (s.iterations, s.termination, s.num_successful_steps) == (rs.iterations, rs.termination, rs.num_successful_steps)
+            assert np.isclose(s.initial_cost, rs.initial_cost, rtol=1e-10) and np.isclose(s.final_cost, rs.final_cost, rtol=1e-9)
+            for k in ("pose", "dv", "dba", "dbg"):
+                assert np.abs(d[k] - ref[k]).max() <= POSE_TOL, (i, k)
+        s0, d0 = out[0][i]
+        s1, d1 = out[1][i]
+        assert (s1.initial_cost, s1.final_cost) == (s0.initial_cost, s0.final_cost)      # same bits on every rank
+        for k in ("pose", "dv", "dba", "dbg"):
+            assert np.array_equal(d1[k], d0[k]), (i, k)
+        assert np.array_equal(d1["lmk"][shards[1][i].n_own:], d0["lmk"][shards[0][i].n_own:])   # the kept landmarks too
+        lmk = sharding.gather_landmarks(w, [shards[0][i], shards[1][i]], [out[0][i][1]["lmk"], out[1][i][1]["lmk"]])
+        assert lmk_err(lmk, ref["lmk"]) <= LMK_TOL
+
+
+def test_dense_prior_refused_when_a_kept_landmark_has_observations_on_rank_1(backend_cls, oracle_lib):
+    """A sharded window's kept landmarks carry their observations on rank 0 only (sadvio_ba.h): a rank-1 shard that holds some is
+    refused with SADVIO_E_INVALID_ARG naming the landmark, by set_windows and by set_dense_prior; correct shards then solve."""
+    from test_gpu_prior import random_prior
+    from vio_helpers import make_vio_window
+    w = make_vio_window(n_kf=6, n_lmk=900, seed=176)
+    w.dense_prior = random_prior(w, 30, w.n_kf - 2, np.random.default_rng(64), rank_deficit=2)
+    bad = sharding.shard_window(w, 0, 2)            # rank 0's shard: the kept landmarks with their observations
+    dp = bad.dense_prior
+    first = int(dp["lmk_index"][0])                 # the first kept landmark (lmk_col >= 0) the check meets
+    assert dp["lmk_col"][0] >= 0 and bad.lmk_obs_ptr[first + 1] > bad.lmk_obs_ptr[first]
+    want = f"landmark {first} has some on rank 1"
+    be = backend_cls(device=0)
+    try:
+        be.set_collective(1, 2, lambda *a: 0)
+        with pytest.raises(capi.SadvioError) as ei:
+            be.set_windows([bad])
+        assert f"rc={capi.E_INVALID_ARG}:" in str(ei.value) and want in str(ei.value)
+    finally:
+        be.close()
+    plain = sharding.shard_window(w, 0, 2)
+    plain.dense_prior = None
+    be = backend_cls(device=0)
+    try:
+        be.set_collective(1, 2, lambda *a: 0)
+        be.set_windows([plain])
+        with pytest.raises(capi.SadvioError) as ei:
+            be.set_dense_prior(0, dp)
+        assert f"rc={capi.E_INVALID_ARG}:" in str(ei.value) and want in str(ei.value)
+    finally:
+        be.close()
+    opts = capi.reference_options()
+    out, shards = _solve_sharded_batch(backend_cls, [w], opts, 2)
+    ref = oracle_lib.solve(w, opts, dense_prior=w.dense_prior)
+    for r in range(2):
+        s, d = out[r][0]
+        assert np.isclose(s.final_cost, ref["summary"].final_cost, rtol=1e-9)
+        assert np.abs(d["pose"] - ref["pose"]).max() <= POSE_TOL
