@@ -20,6 +20,7 @@
 
 #include "../../include/sadvio_ba.h"
 #include "kernels.h"
+#include "tile_pack.h"
 #include "dense_chol.h"
 #include "marg_kernels.h"
 #include "lm_kernels.h"
@@ -232,7 +233,7 @@ struct LineSetHost {   // deep copy of a sadvio_line_set
 // and ~2 MB of fresh std::vectors per call are ~500 page faults (more than the layout arithmetic itself).
 struct LayoutScratch {
     std::vector<double> kf_T0, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_isig, lmk_p, obs_meas;
-    std::vector<int> kf_fidx, lmk_ob, lmk_oe, obs_kf, obs_cam, tile_kf, tile_row, pkf, pcam, run_max, idx, mark, add, kfs, slot_of, chunk_ob, chunk_lm, perm;
+    std::vector<int> kf_fidx, lmk_ob, lmk_oe, obs_kf, obs_cam, tile_kf, tile_row, tile_lmk, pack_order, pack_cut, pkf, pcam, run_max, idx, mark, add, kfs, slot_of, chunk_ob, chunk_lm, perm;
     std::vector<unsigned char> lmk_const, obs_slot, obs_lslot;
     std::vector<char> held;
 };
@@ -245,7 +246,7 @@ struct EnvCfg {
     int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
     double jacobi_tol = 1e-14;
     bool marg_last_small = false, marg_eig_mm = false, marg_pivoted = false, marg_unpivoted = false, pchol_swap = false, pchol_strict = false,
-         jacobi_b4 = false, jacobi_plain = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false;
+         jacobi_b4 = false, jacobi_plain = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false;
     void read() {
         auto on = [](const char* k) { return getenv(k) != nullptr; };
         auto num = [](const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; };
@@ -256,6 +257,7 @@ struct EnvCfg {
         marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_swap = on("SADVIO_PCHOL_SWAP"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         jacobi_b4 = on("SADVIO_JACOBI_B4"); jacobi_plain = on("SADVIO_JACOBI_PLAIN"); no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
         no_bcr = on("SADVIO_NO_BCR");
+        contig_tiles = on("SADVIO_CONTIG_TILES");   // A/B: single-round tiles as runs of consecutive landmarks (no packing, tile_pack.h)
         imu_items = on("SADVIO_IMU_ITEMS");   // A/B: the IMU pairs' entries through k_solve's item loop (the pre-0.5 path) on one device too
     }
 };
@@ -330,7 +332,7 @@ struct sadvio_ba_handle {
     DevBuf<double> d_cam_K, d_cam_T, d_cam_isig;
     DevBuf<double> d_lmk_p, d_xl, d_s_lmk;
     DevBuf<unsigned char> d_lmk_const;
-    DevBuf<int> d_lmk_ob, d_lmk_oe, d_obs_kf, d_obs_cam, d_tile_kf, d_tile_row;
+    DevBuf<int> d_lmk_ob, d_lmk_oe, d_obs_kf, d_obs_cam, d_tile_kf, d_tile_row, d_tile_lmk;
     DevBuf<int> d_pre_lane, d_pre_kf;     // first-round packets of the latency kernels (kernels.h: DevPtrs::pre_lane), few-tile submissions only
     bool pre_ok = false, pre_dirty = false;
     DevBuf<int> d_rank_col; DevBuf<double> d_rank_x;       // refine_rank_by_eigenvalue (guarded calls only): pivot column per step, the solved vectors
@@ -434,7 +436,7 @@ DevPtrs make_ptrs(sadvio_ba_handle* h, const SolveOpts& o, int state_stride) {
     P.lmk_const = h->has_lmk_const ? h->d_lmk_const.p : nullptr;
     P.lmk_ob = h->d_lmk_ob.p; P.lmk_oe = h->d_lmk_oe.p;
     P.obs_kf = h->d_obs_kf.p; P.obs_cam = h->d_obs_cam.p; P.obs_meas = h->d_obs_meas.p;
-    P.obs_slot = h->d_obs_slot.p; P.tile_kf = h->d_tile_kf.p; P.tile_row = h->d_tile_row.p;
+    P.obs_slot = h->d_obs_slot.p; P.tile_kf = h->d_tile_kf.p; P.tile_lmk = h->d_tile_lmk.p; P.tile_row = h->d_tile_row.p;
     P.pre_lane = h->pre_ok ? (const int4*)h->d_pre_lane.p : nullptr; P.pre_kf = h->pre_ok ? (const int2*)h->d_pre_kf.p : nullptr;
     P.ptab = h->d_ptab.p; P.ptab_stride = (long long)POSE_TAB * h->n_kf_tot;
     P.priors = h->d_priors.p; P.prior_lin = h->d_prior_lin.p; P.prior_lin_stride = (long long)h->priors.size() * PRIOR_LIN; P.n_prior_tot = (int)h->priors.size();
@@ -714,7 +716,7 @@ int upload_priors(sadvio_ba_handle* h) {
     HIP_TRY(h->up.flush(h->stream));  // one staged copy + scatter for everything queued since the layout build began
     if (h->pre_ok && h->pre_dirty) {
         hipLaunchKernelGGL(k_pre_packets, dim3((unsigned)h->tiles.size()), dim3(BUILD_THREADS), 0, h->stream, h->d_tiles.p, h->d_lmk_ob.p, h->d_lmk_oe.p, h->d_tile_kf.p,
-                           h->d_kf_fidx.p, (int4*)h->d_pre_lane.p, (int2*)h->d_pre_kf.p);
+                           h->d_tile_lmk.p, h->d_kf_fidx.p, (int4*)h->d_pre_lane.p, (int2*)h->d_pre_kf.p);
         h->pre_dirty = false;
     }
     return SADVIO_OK;
@@ -795,7 +797,7 @@ void sadvio_ba_destroy(sadvio_ba_handle* h) {
     h->d_lmk_ob.release(); h->d_lmk_oe.release(); h->d_obs_kf.release(); h->d_obs_cam.release();
     h->d_obs_meas.release(); h->d_priors.release(); h->d_prior_lin.release(); h->d_S.release(); h->d_rank_s.release(); h->d_gred.release(); h->d_gfull.release();
     h->d_hdiag.release(); h->d_delta.release(); h->d_s_pose.release(); h->d_states.release(); h->d_trace.release(); h->d_tstart.release(); h->d_acc.release();
-    h->d_probe.release(); h->d_tile_kf.release(); h->d_tile_row.release(); h->d_obs_slot.release(); h->d_ptab.release(); h->d_tacc.release(); h->d_dbg.release(); h->d_imus.release(); h->d_imu_scratch.release();
+    h->d_probe.release(); h->d_tile_kf.release(); h->d_tile_row.release(); h->d_tile_lmk.release(); h->d_obs_slot.release(); h->d_ptab.release(); h->d_tacc.release(); h->d_dbg.release(); h->d_imus.release(); h->d_imu_scratch.release();
     delete h;
 }
 
@@ -940,7 +942,7 @@ static int build_layout(sadvio_ba_handle* h) {
     auto& kf_T0 = ls.kf_T0; auto& kf_vel = ls.kf_vel; auto& kf_ba = ls.kf_ba; auto& kf_bg = ls.kf_bg; auto& kf_fidx = ls.kf_fidx;
     auto& cam_K = ls.cam_K; auto& cam_T = ls.cam_T; auto& cam_isig = ls.cam_isig; auto& lmk_p = ls.lmk_p; auto& lmk_const = ls.lmk_const;
     auto& lmk_ob = ls.lmk_ob; auto& lmk_oe = ls.lmk_oe; auto& obs_kf = ls.obs_kf; auto& obs_cam = ls.obs_cam; auto& obs_meas = ls.obs_meas;
-    auto& tile_kf = ls.tile_kf; auto& tile_row = ls.tile_row; auto& obs_slot = ls.obs_slot;
+    auto& tile_kf = ls.tile_kf; auto& tile_row = ls.tile_row; auto& tile_lmk = ls.tile_lmk; auto& obs_slot = ls.obs_slot;
     kf_T0.resize(12 * (size_t)kf_b); kf_vel.assign(3 * (size_t)kf_b, 0.0); kf_ba.assign(3 * (size_t)kf_b, 0.0); kf_bg.assign(3 * (size_t)kf_b, 0.0);
     kf_fidx.resize(kf_b);
     cam_K.resize(4 * (size_t)cam_b); cam_T.resize(12 * (size_t)cam_b); cam_isig.resize(cam_b);
@@ -949,7 +951,7 @@ static int build_layout(sadvio_ba_handle* h) {
     lmk_ob.resize(std::max(lmk_b, 1)); lmk_oe.resize(std::max(lmk_b, 1)); obs_kf.resize(std::max(obs_b, 1)); obs_cam.resize(std::max(obs_b, 1));
     const int ms = h->factor_type == SADVIO_FACTOR_PIXEL ? 2 : 3;
     obs_meas.resize((size_t)ms * std::max(obs_b, 1));
-    tile_kf.clear(); tile_row.clear();
+    tile_kf.clear(); tile_row.clear(); tile_lmk.clear();
     obs_slot.assign(std::max(obs_b, 1), 0);
     h->obs_perm.assign(std::max(obs_b, 1), 0);
     h->max_tile_kf = 1; h->max_tile_free = 0; h->max_gemm_free = 0; h->gemm_run4 = false;
@@ -1065,13 +1067,29 @@ static int build_layout(sadvio_ba_handle* h) {
             if (h->env.tile_rounds > 0) tile_rounds = h->env.tile_rounds;
         }
         d.tile_begin = (int)h->tiles.size();
+        // Single-round tiles of the latency kernels are packed (tile_pack.h): a tile lists its landmarks, so that a few outlier tracks
+        // do not cut the runs around them. Multi-round tiles, sharded ranks and layouts that build the throughput path's chunk tables
+        // (consecutive landmarks throughout) keep the contiguous cut.
+        bool want_lm_w = lmk_b >= 65536;
+        if (h->env.lm >= 0) want_lm_w = h->env.lm != 0;
+        const bool packed = n_windows == 1 && tile_rounds == 1 && F.n_lmk > 0 && h->world == 1 && !h->coll_fn && !want_lm_w && !h->env.contig_tiles;
+        auto& order = ls.pack_order; auto& cut = ls.pack_cut;
+        if (packed) {
+            for (int l = 0; l < F.n_lmk; l++)
+                if (F.lmk_obs_ptr[l + 1] - F.lmk_obs_ptr[l] > MAX_LMK_OBS) { h->err = "set_windows: a landmark has more than 64 observations"; return SADVIO_E_INVALID_ARG; }
+            const TilePackIn in{F.n_lmk, F.n_kf, F.lmk_obs_ptr, pkf.data(), F.kf_const, run_max.data(), BUILD_WAVES * 64, MAX_TILE_KF, MAX_TILE_FREE_KF, MAX_GEMM_FREE_KF};
+            tile_pack(in, order, cut);
+        }
         {
-            int l = 0;
+            int l = 0;   // position in the window's landmark sequence: the landmark itself, or its place in order (packed)
+            size_t next_cut = 0;
+            auto lm_at = [&](int i) { return packed ? order[i] : i; };
             auto& mark = ls.mark; auto& add = ls.add; auto& kfs = ls.kfs; auto& slot_of = ls.slot_of;
             mark.assign(F.n_kf, -1); slot_of.assign(F.n_kf, -1);
             while (l < F.n_lmk || (int)h->tiles.size() == d.tile_begin) {
                 Tile t{};
-                t.w = w; t.lmk0 = d.lmk_base + l; t.kmax = 1; t.G = 8;
+                t.w = w; t.lmk0 = d.lmk_base + (l < F.n_lmk ? lm_at(l) : l); t.kmax = 1; t.G = 8;
+                t.lmk_off = packed ? (int)tile_lmk.size() : -1;
                 t.dpf = d.dpf;  // Np, red_off, S_off, ld: layout_reduced
                 t.cam_base = d.cam_base; t.n_cam = F.n_cam;
                 t.first_of_window = ((int)h->tiles.size() == d.tile_begin) ? 1 : 0;
@@ -1079,16 +1097,18 @@ static int build_layout(sadvio_ba_handle* h) {
                 int nfree = 0, tile_run_max = 0;
                 const int l_begin = l;
                 while (l < F.n_lmk) {
-                    const int k = F.lmk_obs_ptr[l + 1] - F.lmk_obs_ptr[l];
+                    const int gl = lm_at(l);
+                    if (packed && l == cut[next_cut]) break;
+                    const int k = F.lmk_obs_ptr[gl + 1] - F.lmk_obs_ptr[gl];
                     if (k > MAX_LMK_OBS) { h->err = "set_windows: a landmark has more than 64 observations"; return SADVIO_E_INVALID_ARG; }
                     int G = t.G;
                     while (G < k) G <<= 1;
                     const int cap = tile_rounds * BUILD_WAVES * (64 / G);  // landmarks per tile (tile_rounds rounds per wave)
-                    if (l - l_begin + 1 > cap && l > l_begin) break;
+                    if (!packed && l - l_begin + 1 > cap && l > l_begin) break;
                     // key-frames this landmark would add
                     add.clear();
                     int add_free = 0;
-                    for (int o = F.lmk_obs_ptr[l]; o < F.lmk_obs_ptr[l + 1]; o++) {
+                    for (int o = F.lmk_obs_ptr[gl]; o < F.lmk_obs_ptr[gl + 1]; o++) {
                         const int kf = pkf[o];
                         if (mark[kf] != (int)h->tiles.size()) {
                             mark[kf] = (int)h->tiles.size();
@@ -1099,7 +1119,7 @@ static int build_layout(sadvio_ba_handle* h) {
                     const bool fits_hard = (int)(kfs.size() + add.size()) <= MAX_TILE_KF && nfree + add_free <= MAX_TILE_FREE_KF;
                     // soft limit: keep tiles on the MFMA path (<= MAX_GEMM_FREE_KF free key-frames) whenever a cut achieves it
                     const bool fits = fits_hard && (nfree + add_free <= MAX_GEMM_FREE_KF || l == l_begin);
-                    if (!fits && l > l_begin) {
+                    if (!packed && !fits && l > l_begin) {
                         for (int kf : add) mark[kf] = -1;  // roll back
                         break;
                     }
@@ -1107,11 +1127,14 @@ static int build_layout(sadvio_ba_handle* h) {
                     nfree += add_free;
                     t.G = G;
                     t.kmax = std::max(t.kmax, k);
-                    tile_run_max = std::max(tile_run_max, run_max[l]);
+                    tile_run_max = std::max(tile_run_max, run_max[gl]);
+                    if (packed) tile_lmk.push_back(d.lmk_base + gl);
                     l++;
-                    if (!fits_hard) break;  // a single landmark exceeding the capacity: global-atomics tile
+                    if (!packed && !fits_hard) break;  // a single landmark exceeding the capacity: global-atomics tile
                 }
-                t.lmk1 = d.lmk_base + l;
+                if (packed) next_cut++;
+                t.n_lmk = l - l_begin;
+                t.lmk1 = t.lmk0 + t.n_lmk;   // (a packed tile: the count only; its landmarks are tile_lmk's)
                 std::sort(kfs.begin(), kfs.end());
                 t.lds_mode = ((int)kfs.size() <= MAX_TILE_KF && nfree <= MAX_TILE_FREE_KF) ? ((nfree <= MAX_GEMM_FREE_KF && tile_run_max <= (has_asrc ? 4 : 2) && t.G == 8) ? 2 : 1) : 0;
                 if (t.lds_mode == 2 && tile_run_max > 2) h->gemm_run4 = true;   // needs the RARE variant of k_build (pseudo-observations: it is taken)
@@ -1128,8 +1151,8 @@ static int build_layout(sadvio_ba_handle* h) {
                     else if (t.lds_mode) tile_row.push_back(6 * rank++);
                     else tile_row.push_back(6 * kf_fidx[d.kf_base + kf]);  // global mode: 6 * free index of the window
                 }
-                for (int ll = l_begin; ll < l; ll++)
-                    for (int o = F.lmk_obs_ptr[ll]; o < F.lmk_obs_ptr[ll + 1]; o++)
+                for (int li = l_begin; li < l; li++)
+                    for (int o = F.lmk_obs_ptr[lm_at(li)]; o < F.lmk_obs_ptr[lm_at(li) + 1]; o++)
                         obs_slot[d.obs_base + o] = (unsigned char)slot_of[pkf[o]];
                 h->max_tile_kf = std::max(h->max_tile_kf, t.n_kf);
                 h->max_tile_free = std::max(h->max_tile_free, t.n_free);
@@ -1230,7 +1253,8 @@ static int build_layout(sadvio_ba_handle* h) {
     }
     HIP_TRY(h->d_win.alloc(n_windows)); HIP_TRY(h->d_tacc.alloc(2 * h->tiles.size()));
     if (tile_kf.empty()) { tile_kf.push_back(0); tile_row.push_back(-1); }
-    HIP_TRY(h->d_tile_kf.alloc(tile_kf.size())); HIP_TRY(h->d_tile_row.alloc(tile_row.size()));
+    if (tile_lmk.empty()) tile_lmk.push_back(0);
+    HIP_TRY(h->d_tile_kf.alloc(tile_kf.size())); HIP_TRY(h->d_tile_row.alloc(tile_row.size())); HIP_TRY(h->d_tile_lmk.alloc(tile_lmk.size()));
     HIP_TRY(h->d_obs_slot.alloc(obs_slot.size())); HIP_TRY(h->d_ptab.alloc(2 * (size_t)POSE_TAB * kf_b));
     HIP_TRY(h->d_kf_T0.alloc(kf_T0.size())); HIP_TRY(h->d_kf_fidx.alloc(kf_fidx.size()));
     HIP_TRY(h->d_xp.alloc(2 * 6 * (size_t)kf_b)); HIP_TRY(h->d_xv.alloc(2 * 3 * (size_t)kf_b));
@@ -1246,7 +1270,7 @@ static int build_layout(sadvio_ba_handle* h) {
     UP(h->d_kf_ba, kf_ba); UP(h->d_kf_bg, kf_bg); UP(h->d_cam_K, cam_K); UP(h->d_cam_T, cam_T); UP(h->d_cam_isig, cam_isig);
     if (lmk_b) { UP(h->d_lmk_p, lmk_p); }
     UP(h->d_lmk_ob, lmk_ob); UP(h->d_lmk_oe, lmk_oe); UP(h->d_obs_kf, obs_kf);
-    UP(h->d_obs_cam, obs_cam); UP(h->d_obs_meas, obs_meas); UP(h->d_tile_kf, tile_kf); UP(h->d_tile_row, tile_row); UP(h->d_obs_slot, obs_slot);
+    UP(h->d_obs_cam, obs_cam); UP(h->d_obs_meas, obs_meas); UP(h->d_tile_kf, tile_kf); UP(h->d_tile_row, tile_row); UP(h->d_tile_lmk, tile_lmk); UP(h->d_obs_slot, obs_slot);
     // First-round packets (round 6): what a lane of k_build / k_backsub needs to address the inputs of its tile's FIRST landmark round,
     // laid out by (tile, lane) so that the loads hang on blockIdx alone: | landmark | observation (-1: none) | observations of the
     // landmark + valid flag | first observation of the landmark |, and per tile the first PRE_KF key-frames of its list with their free
@@ -1684,7 +1708,7 @@ int run_jacobi_rows(sadvio_ba_handle* h, double* G, int r, int n, int* flag) {
     const double jtol = h->env.jacobi_tol;   // |g_p . g_q| <= jtol |g_p| |g_q| ends a pair
     int sweeps = 0;
     long long* jts = nullptr;   // phase timestamps of one launch (SADVIO_KERNEL_TS builds, SADVIO_DEBUG & 4096)
-    if ((h->env.debug & 4096) && n > 500 && h->d_dbg.alloc(128) == hipSuccess) jts = h->d_dbg.p + 44;
+    if ((h->env.debug & 4096) && n > 500 && h->d_dbg.alloc(DBG_SLOTS) == hipSuccess) jts = h->d_dbg.p + 44;
     for (; sweeps < 40 && nbpad >= 2; sweeps++) {
         if (hipMemsetAsync(flag, 0, sizeof(int), h->stream) != hipSuccess) return -1;
         for (int st = 0; st < nbpad - 1; st++) {
@@ -2914,7 +2938,7 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
     // iteration 0, so at least one slot is always run and the final decision is taken by k_final.
     const int slots = std::max(1, o.max_num_iterations);
     const int stride = slots + 2;
-    HIP_TRY(h->d_dbg.alloc(128));
+    HIP_TRY(h->d_dbg.alloc(DBG_SLOTS));
     HIP_TRY(h->d_states.alloc((size_t)n_win * stride));
     HIP_TRY(h->d_trace.alloc((size_t)n_win * stride * 8));
     HIP_TRY(h->d_tstart.alloc(1));
@@ -3174,7 +3198,7 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
         memcpy(kp, &P, sizeof(DevPtrs)); kp += sizeof(DevPtrs);
         // launch-shape switches read from the environment inside enqueue() are part of the key too: a handle that already captured a
         // graph must not replay it when an A/B switch changes
-        const int env_bits = (int)with_imu + 2 * (int)h->env.no_fork + 32 * (int)h->env.no_bcr + 128 * (int)h->env.no_lpt;
+        const int env_bits = (int)with_imu + 2 * (int)h->env.no_fork + 32 * (int)h->env.no_bcr + 128 * (int)h->env.no_lpt + 256 * (int)h->env.contig_tiles;
         const int ints[8] = {slots, n_tiles, n_win, mtk, strip_doubles, Rp, h->n_kf_tot, h->factor_type + 2 * (int)extras + 4 * (int)rare + 8 * (int)use_lm + 16 * env_bits};  // P (incl. decide_kernel) is part of the key
         memcpy(kp, ints, sizeof(ints)); kp += sizeof(ints);
         const size_t szs[3] = {lds_build, lds_back, lds_solve};
@@ -3217,6 +3241,16 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
             for (int i = 45; i < 55; i++) fprintf(stderr, " %d:%.2f", i - 44, (ts[i] - ts[44]) * 0.01);
             fprintf(stderr, "\n");
         }
+#ifdef SADVIO_KERNEL_TS
+        // every workgroup of one k_build launch: start / end relative to workgroup 0's start, and the CU it ran on
+        std::vector<long long> wg(4 * (size_t)std::min(n_tiles, DBG_WG_MAX));
+        if (!wg.empty() && hipMemcpy(wg.data(), h->d_dbg.p + DBG_WG_BASE, wg.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess)
+            for (size_t b = 0; b < wg.size() / 4; b++) {
+                const unsigned hw = (unsigned)wg[4 * b + 2];
+                fprintf(stderr, "[sadvio dbg] k_build wg %zu start %.2f end %.2f xcc %d se %u sh %u cu %u simd %u\n", b, (wg[4 * b] - wg[0]) * 0.01, (wg[4 * b + 1] - wg[0]) * 0.01,
+                        (int)((wg[4 * b + 2] >> 32) & 15), (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 15, (hw >> 4) & 3);
+            }
+#endif
     }
     h->fin.assign(h->h_final, h->h_final + n_win);
     h->deltas_cached = false;

@@ -51,14 +51,16 @@ struct WinDev {
     int lobs_begin, lobs_end;  // slice of their observations
 };
 
-// One workgroup of k_build / k_backsub: a run of consecutive landmarks of one window. Each landmark is
+// One workgroup of k_build / k_backsub: a run of consecutive landmarks of one window, or (single-round tiles, tile_pack.h) a list of them. Each landmark is
 // processed by a group of G consecutive lanes of one wave (lane q of the group owns the landmark's q-th
 // observation), so per-landmark reductions are lane shuffles. The key-frames the tile touches are listed
 // (sorted by global index) in tile_kf[kf_off .. kf_off + n_kf); obs_slot[o] indexes that list. The free
 // ones among them span the tile's private LDS copy of the reduced system (6 rows each).
 struct Tile {
     int w;
-    int lmk0, lmk1;   // global landmark range
+    int lmk0, lmk1;   // global landmark range of a tile of consecutive landmarks (lmk_off < 0)
+    int lmk_off;      // >= 0: the tile's landmarks are listed in tile_lmk[lmk_off .. lmk_off + n_lmk) (packed single-round tiles)
+    int n_lmk;        // landmarks of the tile, either way
     int G;            // lanes per landmark: power of two, 8 .. 64
     int kf_off, n_kf; // slice of tile_kf / tile_row
     int n_free;       // free key-frames in the slice: LDS tile dimension = 6 * n_free

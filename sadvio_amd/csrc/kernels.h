@@ -34,6 +34,7 @@ struct DevPtrs {
     const int* obs_kf; const int* obs_cam; const double* obs_meas;
     const unsigned char* obs_slot;  // index of the observation's key-frame in its tile's list
     const int* tile_kf;             // per-tile key-frame lists (global indices)
+    const int* tile_lmk;            // landmark lists of the packed tiles (Tile::lmk_off)
     const int* tile_row;            // matching row in the tile's LDS system (6 * rank among free) or -1
     // first-round packets (k_pre_packets; null for submissions of more than PRE_MAX_TILES tiles): per (tile, 8 consecutive lanes — a landmark's
     // lane group is 8 .. 64 wide) | landmark | its first observation | its observation count + (1 << 16 if the landmark exists) | position of the
@@ -95,7 +96,7 @@ struct DevPtrs {
     int n_win;
     long long* t_start; // wall_clock64 at the first kernel of the solve (k_reset)
     double* trace;      // [n_win][state_stride][8] per-iteration log (sadvio_ba_get_trace), written by the slot's single decider
-    long long* dbg_ts;  // [128] phase timestamps (wall_clock64, 100 MHz) of workgroup 0 when debug & 4096
+    long long* dbg_ts;  // [DBG_SLOTS] phase timestamps (wall_clock64, 100 MHz) of workgroup 0 when debug & 4096
     int debug;  // SADVIO_DEBUG env: bit 12 (4096) = in-kernel phase timestamps of workgroup 0 into dbg_ts (results unaffected)
     SolveOpts o;
 };
@@ -105,9 +106,17 @@ struct DevPtrs {
 #ifdef SADVIO_KERNEL_TS
 #define SADVIO_TS(slot_, idx_) do { if ((P.debug & 4096) && blockIdx.x == 0 && threadIdx.x == 0 && slot == (slot_)) P.dbg_ts[idx_] = wall_clock64(); } while (0)
 #define SADVIO_TS_PTR(cond_) ((cond_) ? P.dbg_ts : nullptr)
+// Per-workgroup record of one k_build launch (slot 3): | start | end | XCC id << 32 | HW_ID (gfx9 layout: SIMD 5:4, CU 11:8, SH 12,
+// SE 15:13) | - | behind the 128 phase slots. Shows which workgroups share a CU and when each of them ends (scripts/gpu_time_tiles.py).
+constexpr int DBG_WG_MAX = 1024, DBG_WG_BASE = 128, DBG_SLOTS = DBG_WG_BASE + 4 * DBG_WG_MAX;
+#define SADVIO_WG_TS(slot_, which_) do { if ((P.debug & 4096) && blockIdx.x < DBG_WG_MAX && threadIdx.x == 0 && slot == (slot_)) { \
+        P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + (which_)] = wall_clock64(); \
+        if ((which_) == 0) P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + 2] = ((long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)); } } while (0)
 #else
 #define SADVIO_TS(slot_, idx_) do { } while (0)
 #define SADVIO_TS_PTR(cond_) nullptr
+#define SADVIO_WG_TS(slot_, which_) do { } while (0)
+constexpr int DBG_SLOTS = 128;
 #endif
 
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // i >= j
@@ -493,19 +502,22 @@ __host__ __device__ inline size_t tile_tables_bytes(int n_kf) {
     return (b + 15) & ~(size_t)15;
 }
 
+// global landmark in slot i of a tile: listed (packed tiles) or consecutive
+__device__ __forceinline__ int tile_landmark(const Tile& T, const int* __restrict__ tile_lmk, int i) { return T.lmk_off >= 0 ? tile_lmk[T.lmk_off + i] : T.lmk0 + i; }
+
 // First-round packets (DevPtrs::pre_lane / pre_kf): one launch per layout, behind its upload. What a lane of k_build / k_backsub needs
 // to address the inputs of its tile's FIRST landmark round, laid out by (tile, 8-lane granule) so that those loads hang on blockIdx alone
 // (132 KB for the 258 tiles of config 2; a packet per lane was 1 MB of extra traffic per launch).
 __global__ __launch_bounds__(BUILD_THREADS) void k_pre_packets(const Tile* __restrict__ tiles, const int* __restrict__ lmk_ob, const int* __restrict__ lmk_oe,
-                                                               const int* __restrict__ tile_kf, const int* __restrict__ kf_fidx, int4* __restrict__ pre_lane,
+                                                               const int* __restrict__ tile_kf, const int* __restrict__ tile_lmk, const int* __restrict__ kf_fidx, int4* __restrict__ pre_lane,
                                                                int2* __restrict__ pre_kf) {
     const Tile T = tiles[blockIdx.x];
     const int tid = threadIdx.x;
     if (tid < BUILD_THREADS / 8) {          // one packet per 8 lanes
         const int lane0 = tid * 8, wv = lane0 >> 6, ln = lane0 & 63;
-        const int G = T.G, lpw = 64 / G, grp = ln / G, q0 = ln - grp * G, nl = T.lmk1 - T.lmk0;
+        const int G = T.G, lpw = 64 / G, grp = ln / G, q0 = ln - grp * G, nl = T.n_lmk;
         const bool valid = wv * lpw + grp < nl;
-        const int gl = T.lmk0 + (valid ? wv * lpw + grp : 0);
+        const int gl = nl > 0 ? tile_landmark(T, tile_lmk, valid ? wv * lpw + grp : 0) : T.lmk0;
         const int ob = nl > 0 ? lmk_ob[gl] : 0, nobs = (valid && nl > 0) ? lmk_oe[gl] - ob : 0;
         pre_lane[(long long)blockIdx.x * (BUILD_THREADS / 8) + tid] = make_int4(gl, ob, nobs | (valid ? 1 << 16 : 0), q0);
     }
@@ -537,6 +549,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         pk = P.pre_kf[(long long)blockIdx.x * PRE_KF + tid / POSE_TAB];     // tid / POSE_TAB <= 6 < PRE_KF
     }
     SADVIO_TS(3, 32);
+    SADVIO_WG_TS(3, 0);
     __shared__ double s_part[BUILD_WAVES * 4];
     // LDS carve
     double* poseTab = (double*)smem;
@@ -545,7 +558,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
     double* stage = (double*)(smem + tile_tables_bytes(max_tile_kf));  // [BUILD_WAVES][strip_doubles] wave-private strips
     const int G = T.G, lpw = 64 / G;
     const int grp = ln / G, q = ln - grp * G;
-    const int nl = T.lmk1 - T.lmk0;
+    const int nl = T.n_lmk;
     // ---- everything that does not depend on the LM decision of the previous slot is fetched BEFORE that decision is summed:
     //      the wave's first landmark round (CSR range, position, BOTH delta buffers, the lane's observation) and the pose
     //      tables of BOTH buffers (first POSE_TAB-chunk per thread); the decision then only selects. A single window spends
@@ -597,7 +610,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         pre_o = (pl.w + (tid & 7) < (pl.z & 0xff)) ? pl.y + pl.w + (tid & 7) : -1;
     } else {
         first_valid = wv * lpw + grp < nl;
-        gl_first = T.lmk0 + (first_valid ? wv * lpw + grp : 0);
+        gl_first = tile_landmark(T, P.tile_lmk, first_valid ? wv * lpw + grp : 0);
         pre_ob = P.lmk_ob[gl_first]; pre_oe = P.lmk_oe[gl_first];
         pre_o = (first_valid && q < pre_oe - pre_ob) ? pre_ob + q : -1;
     }
@@ -681,8 +694,8 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
     for (int base = wv * lpw; base < nl; base += BUILD_WAVES * lpw) {
         const int lm = base + grp;
         const bool lmk_valid = lm < nl;
-        const int gl = T.lmk0 + (lmk_valid ? lm : 0);
         const bool first = base == wv * lpw;          // this round was fetched at the top of the kernel
+        const int gl = first ? gl_first : tile_landmark(T, P.tile_lmk, lmk_valid ? lm : 0);
         const int ob = first ? pre_ob : P.lmk_ob[gl], oe = first ? pre_oe : P.lmk_oe[gl];
         const int nobs = lmk_valid ? oe - ob : 0;
         // 0 free (eliminated here), 1 constant, 2 kept in the reduced system by a dense prior: its pose-pose part
@@ -972,6 +985,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         }
     }
     SADVIO_TS(3, 42);
+    SADVIO_WG_TS(3, 1);
 }
 
 // Blocked right-looking Cholesky of the packed lower-triangular matrix P ((N+1) rows: row N is the
@@ -2037,7 +2051,7 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, 
     double* dpTab = candTab + (size_t)max_tile_kf * 12;                  // [n_kf][6] pose step of each listed key-frame
     const int G = T.G, lpw = 64 / G;
     const int grp = ln / G, q = ln - grp * G;
-    const int nl = T.lmk1 - T.lmk0;
+    const int nl = T.n_lmk;
     // the wave's first landmark round is fetched before the tables are staged - and, with the packets, before the state record says
     // which delta buffer holds x (both are fetched, the record selects)
     bool first_valid;
@@ -2047,7 +2061,7 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, 
         pre_o = (pl.w + (tid & 7) < (pl.z & 0xff)) ? pl.y + pl.w + (tid & 7) : -1;
     } else {
         first_valid = wv * lpw + grp < nl;
-        gl_first = T.lmk0 + (first_valid ? wv * lpw + grp : 0);
+        gl_first = tile_landmark(T, P.tile_lmk, first_valid ? wv * lpw + grp : 0);
         pre_ob = P.lmk_ob[gl_first]; pre_oe = P.lmk_oe[gl_first];
         pre_o = (first_valid && q < pre_oe - pre_ob) ? pre_ob + q : -1;
     }
@@ -2127,8 +2141,8 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, 
     for (int base = wv * lpw; base < nl; base += BUILD_WAVES * lpw) {
         const int lm = base + grp;
         const bool lmk_valid = lm < nl;
-        const int gl = T.lmk0 + (lmk_valid ? lm : 0);
         const bool first = base == wv * lpw;
+        const int gl = first ? gl_first : tile_landmark(T, P.tile_lmk, lmk_valid ? lm : 0);
         const int ob = first ? pre_ob : P.lmk_ob[gl], oe = first ? pre_oe : P.lmk_oe[gl];
         const int nobs = lmk_valid ? oe - ob : 0;
         const int lcode = first ? pre_lcode : (P.lmk_const ? P.lmk_const[gl] : 0);
