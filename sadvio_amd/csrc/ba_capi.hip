@@ -5,467 +5,10 @@
 // once (set_windows), the whole LM solve is enqueued on the handle's stream without host round
 // trips, and deltas are read back for the adapter to apply (AOptimizer.cpp:329-340).
 // There is no CPU fallback: without a gfx950 device every compute call fails.
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../../include/sadvio_ba.h"
-#include "kernels.h"
-#include "tile_pack.h"
-#include "dense_chol.h"
-#include "marg_kernels.h"
-#include "lm_kernels.h"
-#include "viinit_kernels.h"
-#include "nofov_kernels.h"
-
-using namespace sadvio;
+#include "ba_handle.h"
+#include "solve_driver.h"
 
 namespace {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            h->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
-            return SADVIO_E_HIP;                                                              \
-        }                                                                                     \
-    } while (0)
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count) {
-        if (count <= n && p && !view) return hipSuccess;
-        if (p && !view) (void)hipFree(p);
-        view = false;
-        p = nullptr; n = 0;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    bool view = false;  // non-owning window into another buffer
-    void set_view(T* ptr, size_t count) { if (p && !view) (void)hipFree(p); p = ptr; n = count; view = true; }
-    void release() { if (p && !view) (void)hipFree(p); p = nullptr; n = 0; view = false; }
-    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(view, o.view); }
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-};
-
-struct KernelClass {
-    const char* name;
-    double total_ms = 0;
-    long long launches = 0;
-};
-
-struct HostWin {
-    WinDev d;
-    std::vector<int64_t> kf_id, lmk_id;
-    int hb_lmk = 0;  // max distance (in free key-frame index) between two key-frames observing one landmark
-};
-
-}  // namespace
-
-// RCCL (all-reduce of the reduced system over xGMI), loaded on first use: single-GPU solves never touch it.
-struct NcclId { char internal[128]; };
-struct RcclLib {
-    void* lib = nullptr;
-    void* comm = nullptr;
-    int (*get_id)(NcclId*) = nullptr;
-    int (*init_rank)(void**, int, NcclId, int) = nullptr;
-    int (*all_reduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*destroy)(void*) = nullptr;
-    const char* (*err_string)(int) = nullptr;
-    int (*comm_count)(void*, int*) = nullptr;
-    int (*comm_user_rank)(void*, int*) = nullptr;
-    int (*comm_cu_device)(void*, int*) = nullptr;
-};
-
-// Deep copy of a caller's window (set_windows) + the observation arrays actually tiled: pose-to-landmark NFR factors
-// whose landmark can be eliminated are appended to the landmark's observation list as two pseudo-observations
-// (rows 0-1 and row 2 of the 3-row factor), so that they ride the ordinary Schur elimination.
-struct SrcWin {
-    sadvio_flat_window v{};   // view into the vectors below
-    std::vector<int64_t> kf_id, lmk_id;
-    std::vector<double> kf_T, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_sigma, lmk_p, obs_meas;
-    std::vector<uint8_t> kf_const, lmk_const;
-    std::vector<int32_t> lmk_obs_ptr, obs_kf, obs_cam;
-    // augmented observation list (what build_layout tiles) and its map to the caller's observation index (-1 = pseudo)
-    std::vector<int32_t> a_ptr, a_kf, a_cam, a_src;
-    std::vector<double> a_meas;
-    // cameras with identical (K, T_s_f, sigma) are stored once: SaDVIO has one ImageSensor object per (frame, camera),
-    // i.e. 2 x N_kf table entries that are all copies of the rig's two cameras
-    std::vector<double> u_cam_K, u_cam_T, u_cam_sigma;
-    std::vector<int32_t> u_obs_cam;
-    std::vector<int> cam_map;   // caller's camera index -> stored camera index
-};
-
-// Host -> device uploads of one layout build are packed into ONE pinned staging buffer, copied with one
-// hipMemcpyAsync and scattered to their destinations by one kernel: ~25 small pageable copies cost ~15 us each.
-struct UploadItem { unsigned long long dst; unsigned long long off; unsigned long long bytes; };
-__global__ void k_scatter_uploads(const char* stage, const UploadItem* items, int n_items) {
-    for (int it = blockIdx.y; it < n_items; it += gridDim.y) {
-        const UploadItem u = items[it];
-        char* dst = (char*)u.dst;
-        const char* src = stage + u.off;
-        const unsigned long long words = u.bytes >> 3;  // staging offsets and device allocations are 8-byte aligned
-        for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (unsigned long long)gridDim.x * blockDim.x)
-            ((unsigned long long*)dst)[i] = ((const unsigned long long*)src)[i];
-        if (blockIdx.x == 0 && threadIdx.x < (u.bytes & 7)) dst[(words << 3) + threadIdx.x] = src[(words << 3) + threadIdx.x];
-    }
-}
-struct UploadBatch {
-    std::vector<UploadItem> items;
-    char* pinned = nullptr; size_t pinned_cap = 0, used = 0;   // sources are packed straight into pinned memory
-    char* dev = nullptr; size_t dev_cap = 0;
-    bool failed = false;
-    // flush() does not wait: the staged copy + scatter are stream work like the kernels that read their output. The pinned buffer is
-    // only touched again (next add / grow) after the event recorded behind the copy has fired — by then it normally has
-    hipEvent_t ev = nullptr;
-    bool in_flight = false;
-    void wait() { if (in_flight) { (void)hipEventSynchronize(ev); in_flight = false; } }
-    void reset() { wait(); items.clear(); used = 0; failed = false; }   // drop what an earlier, failed layout build left queued
-    void reserve(size_t bytes) {
-        if (bytes <= pinned_cap) return;
-        wait();
-        char* np = nullptr;
-        const size_t cap = bytes + bytes / 2 + 4096;
-        if (hipHostMalloc((void**)&np, cap, hipHostMallocDefault) != hipSuccess) { failed = true; return; }
-        if (pinned) { memcpy(np, pinned, used); (void)hipHostFree(pinned); }
-        pinned = np; pinned_cap = cap;
-    }
-    void add(void* dst, const void* src, size_t bytes) {
-        if (!bytes) return;
-        wait();
-        const size_t off = (used + 7) & ~(size_t)7;
-        reserve(off + bytes);
-        if (failed) return;
-        memcpy(pinned + off, src, bytes);
-        used = off + bytes;
-        items.push_back({(unsigned long long)dst, (unsigned long long)off, (unsigned long long)bytes});
-    }
-    hipError_t flush(hipStream_t stream) {
-        if (failed) { failed = false; items.clear(); used = 0; return hipErrorOutOfMemory; }
-        if (items.empty()) return hipSuccess;
-        const size_t data_bytes = (used + 7) & ~(size_t)7;
-        const size_t total = data_bytes + items.size() * sizeof(UploadItem);
-        reserve(total);
-        if (failed) { failed = false; items.clear(); used = 0; return hipErrorOutOfMemory; }
-        hipError_t e = hipSuccess;
-        // every error return drops the queue: callers that do not reset() afterwards (marginalize, sparsify) must not re-send it
-        auto drop = [&](hipError_t err) { items.clear(); used = 0; return err; };
-        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return drop(e);
-        if (dev_cap < total) {
-            if (dev) { (void)hipStreamSynchronize(stream); (void)hipFree(dev); }   // an earlier scatter may still read it
-            dev = nullptr; dev_cap = 0;
-            if ((e = hipMalloc((void**)&dev, total + total / 2)) != hipSuccess) return drop(e);
-            dev_cap = total + total / 2;
-        }
-        memcpy(pinned + data_bytes, items.data(), items.size() * sizeof(UploadItem));
-        if ((e = hipMemcpyAsync(dev, pinned, total, hipMemcpyHostToDevice, stream)) != hipSuccess) return drop(e);
-        hipLaunchKernelGGL(k_scatter_uploads, dim3(64, (unsigned)std::min<size_t>(items.size(), 64)), dim3(256), 0, stream, dev, (const UploadItem*)(dev + data_bytes), (int)items.size());
-        e = hipEventRecord(ev, stream);
-        in_flight = e == hipSuccess;
-        if (!in_flight) e = hipStreamSynchronize(stream);
-        items.clear(); used = 0;
-        return e;
-    }
-    ~UploadBatch() { wait(); if (ev) (void)hipEventDestroy(ev); if (pinned) (void)hipHostFree(pinned); if (dev) (void)hipFree(dev); }
-};
-
-struct DensePriorHost {
-    int n_full = 0, n = 0, kf_keep = -1, kf_col = 0;
-    bool resident = false;      // J, r0 = the handle's prior (PriorState), copied device to device
-    unsigned long long serial = 0;   // ... as it was when set_dense_prior named it
-    std::vector<double> J, r0;
-    std::vector<int> lmk_index, lmk_col;
-};
-
-// The handle's marginalisation prior: what the reference keeps in `_marginalization_last` inside the optimizer between
-// marginalize() and the next window solve / the next marginalize() (AOptimizer.h:88-90, …Analytic.cpp:627-660). Device
-// resident; the variables its columns refer to are named by the caller per window (it owns the id bookkeeping).
-struct PriorState {
-    bool valid = false;
-    int n_full = 0, n = 0, form = 0, cut_mode = 0;   // cut_mode: the SADVIO_EIG_CUT_* it was built with (sparsify applies the same cut)
-    DevBuf<double> J, r0;        // n_full x n row-major packed, n_full
-    DevBuf<double> Z;            // n_full x n with Z^T Z = Sigma_k (built by the first sparsify of this prior)
-    bool z_valid = false;
-    DevBuf<int> step_of;         // Cholesky form: pivot step of every column
-    DevBuf<double> H, g;         // J^T J = Ak and -J^T r0 = bk as the marginalisation that built the prior had them (full-rank Cholesky form only):
-    bool hg_valid = false;       // the next marginalize / the next window's dense prior take them instead of re-forming J^T J (n^3 flops)
-    unsigned long long serial = 0;   // bumped whenever the prior changes: a window that attached it checks it is still the same one
-};
-
-// Work buffers of marginalize / sparsify, kept in the handle: both run once per key-frame, and ~20 hipMalloc / hipFree pairs
-// per call cost more than the kernels between them.
-struct TriLevel { int first, count, max_m, max_n; };
-struct MargScratch {
-    DevBuf<double> A, b, G, V, ev, Vs, Ainv, T, Ak, bk, newJ, newr, lastJ, lastr, L, Tb, Zt, S, mi, jsel, lam, wtmp, Hl;
-    DevBuf<int> ditems, flag, sel, lastcol, piv_of, lc, piv_mm;
-    DevBuf<MargSmall> small;
-    DevBuf<NfrSpecC> spec;
-    std::vector<int> lcol, items, items_l, col;
-    std::vector<double> hev, hS;
-    struct TriPlan { DevBuf<TriNode> nodes; std::vector<TriLevel> levels; int leaves = 0; };
-    std::map<int, TriPlan> tri_plans;   // node tables of the triangular inverse, by padded size (m of Amm and n of the prior alternate)
-};
-
-struct LineSetHost {   // deep copy of a sadvio_line_set
-    std::vector<int64_t> id;
-    std::vector<double> T, model, meas;
-    std::vector<unsigned char> is_const;
-    std::vector<int> ptr, obs_kf, obs_cam;
-    int n() const { return (int)id.size(); }
-};
-
-// Host-side work arrays of build_layout, kept between calls: a sliding-window back end calls set_windows once per key-frame,
-// and ~2 MB of fresh std::vectors per call are ~500 page faults (more than the layout arithmetic itself).
-struct LayoutScratch {
-    std::vector<double> kf_T0, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_isig, lmk_p, obs_meas;
-    std::vector<int> kf_fidx, lmk_ob, lmk_oe, obs_kf, obs_cam, tile_kf, tile_row, tile_lmk, pack_order, pack_cut, pkf, pcam, run_max, idx, mark, add, kfs, slot_of, chunk_ob, chunk_lm, perm;
-    std::vector<unsigned char> lmk_const, obs_slot, obs_lslot;
-    std::vector<char> held;
-};
-
-// The diagnostic switches of DESIGN.md 4 (environment), read ONCE when the handle is created: none is needed in production, and none is
-// looked up again on a per-key-frame path (round 4 called getenv 39 times across set_windows / marginalize / solve).
-struct EnvCfg {
-    int debug = 0;
-    int lm = -1, pf_wg = -1;            // -1: not set
-    int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
-    double jacobi_tol = 1e-14;
-    bool marg_last_small = false, marg_eig_mm = false, marg_pivoted = false, marg_unpivoted = false, pchol_swap = false, pchol_strict = false,
-         jacobi_b4 = false, jacobi_plain = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false;
-    void read() {
-        auto on = [](const char* k) { return getenv(k) != nullptr; };
-        auto num = [](const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; };
-        debug = num("SADVIO_DEBUG", 0); lm = num("SADVIO_LM", -1); pf_wg = num("SADVIO_PF_WG", -1);
-        tile_rounds = num("SADVIO_TILE_ROUNDS", 0); lm_subs = num("SADVIO_LM_SUBS", 0); band_c = num("SADVIO_BAND_C", 0);
-        if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);
-        marg_last_small = on("SADVIO_MARG_LAST_SMALL"); marg_eig_mm = on("SADVIO_MARG_EIG_MM"); marg_pivoted = on("SADVIO_MARG_PIVOTED");
-        marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_swap = on("SADVIO_PCHOL_SWAP"); pchol_strict = on("SADVIO_PCHOL_STRICT");
-        jacobi_b4 = on("SADVIO_JACOBI_B4"); jacobi_plain = on("SADVIO_JACOBI_PLAIN"); no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
-        no_bcr = on("SADVIO_NO_BCR");
-        contig_tiles = on("SADVIO_CONTIG_TILES");   // A/B: single-round tiles as runs of consecutive landmarks (no packing, tile_pack.h)
-        imu_items = on("SADVIO_IMU_ITEMS");   // A/B: the IMU pairs' entries through k_solve's item loop (the pre-0.5 path) on one device too
-    }
-};
-
-struct sadvio_ba_handle {
-    EnvCfg env;
-    sadvio_ba_config cfg{};
-    LayoutScratch ls;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    // host mirrors
-    std::vector<HostWin> wins;
-    std::vector<Tile> tiles;
-    std::vector<PriorDev> priors;
-    std::vector<int> obs_perm;  // device observation position -> caller's observation index (within window)
-    std::vector<std::vector<PriorDev>> priors_per_win;
-    std::vector<std::vector<ImuDev>> imus_per_win;
-    std::vector<ImuDev> imus;
-    int n_kf_tot = 0, n_cam_tot = 0, n_lmk_tot = 0, n_obs_tot = 0, np_tot = 0;
-    long long s_tot = 0;
-    int factor_type = 0;
-    int max_n_kf = 0, max_npose = 0, max_np = 0, n_big = 0;
-    DevBuf<int> d_big_info;
-    DevBuf<double> d_big_M;     // inverse diagonal blocks of the wide-panel dense solver, 96 x 96 per 96 columns (+ the factors' tiles)
-    DevBuf<double> d_big_Lx;    // its out-of-place panels
-    DevBuf<double> d_big_linv;  // inverse pivot blocks of the banded solver, N * NB doubles per out-of-LDS window
-    DevBuf<double> d_coll_band; // band-packed copy of the reduced system for the sharded all-reduce
-    DevBuf<double> d_bcr;       // block-cyclic-reduction workspace of the long banded systems
-    DevBuf<double> d_big_mid;   // the two Schur complements on the middle block of the twisted banded factorisation
-    bool uploaded = false, solved = false;
-    bool defer = false, pending = false;   // begin_update .. commit_update: set_* calls only record, ONE layout build + staged upload at commit
-    UploadBatch up;   // pending host -> device uploads of the current layout build
-    // window sharded over several GPUs: collective hook (user callback or the built-in RCCL one)
-    int world = 1, rank = 0;
-    sadvio_allreduce_fn coll_fn = nullptr;
-    void* coll_ctx = nullptr;
-    RcclLib rccl;
-    long long red_total = 0;  // doubles in [S | gred | gfull | hdiag | rank_b], the buffer of the per-step all-reduce
-    DevBuf<double> d_rank_b, d_rank_s;
-    // dense marginalisation priors (host copies, one per window) and the layout they induce
-    std::vector<DensePriorHost> dprior_per_win;
-    PriorState prior;   // the handle's own prior (sadvio_ba_marginalize leaves it here)
-    MargScratch mg;
-    std::vector<SrcWin> src;                       // caller windows (deep copies)
-    std::vector<std::vector<char>> sp_elim;        // per window, per sparse factor: handled as pseudo-observations
-    std::vector<int> n_obs_user;                   // caller's observation count per window
-    std::vector<std::vector<sadvio_sparse_prior>> sparse_per_win;
-    std::vector<LineSetHost> lines_per_win;        // linexd landmarks
-    DevBuf<LineDev> d_lines;
-    DevBuf<LineObsDev> d_lobs;
-    DevBuf<double> d_xline, d_line_scratch;
-    int n_line_tot = 0, n_lobs_tot = 0;
-    DevBuf<SparseDev> d_sparse;
-    DevBuf<int> d_sp_list;
-    int n_sp_list = 0;   // sparse prior factors evaluated by sparse_factor_eval (all windows)
-    size_t n_sparse_tot = 0;
-    DevBuf<double> d_sp_scratch;
-    std::vector<unsigned char> h_lmk_const_user;  // as given by the caller
-    std::vector<int> h_lmk_ob, h_lmk_oe, h_kf_fidx, h_obs_kf;
-    bool user_lmk_const = false;
-    int n_kept = 0;
-    DevBuf<int> d_lmk_red, d_kept_obs, d_dp_ints;
-    DevBuf<double> d_dp_data;
-    int slots_cap = 0;
-    int last_slots = 0;
-    // device buffers
-    DevBuf<WinDev> d_win;
-    DevBuf<Tile> d_tiles;
-    DevBuf<double> d_kf_T0, d_xp, d_xv, d_xba, d_xbg, d_kf_vel, d_kf_ba, d_kf_bg;
-    DevBuf<int> d_kf_fidx;
-    DevBuf<double> d_cam_K, d_cam_T, d_cam_isig;
-    DevBuf<double> d_lmk_p, d_xl, d_s_lmk;
-    DevBuf<unsigned char> d_lmk_const;
-    DevBuf<int> d_lmk_ob, d_lmk_oe, d_obs_kf, d_obs_cam, d_tile_kf, d_tile_row, d_tile_lmk;
-    DevBuf<int> d_pre_lane, d_pre_kf;     // first-round packets of the latency kernels (kernels.h: DevPtrs::pre_lane), few-tile submissions only
-    bool pre_ok = false, pre_dirty = false;
-    DevBuf<int> d_rank_col; DevBuf<double> d_rank_x;       // refine_rank_by_eigenvalue (guarded calls only): pivot column per step, the solved vectors
-    DevBuf<unsigned char> d_obs_slot, d_obs_lslot;
-    DevBuf<int> d_chunk_ob, d_chunk_lm, d_tile_perm;   // chunk tables of the throughput kernels (lm_kernels.h)
-    DevBuf<int> d_jac_ints;               // pivoting / rank of the Cholesky-preconditioned Jacobi
-    DevBuf<double> d_jac_dbl;             // its remaining diagonal + threshold
-    DevBuf<double> d_lm_hg, d_lm_dt, d_lm_sacc;
-    DevBuf<int> d_lm_sub;                 // work list of k_lm_pass (tile, sub-block), see DevPtrs
-    int lm_n_sub = 0, lm_ksub = 1, lm_sub_per_item = 8;   // sub-blocks per work item of k_lm_pass (8 = the whole tile: MAX tile = 512 landmarks)   // throughput path: elimination records, per-landmark H_ll | g_l and per-tile key-frame sums (both per delta buffer)
-    int lm_max_cam = 1;
-    int hidden_eig_count = 0;             // sparsify: priors of full rank by their pivots whose inverse showed an eigenvalue that may lie below the cut (SADVIO_DEBUG prints it)
-    int marg_stats[4] = {0, 0, 0, 0};     // Cholesky-form marginalisations: calls | took the unpivoted route | tried it and fell back | calls whose rank the eigenvalue refinement lowered
-    int lm_sub_obs = 0;                   // most observations of LM_PASS_THREADS consecutive landmarks of a tile (LDS staging of k_lm_pass)
-    bool gemm_run4 = false;               // a tile on the MFMA path holds runs of 3 - 4 observations on one key-frame (k_build<.., RARE = true> only)
-    bool lm_ok = false;                   // every tile is on the MFMA path and chunked: k_build_obs / k_lm_pass may run
-    long long lm_landmarks = 0;
-    DevBuf<double> d_ptab;
-    int max_tile_kf = 1, max_tile_free = 0, max_gemm_free = 0;
-    DevBuf<double> d_obs_meas;
-    DevBuf<PriorDev> d_priors;
-    DevBuf<double> d_prior_lin;   // [2][n_prior][PRIOR_LIN], see DevPtrs::prior_lin
-    DevBuf<ImuDev> d_imus;
-    DevBuf<double> d_imu_scratch;
-    DevBuf<double> d_S, d_gred, d_gfull, d_hdiag, d_delta, d_s_pose;
-    DevBuf<LmState> d_states;
-    DevBuf<double> d_trace;
-    DevBuf<long long> d_tstart;
-    DevBuf<IterAcc> d_acc;
-    DevBuf<FinalRec> d_final;
-    FinalRec* h_final = nullptr;  // pinned
-    double* h_deltas = nullptr; size_t h_deltas_cap = 0; bool deltas_cached = false;   // pinned copy of BOTH delta buffers, fetched by the first get_deltas after a solve
-    size_t h_final_n = 0;
-    std::vector<FinalRec> fin;    // last solve's records
-    DevBuf<TileAcc> d_tacc;
-    DevBuf<long long> d_dbg;
-    // hipGraph of one complete solve (all slots), re-captured whenever the launch parameters change
-    hipGraphExec_t graph_exec = nullptr;
-    std::vector<unsigned char> graph_key;
-    DevBuf<double> d_probe;
-    bool has_lmk_const = false;
-    // profiling
-    std::vector<KernelClass> kclasses;
-    hipStream_t side = nullptr;            // IMU factor evaluation runs here, concurrently with k_build / k_backsub
-    hipEvent_t ev_fork = nullptr, ev_lin = nullptr, ev_solved = nullptr, ev_cost = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    std::vector<std::pair<int, int>> ev_used;  // (class, pool index)
-    size_t ev_next = 0;
-};
-
-namespace {
-
-int kclass_id(sadvio_ba_handle* h, const char* name) {
-    for (size_t i = 0; i < h->kclasses.size(); i++)
-        if (!strcmp(h->kclasses[i].name, name)) return (int)i;
-    KernelClass k; k.name = name;
-    h->kclasses.push_back(k);
-    return (int)h->kclasses.size() - 1;
-}
-
-struct ScopedTimer {
-    sadvio_ba_handle* h;
-    int pool = -1;
-    ScopedTimer(sadvio_ba_handle* h_, const char* name) : h(h_) {
-        if (!h->cfg.profile_kernels) return;
-        if (h->ev_next == h->ev_pool.size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-            h->ev_pool.push_back({a, b});
-        }
-        pool = (int)h->ev_next++;
-        h->ev_used.push_back({kclass_id(h, name), pool});
-        (void)hipEventRecord(h->ev_pool[pool].first, h->stream);
-    }
-    ~ScopedTimer() {
-        if (pool >= 0) (void)hipEventRecord(h->ev_pool[pool].second, h->stream);
-    }
-};
-
-void collect_timers(sadvio_ba_handle* h) {
-    for (auto& u : h->ev_used) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, h->ev_pool[u.second].first, h->ev_pool[u.second].second) == hipSuccess) {
-            h->kclasses[u.first].total_ms += ms;
-            h->kclasses[u.first].launches += 1;
-        }
-    }
-    h->ev_used.clear();
-    h->ev_next = 0;
-}
-
-DevPtrs make_ptrs(sadvio_ba_handle* h, const SolveOpts& o, int state_stride) {
-    DevPtrs P{};
-    P.win = h->d_win.p; P.tiles = h->d_tiles.p;
-    P.kf_T0 = h->d_kf_T0.p; P.kf_fidx = h->d_kf_fidx.p;
-    P.xp = h->d_xp.p; P.xv = h->d_xv.p; P.xba = h->d_xba.p; P.xbg = h->d_xbg.p;
-    P.xp_stride = 6LL * h->n_kf_tot; P.xv_stride = 3LL * h->n_kf_tot; P.xl_stride = 3LL * h->n_lmk_tot;
-    P.kf_vel = h->d_kf_vel.p; P.kf_ba = h->d_kf_ba.p; P.kf_bg = h->d_kf_bg.p;
-    P.cam_K = h->d_cam_K.p; P.cam_T = h->d_cam_T.p; P.cam_isig = h->d_cam_isig.p;
-    P.lmk_p = h->d_lmk_p.p; P.xl = h->d_xl.p; P.s_lmk = h->d_s_lmk.p;
-    P.lmk_const = h->has_lmk_const ? h->d_lmk_const.p : nullptr;
-    P.lmk_ob = h->d_lmk_ob.p; P.lmk_oe = h->d_lmk_oe.p;
-    P.obs_kf = h->d_obs_kf.p; P.obs_cam = h->d_obs_cam.p; P.obs_meas = h->d_obs_meas.p;
-    P.obs_slot = h->d_obs_slot.p; P.tile_kf = h->d_tile_kf.p; P.tile_lmk = h->d_tile_lmk.p; P.tile_row = h->d_tile_row.p;
-    P.pre_lane = h->pre_ok ? (const int4*)h->d_pre_lane.p : nullptr; P.pre_kf = h->pre_ok ? (const int2*)h->d_pre_kf.p : nullptr;
-    P.ptab = h->d_ptab.p; P.ptab_stride = (long long)POSE_TAB * h->n_kf_tot;
-    P.priors = h->d_priors.p; P.prior_lin = h->d_prior_lin.p; P.prior_lin_stride = (long long)h->priors.size() * PRIOR_LIN; P.n_prior_tot = (int)h->priors.size();
-    P.imus = h->d_imus.p; P.imu_scratch = h->d_imu_scratch.p; P.imu_scratch_stride = (long long)h->imus.size() * IMU_ROW;
-    P.S = h->d_S.p; P.gred = h->d_gred.p; P.gfull = h->d_gfull.p; P.hdiag = h->d_hdiag.p;
-    P.delta = h->d_delta.p; P.s_pose = h->d_s_pose.p;
-    P.dbg_ts = h->d_dbg.p;
-    P.trace = h->d_trace.p; P.t_start = h->d_tstart.p;
-    P.states = h->d_states.p; P.acc = h->d_acc.p; P.tacc = h->d_tacc.p; P.n_tiles = (int)h->tiles.size();
-    P.state_stride = state_stride;
-    P.final_out = h->h_final ? h->h_final : h->d_final.p;   // the final records go straight to pinned host memory (device-visible): no copy after the last kernel
-    P.big_info = h->d_big_info.p;
-    P.world = h->world; P.rank = h->rank; P.rank_b = h->d_rank_b.p; P.rank_s = h->d_rank_s.p;
-    P.lmk_red = h->d_lmk_red.p; P.kept_obs = h->d_kept_obs.p; P.n_kept = h->n_kept;
-    P.dp_data = h->d_dp_data.p; P.dp_ints = h->d_dp_ints.p;
-    P.sparse = h->d_sparse.p; P.sp_scratch = h->d_sp_scratch.p; P.sp_list = h->d_sp_list.p;
-    P.sp_scratch_stride = (long long)std::max<size_t>(h->n_sparse_tot, 1) * SPARSE_J; P.n_imu_tot = (int)h->imus.size(); P.n_sp_list = h->n_sp_list;
-    P.chunk_ob = h->d_chunk_ob.p; P.chunk_lm = h->d_chunk_lm.p; P.tile_perm = h->d_tile_perm.p; P.obs_lslot = h->d_obs_lslot.p;
-    P.lm_hg = h->d_lm_hg.p; P.lm_hg_stride = (long long)LM_HG * std::max(h->n_lmk_tot, 1);
-    P.lm_dt = h->d_lm_dt.p; P.lm_dt_stride = (long long)LM_DT * std::max<long long>((long long)h->tiles.size(), 1) * h->lm_ksub;
-    P.lm_sub = h->d_lm_sub.p; P.lm_ksub = h->lm_ksub; P.lm_sub_per_item = h->lm_sub_per_item; P.lm_sacc = h->lm_ok ? h->d_lm_sacc.p : nullptr;
-    P.lines = h->d_lines.p; P.lobs = h->d_lobs.p; P.xline = h->d_xline.p; P.line_scratch = h->d_line_scratch.p;
-    P.xline_stride = 6LL * h->n_line_tot;
-    P.n_xp = (long long)h->d_xp.n; P.n_xv = (long long)h->d_xv.n; P.n_xl = (long long)h->d_xl.n;
-    P.n_win = (int)h->wins.size();
-    P.debug = h->env.debug;
-    P.o = o;
-    return P;
-}
 
 // J^T of a dense prior, once per upload (J is constant during the solve); H = J^T J is a k_mgemm launch (FP64 matrix cores:
 // the one-thread-per-entry loop this replaces took 0.92 ms at n = 915, more than the layout build itself).
@@ -790,14 +333,6 @@ void sadvio_ba_destroy(sadvio_ba_handle* h) {
     for (hipEvent_t e : {h->ev_fork, h->ev_lin, h->ev_solved, h->ev_cost}) if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    h->d_win.release(); h->d_tiles.release(); h->d_kf_T0.release(); h->d_xp.release(); h->d_xv.release();
-    h->d_xba.release(); h->d_xbg.release(); h->d_kf_vel.release(); h->d_kf_ba.release(); h->d_kf_bg.release();
-    h->d_kf_fidx.release(); h->d_cam_K.release(); h->d_cam_T.release(); h->d_cam_isig.release();
-    h->d_lmk_p.release(); h->d_xl.release(); h->d_s_lmk.release(); h->d_lmk_const.release();
-    h->d_lmk_ob.release(); h->d_lmk_oe.release(); h->d_obs_kf.release(); h->d_obs_cam.release();
-    h->d_obs_meas.release(); h->d_priors.release(); h->d_prior_lin.release(); h->d_S.release(); h->d_rank_s.release(); h->d_gred.release(); h->d_gfull.release();
-    h->d_hdiag.release(); h->d_delta.release(); h->d_s_pose.release(); h->d_states.release(); h->d_trace.release(); h->d_tstart.release(); h->d_acc.release();
-    h->d_probe.release(); h->d_tile_kf.release(); h->d_tile_row.release(); h->d_tile_lmk.release(); h->d_obs_slot.release(); h->d_ptab.release(); h->d_tacc.release(); h->d_dbg.release(); h->d_imus.release(); h->d_imu_scratch.release();
     delete h;
 }
 
@@ -2766,162 +2301,12 @@ int sadvio_ba_comm_info(sadvio_ba_handle* h, int32_t* nranks, int32_t* rank, int
 }
 
 namespace {
-// The reduced system of an out-of-LDS window (N_p > MAX_LDS_NP) is factored and solved in HBM by one of five routes (dense_chol.h),
-// chosen once per solve call (BigPlan::choose).
-enum class BigRoute {
-    band,           // block-banded: one workgroup slides an LDS window down the band (k_band_solve)
-    band_twisted,   // long band: the twisted factorisation, both ends at once (k_band_solve x 2 + k_band_mid)
-    bcr,            // very long band of one window: block cyclic reduction over the bw x bw blocks (k_bcr_*)
-    wide,           // not banded, N >= 2 * WD: 96-column panels on the matrix cores (launch_wfac + k_wchol_backstep)
-    panel,          // not banded, N < 2 * WD: 32-column panels (k_chol_panel / k_chol_update / k_chol_backsolve)
-};
-struct BigPlan {
-    BigRoute route = BigRoute::panel;
-    int bw = 0;                   // rows below a block column of S that can be non-zero (block half-bandwidth + 1) * dpf
-    int C = 0;                    // band window of the band routes
-    long long linv_off = 0, mid_off = 0, M_off = 0, Lx_off = 0;   // the window's share of d_big_linv / d_big_mid / d_big_M / d_big_Lx
-    bool banded() const { return route == BigRoute::band || route == BigRoute::band_twisted || route == BigRoute::bcr; }
-    // route and C from bw; on a sharded window bw is the all-reduced one, so every rank takes the same route
-    void choose(const WinDev& d, int n_win, const EnvCfg& env) {
-        const int N = d.Np, nb = d.dpf == 6 ? 6 : 5;
-        if (!(bw < N && bw + nb <= MAX_LDS_NP)) {
-            route = N >= 2 * WD ? BigRoute::wide : BigRoute::panel;
-            return;
-        }
-        // with the update trimmed to the band a step costs the same in any window: the largest window that fits amortises the
-        // per-window carry / load / store best (SADVIO_BAND_C overrides, for measurements)
-        C = std::max(nb, (MAX_LDS_NP - bw) / nb * nb);
-        if (env.band_c > 0) C = std::max(nb, std::min(C, env.band_c / nb * nb));
-        const int Kb = (N + bw - 1) / bw;
-        if (nb == 6 && Kb >= 22 && 2 * bw <= MAX_LDS_NP - 1 && n_win == 1 && !env.no_bcr) route = BigRoute::bcr;   // below ~22 blocks the twisted solver wins (measured)
-        else if (N - bw >= 4 * C) route = BigRoute::band_twisted;
-        else route = BigRoute::band;
-    }
-};
-
-// LDS of the band kernels (k_band_solve, k_band_mid, k_bcr_elim / root): the in-LDS solver's window of R rows (pivot strip, packed
-// triangle + rhs row, two vectors) and `blocks` inverse pivot blocks of nb x nb
-size_t band_lds_bytes(int R, int nb, int blocks) {
-    return sizeof(double) * ((size_t)(R + 2) * 6 + (size_t)(R + 1) * (R + 2) / 2 + 2 * (size_t)R + (size_t)blocks * nb * nb) + 64;
-}
-
-// The routes: S (leading dimension d.ld) and y = gred of window d in place; dbg: SADVIO_DEBUG & 4096 stamps of this slot
-void solve_band(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
-    const int N = d.Np, bw = p.bw, C = p.C, nb = d.dpf == 6 ? 6 : 5;
-    const int Rmax = bw + C;
-    const size_t lds = band_lds_bytes(Rmax, nb, Rmax / nb + 1);
-    auto kbs = d.dpf == 6 ? k_band_solve<6> : k_band_solve<5>;
-    (void)hipFuncSetAttribute((const void*)kbs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    long long* ts = dbg ? h->d_dbg.p + 44 : nullptr;
-    double* lv = h->d_big_linv.p + p.linv_off;
-    if (p.route == BigRoute::band) {
-        hipLaunchKernelGGL(kbs, dim3(1), dim3(SOLVE_THREADS), lds, h->stream, S, (long long)d.ld, y, lv, N, bw, C, info, skip, ts, -1, 0, (double*)nullptr);
-        return;
-    }
-    const int M = (N - bw) / 2 / nb * nb;
-    double* md = h->d_big_mid.p + p.mid_off;
-    auto kbm = d.dpf == 6 ? k_band_mid<6> : k_band_mid<5>;
-    const size_t lds_m = band_lds_bytes(bw, nb, bw / nb + 1);
-    (void)hipFuncSetAttribute((const void*)kbm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
-    if (dbg) fprintf(stderr, "[sadvio dbg] twisted band solve N %d bw %d C %d M %d\n", N, bw, C, M);
-    hipLaunchKernelGGL(kbs, dim3(2), dim3(SOLVE_THREADS), lds, h->stream, S, (long long)d.ld, y, lv, N, bw, C, info, skip, ts, M, 0, md);
-    hipLaunchKernelGGL(kbm, dim3(1), dim3(SOLVE_THREADS), lds_m, h->stream, S, (long long)d.ld, y, N, bw, M, md, info, skip);
-    hipLaunchKernelGGL(kbs, dim3(2), dim3(SOLVE_THREADS), lds, h->stream, S, (long long)d.ld, y, lv, N, bw, C, info, skip, ts, M, 1, md);
-}
-
-size_t bcr_doubles(int N, int bw) {
-    const size_t b = (size_t)bw, K = ((size_t)N + b - 1) / b;
-    return K * (8 * b * b + b * (b + 1) / 2 + (b / 6) * 36 + 5 * b);
-}
-
-void solve_bcr(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
-    const int N = d.Np, bw = p.bw, Kb = (N + bw - 1) / bw;
-    const size_t b = (size_t)bw, bb = b * b, K = (size_t)Kb;
-    BcrPtrs B{};
-    double* q = h->d_bcr.p;
-    B.D = q; q += K * bb; B.E = q; q += K * bb; B.Wp = q; q += K * bb; B.Wn = q; q += K * bb;
-    B.Ul = q; q += K * bb; B.Ur = q; q += K * bb;
-    B.Lp = q; q += K * (b * (b + 1) / 2); B.linv = q; q += K * (b / 6) * 36;
-    B.g = q; q += K * b; B.yv = q; q += K * b; B.gl = q; q += K * b; B.gr = q; q += K * b; B.X = q; q += K * b;
-    B.K = Kb; B.b = bw; B.N = N;
-    const size_t lds_e = band_lds_bytes(2 * bw, 6, bw / 6 + 1);
-    const size_t lds_c = sizeof(double) * 2 * b * (b + 1);
-    const size_t lds_r = band_lds_bytes(2 * bw, 6, 2 * (bw / 6 + 1));   // up to two blocks, all 2 b / 6 pivot blocks kept
-    const size_t lds_b = sizeof(double) * (b * (b + 1) / 2 + 4 * b + (b / 6) * 36);
-    (void)hipFuncSetAttribute((const void*)k_bcr_elim<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e);
-    (void)hipFuncSetAttribute((const void*)k_bcr_combine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-    (void)hipFuncSetAttribute((const void*)k_bcr_root<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-    (void)hipFuncSetAttribute((const void*)k_bcr_back<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-    hipLaunchKernelGGL(k_bcr_extract, dim3(Kb), dim3(256), 0, h->stream, S, (long long)d.ld, y, B, skip, info);
-    int smax = 0, s_root = 0;
-    for (int sst = 1; sst < Kb; sst *= 2) {
-        const int na = (Kb + sst - 1) / sst;
-        if (na == 2) { s_root = sst; break; }   // two blocks left: solved together by k_bcr_root
-        hipLaunchKernelGGL(k_bcr_elim<6>, dim3(na / 2, 2), dim3(SOLVE_THREADS), lds_e, h->stream, B, sst, info, skip);
-        hipLaunchKernelGGL(k_bcr_combine, dim3(na), dim3(512), lds_c, h->stream, B, sst, info, skip);
-        smax = sst;
-    }
-    hipLaunchKernelGGL(k_bcr_root<6>, dim3(1), dim3(SOLVE_THREADS), lds_r, h->stream, B, s_root, info, skip);
-    for (int sst = smax; sst >= 1; sst /= 2) {
-        const int na = (Kb + sst - 1) / sst;
-        hipLaunchKernelGGL(k_bcr_back<6>, dim3(na / 2), dim3(256), lds_b, h->stream, B, sst, info, skip);
-    }
-    hipLaunchKernelGGL(k_bcr_writeback, dim3((N + 255) / 256), dim3(256), 0, h->stream, B, y, info, skip);
-    if (dbg) fprintf(stderr, "[sadvio dbg] block cyclic reduction N %d bw %d K %d\n", N, bw, Kb);
-}
-
-void solve_wide(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
-    const int N = d.Np, nsteps = (N + WD - 1) / WD;
-    double* M = h->d_big_M.p + p.M_off;
-    double* Ltw = M + (size_t)nsteps * WD * WD;
-    (void)hipFuncSetAttribute((const void*)k_wchol_backstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * WD * WDS));
-    launch_wfac(h, S, (long long)d.ld, N, y, h->d_big_Lx.p + p.Lx_off, Ltw, M, info, skip, dbg ? h->d_dbg.p + 106 : nullptr);
-    for (int bs = nsteps - 1; bs >= 0; bs--)
-        hipLaunchKernelGGL(k_wchol_backstep, dim3(1 + (bs + 1 < nsteps ? (bs * WD + 63) / 64 : 0)), dim3(SOLVE_THREADS), sizeof(double) * WD * WDS, h->stream,
-                           h->d_big_Lx.p + p.Lx_off, (long long)d.ld, y, M, N, bs, info, skip);
-}
-
-void solve_panel(sadvio_ba_handle* h, const WinDev& d, const BigPlan& p, double* S, double* y, int* info, const int* skip, bool dbg) {
-    const int N = d.Np;
-    for (int k0 = 0; k0 < N; k0 += CH_NB) {
-        const int nb = std::min(CH_NB, N - k0), s0 = k0 + nb;
-        const int rows_end = std::min(N, s0 + p.bw), m = rows_end - s0;
-        hipLaunchKernelGGL(k_chol_panel, dim3((m + 1 + CH_THREADS - 1) / CH_THREADS), dim3(CH_THREADS), 0, h->stream,
-                           S, (long long)d.ld, y, N, k0, rows_end, info, skip, dbg && k0 == 64 ? h->d_dbg.p + 44 : nullptr);
-        if (m > 0) {
-            const int nt = (m + CH_TS - 1) / CH_TS;
-            hipLaunchKernelGGL(k_chol_update, dim3(nt * (nt + 1) / 2 + (m + CH_THREADS - 1) / CH_THREADS), dim3(CH_THREADS), 0,
-                               h->stream, S, (long long)d.ld, y, N, k0, rows_end, info, skip);
-        }
-    }
-    hipLaunchKernelGGL(k_chol_backsolve, dim3(1), dim3(CH_THREADS), 0, h->stream, S, (long long)d.ld, y, N, p.bw, info, skip);
-}
-
-// Cholesky + solve of the reduced system of out-of-LDS window w at slot s by the route of its plan
-void solve_big(sadvio_ba_handle* h, const BigPlan& p, int w, int s, int stride, bool dbg) {
-    const WinDev& d = h->wins[w].d;
-    double* S = h->d_S.p + d.S_off;
-    double* y = h->d_gred.p + d.red_off;
-    int* info = h->d_big_info.p + w;
-    const int* skip = (const int*)((const char*)(h->d_states.p + (size_t)w * stride + s) + offsetof(LmState, done));
-    switch (p.route) {
-        case BigRoute::band: case BigRoute::band_twisted: solve_band(h, d, p, S, y, info, skip, dbg); break;
-        case BigRoute::bcr: solve_bcr(h, d, p, S, y, info, skip, dbg); break;
-        case BigRoute::wide: solve_wide(h, d, p, S, y, info, skip, dbg); break;
-        case BigRoute::panel: solve_panel(h, d, p, S, y, info, skip, dbg); break;
-    }
-}
-}  // namespace
-
-int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvio_solve_summary* summaries) {
-    if (!h) return SADVIO_E_INVALID_ARG;
-    if (!h->uploaded) { h->err = "solve before set_windows"; return SADVIO_E_STATE; }
-    if (h->defer) { h->err = "solve between begin_update and commit_update"; return SADVIO_E_STATE; }
+// The caller's options as the kernels take them; null: the defaults
+int convert_options(sadvio_ba_handle* h, const sadvio_solve_options* opts, SolveOpts& o) {
     sadvio_solve_options defo;
     if (!opts) { sadvio_ba_default_options(&defo); opts = &defo; }
     if (opts->max_num_iterations < 0 || opts->max_num_iterations > 1000) { h->err = "solve: max_num_iterations out of range"; return SADVIO_E_INVALID_ARG; }
-    HIP_TRY(hipSetDevice(h->device));
-    SolveOpts o{};
+    memset(&o, 0, sizeof(o));   // it travels in DevPtrs, whose bytes are part of the graph key
     o.max_num_iterations = opts->max_num_iterations; o.jacobi_scaling = opts->jacobi_scaling;
     o.max_num_consecutive_invalid_steps = opts->max_num_consecutive_invalid_steps;
     o.function_tolerance = opts->function_tolerance; o.gradient_tolerance = opts->gradient_tolerance;
@@ -2933,328 +2318,56 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
     // wall_clock64: 100 MHz. Not applied to a window sharded over several GPUs: the ranks' clocks would disagree on the slot
     o.max_time_ticks = (opts->max_solver_time_in_seconds > 0.0 && h->world == 1) ? opts->max_solver_time_in_seconds * 1e8 : 0.0;
     if (!(o.huber_a >= 0.0)) { h->err = "solve: huber_a must be >= 0"; return SADVIO_E_INVALID_ARG; }
-    const int n_win = (int)h->wins.size();
-    // Slot s (s = 0 .. slots-1) is one step attempt; with max_num_iterations = 0 Ceres still evaluates
-    // iteration 0, so at least one slot is always run and the final decision is taken by k_final.
-    const int slots = std::max(1, o.max_num_iterations);
-    const int stride = slots + 2;
-    HIP_TRY(h->d_dbg.alloc(DBG_SLOTS));
-    HIP_TRY(h->d_states.alloc((size_t)n_win * stride));
-    HIP_TRY(h->d_trace.alloc((size_t)n_win * stride * 8));
-    HIP_TRY(h->d_tstart.alloc(1));
-    HIP_TRY(h->d_acc.alloc((size_t)n_win * stride));
-    HIP_TRY(h->d_final.alloc((size_t)n_win));
-    HIP_TRY(h->d_big_info.alloc((size_t)n_win));
-    if (h->h_final_n < (size_t)n_win) {
-        if (h->h_final) (void)hipHostFree(h->h_final);
-        h->h_final = nullptr; h->h_final_n = 0;
-        HIP_TRY(hipHostMalloc((void**)&h->h_final, sizeof(FinalRec) * (size_t)n_win, hipHostMallocDefault));
-        h->h_final_n = (size_t)n_win;
-    }
-    DevPtrs P = make_ptrs(h, o, stride);
-    const int n_tiles = (int)h->tiles.size();
-    // with many tiles, re-summing all partials in every k_build workgroup costs more than one tiny launch per slot
-    // The decision of a slot is re-derived by every k_build workgroup from its OWN window's tile partials (read by all 256 threads
-    // with every load in flight: the cost does not depend on how many windows the batch has), as long as a window has at most
-    // 4 * BUILD_THREADS tiles (the canonical summation order of wave_sum_backsub_partials); a separate k_decide launch per slot
-    // only for larger windows (configs 4 / 5) and for the throughput kernels, which read the decided state.
-    int max_win_tiles = 0;
-    for (int w = 0; w < n_win; w++) max_win_tiles = std::max(max_win_tiles, h->wins[w].d.tile_end - h->wins[w].d.tile_begin);
-    P.decide_kernel = max_win_tiles > 4 * BUILD_THREADS ? 1 : 0;
-    // a sharded window keeps the item loop of k_solve: every rank must leave it with the same bits (plain adds, one factor at a time)
-    P.imu_direct = (!h->coll_fn && P.world == 1 && !h->env.imu_items) ? 1 : 0;
-    const int mtk = h->max_tile_kf;
-    const size_t nt = 6 * (size_t)h->max_tile_free;
-    int Rp = 16 * ((6 * h->max_gemm_free + 15) / 16);                          // padded rows of the Y / E strips
-    int strip_doubles = std::max(STAGE_VALS * 64, 2 * Rp * (32 + 2));          // per wave: Y | E strips, later the wave's copy of the tile
-    size_t lds_build = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)BUILD_WAVES * strip_doubles + nt * (nt + 1) / 2 + 3 * nt +
-                                                                   0) + 16;
-    if (lds_build > 160 * 1024 && h->max_gemm_free > 0) {
-        // a window mixing short tracks with very long ones: the MFMA strips + the large atomic tile do not fit
-        // together; run every tile on the ds_add_f64 path instead
-        for (auto& t : h->tiles) if (t.lds_mode == 2) t.lds_mode = 1;
-        HIP_TRY(hipMemcpyAsync(h->d_tiles.p, h->tiles.data(), h->tiles.size() * sizeof(Tile), hipMemcpyHostToDevice, h->stream));
-        h->max_gemm_free = 0;
-        Rp = 0; strip_doubles = STAGE_VALS * 64;
-        lds_build = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)BUILD_WAVES * strip_doubles + nt * (nt + 1) / 2 + 3 * nt +
-                                                               0) + 16;
-    }
-    if (h->env.debug) fprintf(stderr, "[sadvio dbg] lds_build %zu B, Rp %d, strip_doubles %d, max_tile_kf %d, max_tile_free %d, tiles %d\n", lds_build, Rp, strip_doubles, mtk, h->max_tile_free, n_tiles);
-    const size_t lds_back = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)mtk * 18) + 16;
-    // k_solve<0>: tile-packed image + y / gf / hd / xs + the chol16 exchange areas
-    const size_t npq = (size_t)h->max_np;
-    const size_t lds_solve = sizeof(double) * ((size_t)c16_size((int)npq) + 4 * npq + 1 + C16_WORK + 16 * (size_t)c16_blocks((int)npq + 1) + SOLVE_KFC * SOLVE_KFC_STRIDE) + 64;
-    // robust loss or prior-kept landmarks in the batch: the kernels carrying those (rare) paths
-    bool any_pseudo = false;
-    for (const auto& v : h->sp_elim) for (char e : v) any_pseudo |= e != 0;
-    // (kept landmarks: by their reduced columns, not by their observations — on a sharded window the ranks other than 0 hold them without any)
-    bool any_kept_lmk = false;
-    for (int w = 0; w < n_win; w++) any_kept_lmk |= h->wins[w].d.n_red > 0;
-    const bool rare = o.huber_a > 0.0 || h->n_kept > 0 || any_kept_lmk || any_pseudo || h->gemm_run4;
-    const bool pix = h->factor_type == SADVIO_FACTOR_PIXEL;
-    // IMU factor pairs and listed sparse-prior factors ride k_build (linearisation) and k_backsub (candidate cost) as extra workgroups
-    // when the submission is a window or two: the inlined linearisation leaves those variants of k_build one workgroup per CU, which
-    // a batch of VIO windows would pay for; there the evaluation runs as kernels of its own on the same stream (k_pf_eval)
-    const bool have_pf = !h->imus.empty() || h->n_sp_list > 0;
-    bool with_imu = have_pf && n_tiles <= 3 * 256;
-    if (h->env.pf_wg >= 0) with_imu = have_pf && h->env.pf_wg != 0;
-    auto kb = with_imu ? (pix ? (rare ? k_build<0, true, true> : k_build<0, false, true>) : (rare ? k_build<1, true, true> : k_build<1, false, true>))
-                       : (pix ? (rare ? k_build<0, true, false> : k_build<0, false, false>) : (rare ? k_build<1, true, false> : k_build<1, false, false>));
-    auto kk = with_imu ? (pix ? (rare ? k_backsub<0, true, true> : k_backsub<0, false, true>) : (rare ? k_backsub<1, true, true> : k_backsub<1, false, true>))
-                       : (pix ? (rare ? k_backsub<0, true, false> : k_backsub<0, false, false>) : (rare ? k_backsub<1, true, false> : k_backsub<1, false, false>));
-    auto kbk = h->factor_type == SADVIO_FACTOR_PIXEL ? k_build_kept<0> : k_build_kept<1>;
-    // large plain batches: the throughput kernels of lm_kernels.h (SADVIO_LM=1 / 0 forces / forbids them, for tests and A/B runs)
-    bool use_lm = h->lm_ok && !rare && !h->coll_fn && h->world == 1 && h->lm_landmarks >= 65536;
-    if (h->env.lm >= 0) use_lm = h->lm_ok && !rare && !h->coll_fn && h->world == 1 && h->env.lm != 0;
-    auto kbo = pix ? k_build_obs<0> : k_build_obs<1>;
-    auto kps = pix ? k_lm_pass<0, false> : k_lm_pass<1, false>;
-    auto kps0 = pix ? k_lm_pass<0, true> : k_lm_pass<1, true>;
-    const size_t lds_views = pix ? sizeof(double) * (size_t)mtk * h->lm_max_cam * LM_VT : 0;   // view tables of the pixel factor
-    const size_t lds_bobs = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)BUILD_WAVES * Rp * LM_KS + nt * (nt + 1) / 2 + nt + 1 + LM_DT) + lds_views + 16;
-    // k_lm_pass: tables at x (+ at the candidate, + the pose steps), the tile's key-frame sums, the staged observation constants
-    const size_t lds_pass0 = tile_tables_bytes(mtk) + sizeof(double) * LM_DT_COST + (size_t)h->lm_sub_obs * ((pix ? 2 : 3) * sizeof(double) + sizeof(int)) + lds_views + 16;
-    const size_t lds_pass = lds_pass0 + sizeof(double) * (size_t)mtk * (POSE_TAB + 6) + lds_views;
-    if (!use_lm) P.lm_sacc = nullptr;   // k_decide sums the tiles' k_backsub partials
-    if (use_lm) {
-        P.decide_kernel = 1;   // the kernels read the decided state of their slot
-        HIP_TRY(hipFuncSetAttribute((const void*)kbo, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bobs));
-        HIP_TRY(hipFuncSetAttribute((const void*)kps, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
-        HIP_TRY(hipFuncSetAttribute((const void*)kps0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass0));
-    }
-    HIP_TRY(hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_build));
-    HIP_TRY(hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_back));
-    bool extras = false;  // any pose-only factor family beyond PosePriordx in the batch?
-    for (int w = 0; w < n_win; w++) {
-        const WinDev& d = h->wins[w].d;
-        if (d.imu_end > d.imu_begin || d.sp_end > d.sp_begin || d.dp_n_full > 0 || d.dpf == 15 || d.lobs_end > d.lobs_begin || d.line_end > d.line_begin) extras = true;   // dpf 15: padded pivots live in the EXTRAS kernel
-    }
-    auto ks0 = extras ? k_solve<0, true> : k_solve<0, false>;
-    auto ks1 = extras ? k_solve<1, true> : k_solve<1, false>;
-    auto ks2 = extras ? k_solve<2, true> : k_solve<2, false>;
-    HIP_TRY(hipFuncSetAttribute((const void*)ks0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
-    const int reset_blocks = (int)std::min<long long>(1024, std::max<long long>(1, (P.n_xl + P.n_xp + 255) / 256));
-    // rows below a block column of S that can be non-zero: (block half-bandwidth + 1) * dpf from the co-visibility
-    // structure and the IMU pairs; a dense prior fills the kept-landmark block, so those windows are dense
-    std::vector<BigPlan> big(n_win);
-    for (int w = 0; w < n_win; w++) {
-        const WinDev& d = h->wins[w].d;
-        if (!d.ld) continue;
-        int hb = h->wins[w].hb_lmk;
-        for (const ImuDev& f : h->imus_per_win[w]) {
-            const int fi = h->h_kf_fidx[f.kf_i], fj = h->h_kf_fidx[f.kf_j];
-            if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
-        }
-        if (w < (int)h->sparse_per_win.size())
-            for (const sadvio_sparse_prior& sp : h->sparse_per_win[w])
-                if (sp.type == SADVIO_SPARSE_RELATIVE_POSE) {     // a relative-pose factor couples its two key-frames
-                    const int fi = h->h_kf_fidx[d.kf_base + sp.kf], fj = h->h_kf_fidx[d.kf_base + sp.kf_b];
-                    if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
-                }
-        big[w].bw = (d.n_red > 0 || d.dp_n_full > 0 || d.line_end > d.line_begin) ? d.Np : std::min(d.Np, (hb + 1) * d.dpf);
-    }
-    if (h->coll_fn && h->world > 1 && h->n_big) {
-        // every rank must factor the all-reduced S with the same (largest) bandwidth: gather the local ones
-        std::vector<double> slots((size_t)n_win * h->world * 4, 0.0);
-        for (int w = 0; w < n_win; w++) slots[((size_t)w * h->world + h->rank) * 4] = (double)big[w].bw;
-        HIP_TRY(hipMemcpyAsync(h->d_rank_s.p, slots.data(), slots.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        if (h->coll_fn(h->coll_ctx, h->d_rank_s.p, (int64_t)slots.size(), (void*)h->stream) != 0) { h->err = "solve: all-reduce failed"; return SADVIO_E_RCCL; }
-        HIP_TRY(hipMemcpyAsync(slots.data(), h->d_rank_s.p, slots.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        for (int w = 0; w < n_win; w++)
-            for (int r = 0; r < h->world; r++) big[w].bw = std::max(big[w].bw, (int)slots[((size_t)w * h->world + r) * 4]);
-    }
-    {
-        // the route of every out-of-LDS window and the workspace it needs, allocated here, never inside the (possibly captured) launch sequence
-        long long totv = 0, totm = 0, totM = 0, totL = 0;
-        for (int w = 0; w < n_win; w++) {
-            const WinDev& d = h->wins[w].d;
-            if (!d.ld) continue;
-            BigPlan& p = big[w];
-            p.choose(d, n_win, h->env);
-            const long long b = p.bw;
-            if (p.route == BigRoute::band || p.route == BigRoute::band_twisted) { p.linv_off = totv; totv += 6LL * d.Np; }
-            if (p.route == BigRoute::band_twisted) { p.mid_off = totm; totm += 2 * (b * (b + 1) / 2 + b); }
-            if (p.route == BigRoute::bcr) HIP_TRY(h->d_bcr.alloc(bcr_doubles(d.Np, p.bw)));   // (one window only)
-            if (p.route == BigRoute::wide) {
-                p.M_off = totM; totM += (long long)((d.Np + WD - 1) / WD) * (WD * WD + WD_LT);   // M | the factors' tiles
-                p.Lx_off = totL; totL += (long long)d.Np * d.ld;                              // the out-of-place panels
-            }
-        }
-        HIP_TRY(h->d_big_linv.alloc((size_t)std::max<long long>(totv, 1)));
-        HIP_TRY(h->d_big_mid.alloc((size_t)std::max<long long>(totm, 1)));
-        HIP_TRY(h->d_big_M.alloc((size_t)std::max<long long>(totM, 1)));
-        HIP_TRY(h->d_big_Lx.alloc((size_t)std::max<long long>(totL, 1)));
-    }
-    int dp_max_nf = 0, dp_max_n = 0;
-    for (int w = 0; w < n_win; w++) { dp_max_nf = std::max(dp_max_nf, h->wins[w].d.dp_n_full); dp_max_n = std::max(dp_max_n, h->wins[w].d.dp_n); }
-    bool coll_failed = false;
-    auto enqueue = [&]() {
-        {   // zero deltas / accumulators + initial LM state, and (extra blocks) the pose tables / prior records at x = 0
-            ScopedTimer t(h, "k_reset");
-            const int table_blocks = (std::max(h->n_kf_tot, (int)h->priors.size()) + 63) / 64;
-            hipLaunchKernelGGL(k_reset, dim3(reset_blocks + table_blocks), dim3(256), 0, h->stream, P, reset_blocks, h->n_kf_tot);
-        }
-        const int n_imu_all = (int)h->imus.size();
-        // IMU factor pairs and the listed sparse-prior factors ride the tile kernels as extra workgroups (kernels.h: pose_factor_eval).
-        // Line observations are still evaluated on a side stream: the linearisation next to k_build, the candidate cost next to
-        // k_backsub (fork / join with events; parallel branches of the captured graph)
-        const int n_pf = n_imu_all + h->n_sp_list;
-        const int n_lo = h->n_lobs_tot;
-        const bool fork = n_lo > 0 && h->side && !h->cfg.profile_kernels && !h->coll_fn && !h->env.no_fork;
-        for (int s = 0; s < slots; s++) {
-            if (fork) {
-                (void)hipEventRecord(h->ev_fork, h->stream);
-                (void)hipStreamWaitEvent(h->side, h->ev_fork, 0);
-                if (n_lo) hipLaunchKernelGGL(k_line_eval<true>, dim3(n_lo), dim3(64), 0, h->side, P, s, 1);
-                (void)hipEventRecord(h->ev_lin, h->side);
-            }
-            if (use_lm) {
-                // the opening pass linearises at x (H_ll, g_l per landmark, key-frame sums per tile); later slots get them from the
-                // candidate pass of the slot before
-                if (s == 0) { ScopedTimer t(h, "k_lm_pass0"); hipLaunchKernelGGL(kps0, dim3(h->lm_n_sub), dim3(LM_PASS_THREADS), lds_pass0, h->stream, P, s, mtk, h->lm_sub_obs); }
-                { ScopedTimer t(h, "k_build_obs"); hipLaunchKernelGGL(kbo, dim3(n_tiles), dim3(BUILD_THREADS), lds_bobs, h->stream, P, s, mtk, Rp); }
-            } else
-            { ScopedTimer t(h, "k_build"); hipLaunchKernelGGL(kb, dim3(n_tiles + (with_imu ? n_pf : 0)), dim3(BUILD_THREADS), lds_build, h->stream, P, s, mtk, strip_doubles, Rp); }
-            if (n_pf && (use_lm || !with_imu)) { ScopedTimer t(h, "k_pf_lin"); hipLaunchKernelGGL(k_pf_eval<false>, dim3(n_pf), dim3(BUILD_THREADS), 0, h->stream, P, s); }
-            if (h->n_kept) { ScopedTimer t(h, "k_build_kept"); hipLaunchKernelGGL(kbk, dim3((h->n_kept + 127) / 128), dim3(128), 0, h->stream, P, s); }
-            if (dp_max_nf > 0) {
-                ScopedTimer t(h, "k_prior_r+gh");
-                const int colb = (dp_max_n + 3) / 4;
-                hipLaunchKernelGGL(k_prior_r, dim3((dp_max_nf + 3) / 4, n_win), dim3(256), 0, h->stream, P, s);
-                hipLaunchKernelGGL(k_prior_gh, dim3(colb + (unsigned)(((long long)dp_max_n * dp_max_n + 255) / 256), n_win), dim3(256), 0, h->stream, P, s, colb);
-            }
-            if (h->coll_fn) {
-                // the window spans devices: gather the per-rank partial sums and all-reduce the reduced system
-                { ScopedTimer t(h, "k_rank_partials"); hipLaunchKernelGGL(k_rank_partials, dim3(n_win), dim3(64), 0, h->stream, P, s, 0); }
-                ScopedTimer t(h, "allreduce_reduced_system");
-                const WinDev& d0 = h->wins[0].d;
-                if (n_win == 1 && d0.ld && big[0].bw < d0.Np && d0.S_off == 0) {
-                    // one banded window spanning the devices: only the band of S travels (dense_chol.h: k_band_pack)
-                    const long long nbd = (long long)d0.Np * big[0].bw, tail = h->red_total - (long long)d0.Np * d0.ld;
-                    if (h->d_coll_band.alloc((size_t)(nbd + tail)) != hipSuccess) coll_failed = true;
-                    else {
-                        const int pb = (int)std::min<long long>((nbd + tail + 255) / 256, 2048);
-                        hipLaunchKernelGGL(k_band_pack, dim3(pb), dim3(256), 0, h->stream, h->d_S.p, (long long)d0.ld, d0.Np, big[0].bw, tail, h->d_coll_band.p, 0);
-                        if (h->coll_fn(h->coll_ctx, h->d_coll_band.p, (int64_t)(nbd + tail), (void*)h->stream) != 0) coll_failed = true;
-                        hipLaunchKernelGGL(k_band_pack, dim3(pb), dim3(256), 0, h->stream, h->d_S.p, (long long)d0.ld, d0.Np, big[0].bw, tail, h->d_coll_band.p, 1);
-                    }
-                } else if (h->coll_fn(h->coll_ctx, h->d_S.p, (int64_t)h->red_total, (void*)h->stream) != 0) coll_failed = true;
-            }
-            if (fork) (void)hipStreamWaitEvent(h->stream, h->ev_lin, 0);
-            else {
-                if (n_lo) { ScopedTimer t(h, "k_line_lin"); hipLaunchKernelGGL(k_line_eval<true>, dim3(n_lo), dim3(64), 0, h->stream, P, s, 0); }
-            }
-            if (h->n_big < n_win) { ScopedTimer t(h, "k_solve"); hipLaunchKernelGGL(ks0, dim3(n_win), dim3(SOLVE_THREADS), lds_solve, h->stream, P, s); }
-            if (h->n_big) {
-                { ScopedTimer t(h, "k_solve_front"); hipLaunchKernelGGL(ks1, dim3(n_win), dim3(SOLVE_THREADS), 64, h->stream, P, s); }
-                {
-                    ScopedTimer t(h, "reduced_cholesky_solve");
-                    for (int w = 0; w < n_win; w++)
-                        if (h->wins[w].d.ld) solve_big(h, big[w], w, s, stride, (P.debug & 4096) && s == 3);
-                }
-                { ScopedTimer t(h, "k_solve_back"); hipLaunchKernelGGL(ks2, dim3(n_win), dim3(SOLVE_THREADS), 64, h->stream, P, s); }
-                for (int w = 0; w < n_win; w++) {
-                    const WinDev& d = h->wins[w].d;
-                    if (!d.ld) continue;
-                    if (big[w].banded())   // only the band was written
-                        hipLaunchKernelGGL(k_band_zero, dim3((unsigned)std::min<long long>(((long long)d.Np * big[w].bw + 255) / 256, 4096)), dim3(256), 0, h->stream,
-                                           h->d_S.p + d.S_off, (long long)d.ld, d.Np, big[w].bw);
-                    else (void)hipMemsetAsync(h->d_S.p + d.S_off, 0, sizeof(double) * (size_t)d.Np * d.Np, h->stream);
-                }
-            }
-            if (fork) {
-                (void)hipEventRecord(h->ev_solved, h->stream);
-                (void)hipStreamWaitEvent(h->side, h->ev_solved, 0);
-                if (n_lo) hipLaunchKernelGGL(k_line_eval<false>, dim3(n_lo), dim3(64), 0, h->side, P, s, 0);
-                (void)hipEventRecord(h->ev_cost, h->side);
-            } else {
-                if (n_lo) { ScopedTimer t(h, "k_line_cost"); hipLaunchKernelGGL(k_line_eval<false>, dim3(n_lo), dim3(64), 0, h->stream, P, s, 0); }
-            }
-            if (dp_max_nf > 0) { ScopedTimer t(h, "k_prior_m"); hipLaunchKernelGGL(k_prior_m, dim3((dp_max_nf + 3) / 4, n_win), dim3(256), 0, h->stream, P, s); }
-            if (n_pf && (use_lm || !with_imu)) { ScopedTimer t(h, "k_pf_cost"); hipLaunchKernelGGL(k_pf_eval<true>, dim3(n_pf), dim3(64), 0, h->stream, P, s); }
-            if (use_lm) {
-                ScopedTimer t(h, "k_lm_pass"); hipLaunchKernelGGL(kps, dim3(h->lm_n_sub), dim3(LM_PASS_THREADS), lds_pass, h->stream, P, s, mtk, h->lm_sub_obs);
-            }
-            else
-            { ScopedTimer t(h, "k_backsub"); hipLaunchKernelGGL(kk, dim3(n_tiles + (with_imu ? n_pf : 0)), dim3(BUILD_THREADS), lds_back, h->stream, P, s, mtk); }
-            if (fork) (void)hipStreamWaitEvent(h->stream, h->ev_cost, 0);
-            if (h->coll_fn) {
-                { ScopedTimer t(h, "k_rank_partials"); hipLaunchKernelGGL(k_rank_partials, dim3(n_win), dim3(64), 0, h->stream, P, s, 1); }
-                ScopedTimer t(h, "allreduce_step_partials");
-                if (h->coll_fn(h->coll_ctx, h->d_rank_s.p, (int64_t)n_win * h->world * 4, (void*)h->stream) != 0) coll_failed = true;
-            }
-            if (P.decide_kernel) { ScopedTimer t(h, "k_decide"); hipLaunchKernelGGL(k_decide, dim3(n_win), dim3(max_win_tiles > 4 * BUILD_THREADS ? 1024 : 64), 0, h->stream, P, s, 0); }
-        }
-        { ScopedTimer t(h, "k_final"); hipLaunchKernelGGL(k_decide, dim3(n_win), dim3(64), 0, h->stream, P, slots - 1, 1); }
-    };
+    return SADVIO_OK;
+}
+}  // namespace
+
+int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvio_solve_summary* summaries) {
+    if (!h) return SADVIO_E_INVALID_ARG;
+    if (!h->uploaded) { h->err = "solve before set_windows"; return SADVIO_E_STATE; }
+    if (h->defer) { h->err = "solve between begin_update and commit_update"; return SADVIO_E_STATE; }
+    // 1. options
+    SolveOpts o;
+    if (int rc = convert_options(h, opts, o)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    // 2. plan: everything the launch sequence reads
+    SolvePlan plan;
+    std::vector<BigPlan> big;
+    if (int rc = plan_solve(h, o, plan, big)) return rc;
+    // 3. launch, as one graph where the handle asks for it
+    bool coll_ok = true;
     if (h->cfg.use_graph && !h->cfg.profile_kernels && !h->coll_fn) {
-        // the whole <= 20-iteration solve is one graph launch; the key covers every kernel argument
-        std::vector<int> lay;  // layout-dependent launch parameters of the out-of-LDS windows
-        for (int w = 0; w < n_win; w++) { lay.push_back(h->wins[w].d.Np); lay.push_back(h->wins[w].d.ld); lay.push_back(big[w].bw); }
-        lay.push_back(h->n_kept); lay.push_back(h->lm_sub_obs); lay.push_back(h->lm_n_sub); lay.push_back(h->lm_max_cam); lay.push_back(h->n_lobs_tot); lay.push_back(h->n_line_tot); lay.push_back(h->n_big); lay.push_back(dp_max_nf); lay.push_back(dp_max_n);
-        std::vector<unsigned char> key(sizeof(DevPtrs) + 8 * sizeof(int) + 3 * sizeof(size_t) + lay.size() * sizeof(int));
-        unsigned char* kp = key.data();
-        memcpy(kp + sizeof(DevPtrs) + 8 * sizeof(int) + 3 * sizeof(size_t), lay.data(), lay.size() * sizeof(int));
-        memcpy(kp, &P, sizeof(DevPtrs)); kp += sizeof(DevPtrs);
-        // launch-shape switches read from the environment inside enqueue() are part of the key too: a handle that already captured a
-        // graph must not replay it when an A/B switch changes
-        const int env_bits = (int)with_imu + 2 * (int)h->env.no_fork + 32 * (int)h->env.no_bcr + 128 * (int)h->env.no_lpt + 256 * (int)h->env.contig_tiles;
-        const int ints[8] = {slots, n_tiles, n_win, mtk, strip_doubles, Rp, h->n_kf_tot, h->factor_type + 2 * (int)extras + 4 * (int)rare + 8 * (int)use_lm + 16 * env_bits};  // P (incl. decide_kernel) is part of the key
-        memcpy(kp, ints, sizeof(ints)); kp += sizeof(ints);
-        const size_t szs[3] = {lds_build, lds_back, lds_solve};
-        memcpy(kp, szs, sizeof(szs));
+        // the whole <= 20-iteration solve is one graph launch, re-captured whenever the plan differs from the captured one in any byte
+        const unsigned char* pb = (const unsigned char*)&plan;
+        const unsigned char* bb = (const unsigned char*)big.data();
+        std::vector<unsigned char> key(pb, pb + sizeof(plan));
+        key.insert(key.end(), bb, bb + big.size() * sizeof(BigPlan));
         if (!h->graph_exec || key != h->graph_key) {
             if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
             hipGraph_t g = nullptr;
             HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            enqueue();
+            enqueue_solve(h, plan, big);
             HIP_TRY(hipStreamEndCapture(h->stream, &g));
             HIP_TRY(hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0));
             (void)hipGraphDestroy(g);
-            h->graph_key = key;
+            h->graph_key.swap(key);
         }
         HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
     } else {
-        enqueue();
+        coll_ok = enqueue_solve(h, plan, big);
     }
     HIP_TRY(hipGetLastError());
-    if (coll_failed) { h->err = "solve: the all-reduce of the reduced system failed"; return SADVIO_E_RCCL; }
+    if (!coll_ok) { h->err = "solve: the all-reduce of the reduced system failed"; return SADVIO_E_RCCL; }
+    // 4. wait, collect the timers
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->cfg.profile_kernels) collect_timers(h);
-    if ((h->env.debug & 4096)) {
-        long long ts[128];
-        if (hipMemcpy(ts, h->d_dbg.p, sizeof(ts), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "[sadvio dbg] phase dt (us):");
-            for (int i = 1; i < 16; i++) fprintf(stderr, " %d:%.2f", i, (ts[i] - ts[0]) * 0.01);
-            fprintf(stderr, "  shader clock %.3f GHz\n[sadvio dbg] k_build:", (double)(ts[21] - ts[20]) / ((ts[15] - ts[0]) * 10.0));
-            for (int i = 33; i < 43; i++) fprintf(stderr, " %d:%.2f", i, (ts[i] - ts[32]) * 0.01);
-            fprintf(stderr, "\n[sadvio dbg] first IMU pair of k_build, us since its start (residual + Jacobian on lane 0 | decision | W J | entries + adds): %.2f %.2f %.2f %.2f, start %.2f us after tile 0",
-                    (ts[57] - ts[56]) * 0.01, (ts[58] - ts[56]) * 0.01, (ts[59] - ts[56]) * 0.01, (ts[60] - ts[56]) * 0.01, (ts[56] - ts[32]) * 0.01);
-            fprintf(stderr, "\n[sadvio dbg] k_wchol_step (panel 1), us since the workgroup's start: look-ahead (operands in LDS | substituted | block updated | factored) %.2f %.2f %.2f %.2f",
-                    (ts[107] - ts[106]) * 0.01, (ts[108] - ts[106]) * 0.01, (ts[109] - ts[106]) * 0.01, (ts[110] - ts[106]) * 0.01);
-            fprintf(stderr, " | tile workgroup 7, %.2f us after it (operands | substituted | end) %.2f %.2f %.2f | inverse workgroup, %.2f us after it: %.2f",
-                    (ts[114] - ts[106]) * 0.01, (ts[115] - ts[114]) * 0.01, (ts[116] - ts[114]) * 0.01, (ts[117] - ts[114]) * 0.01, (ts[120] - ts[106]) * 0.01, (ts[121] - ts[120]) * 0.01);
-            fprintf(stderr, "\n[sadvio dbg] chol16 cycles since its first barrier (panel | trailing + next pivot, per block column):");
-            for (int i = 65; i < 81; i++) fprintf(stderr, " %lld", ts[i] - ts[64]);
-            fprintf(stderr, " | end %lld", ts[84] - ts[64]);
-            fprintf(stderr, "\n[sadvio dbg] k_chol_panel / k_band_solve (fwd window 2: carry fresh chol store | fwd end | bwd window 2: load below steps | bwd end):");
-            for (int i = 45; i < 55; i++) fprintf(stderr, " %d:%.2f", i - 44, (ts[i] - ts[44]) * 0.01);
-            fprintf(stderr, "\n");
-        }
-#ifdef SADVIO_KERNEL_TS
-        // every workgroup of one k_build launch: start / end relative to workgroup 0's start, and the CU it ran on
-        std::vector<long long> wg(4 * (size_t)std::min(n_tiles, DBG_WG_MAX));
-        if (!wg.empty() && hipMemcpy(wg.data(), h->d_dbg.p + DBG_WG_BASE, wg.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess)
-            for (size_t b = 0; b < wg.size() / 4; b++) {
-                const unsigned hw = (unsigned)wg[4 * b + 2];
-                fprintf(stderr, "[sadvio dbg] k_build wg %zu start %.2f end %.2f xcc %d se %u sh %u cu %u simd %u\n", b, (wg[4 * b] - wg[0]) * 0.01, (wg[4 * b + 1] - wg[0]) * 0.01,
-                        (int)((wg[4 * b + 2] >> 32) & 15), (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 15, (hw >> 4) & 3);
-            }
-#endif
-    }
+    // 5. diagnostics
+    if (h->env.debug & 4096) print_debug_stamps(h, plan.P.n_tiles);
+    // 6. summaries
+    const int n_win = plan.P.n_win;
     h->fin.assign(h->h_final, h->h_final + n_win);
     h->deltas_cached = false;
-    h->last_slots = slots;
+    h->last_slots = plan.slots;
     h->solved = true;
     int rc = SADVIO_OK;
     for (int w = 0; w < n_win; w++) {
@@ -3267,8 +2380,6 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
         }
         if (s.termination == SADVIO_TERM_FAILURE) rc = SADVIO_E_NOT_USABLE;
     }
-    // remember which buffer holds x for each window
-    (void)h->d_probe.alloc(1);
     return rc;
 }
 

@@ -1,0 +1,423 @@
+// ba_handle.h — the handle behind the C ABI (sadvio_ba_handle) and its helper structs: device buffers, the staged upload batch,
+// the host copies of the caller's windows, the environment switches and the kernel-class timers.
+// Part of the library's single translation unit (ba_capi.hip); not a public header.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <dlfcn.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/sadvio_ba.h"
+#include "kernels.h"
+#include "tile_pack.h"
+#include "dense_chol.h"
+#include "marg_kernels.h"
+#include "lm_kernels.h"
+#include "viinit_kernels.h"
+#include "nofov_kernels.h"
+
+using namespace sadvio;
+
+namespace {
+
+#define HIP_TRY(expr)                                                                        \
+    do {                                                                                      \
+        hipError_t _e = (expr);                                                               \
+        if (_e != hipSuccess) {                                                               \
+            h->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
+            return SADVIO_E_HIP;                                                              \
+        }                                                                                     \
+    } while (0)
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    hipError_t alloc(size_t count) {
+        if (count <= n && p && !view) return hipSuccess;
+        if (p && !view) (void)hipFree(p);
+        view = false;
+        p = nullptr; n = 0;
+        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    bool view = false;  // non-owning window into another buffer
+    void set_view(T* ptr, size_t count) { if (p && !view) (void)hipFree(p); p = ptr; n = count; view = true; }
+    void release() { if (p && !view) (void)hipFree(p); p = nullptr; n = 0; view = false; }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(view, o.view); }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+};
+
+struct KernelClass {
+    const char* name;
+    double total_ms = 0;
+    long long launches = 0;
+};
+
+struct HostWin {
+    WinDev d;
+    std::vector<int64_t> kf_id, lmk_id;
+    int hb_lmk = 0;  // max distance (in free key-frame index) between two key-frames observing one landmark
+};
+
+}  // namespace
+
+// RCCL (all-reduce of the reduced system over xGMI), loaded on first use: single-GPU solves never touch it.
+struct NcclId { char internal[128]; };
+struct RcclLib {
+    void* lib = nullptr;
+    void* comm = nullptr;
+    int (*get_id)(NcclId*) = nullptr;
+    int (*init_rank)(void**, int, NcclId, int) = nullptr;
+    int (*all_reduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
+    int (*destroy)(void*) = nullptr;
+    const char* (*err_string)(int) = nullptr;
+    int (*comm_count)(void*, int*) = nullptr;
+    int (*comm_user_rank)(void*, int*) = nullptr;
+    int (*comm_cu_device)(void*, int*) = nullptr;
+};
+
+// Deep copy of a caller's window (set_windows) + the observation arrays actually tiled: pose-to-landmark NFR factors
+// whose landmark can be eliminated are appended to the landmark's observation list as two pseudo-observations
+// (rows 0-1 and row 2 of the 3-row factor), so that they ride the ordinary Schur elimination.
+struct SrcWin {
+    sadvio_flat_window v{};   // view into the vectors below
+    std::vector<int64_t> kf_id, lmk_id;
+    std::vector<double> kf_T, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_sigma, lmk_p, obs_meas;
+    std::vector<uint8_t> kf_const, lmk_const;
+    std::vector<int32_t> lmk_obs_ptr, obs_kf, obs_cam;
+    // augmented observation list (what build_layout tiles) and its map to the caller's observation index (-1 = pseudo)
+    std::vector<int32_t> a_ptr, a_kf, a_cam, a_src;
+    std::vector<double> a_meas;
+    // cameras with identical (K, T_s_f, sigma) are stored once: SaDVIO has one ImageSensor object per (frame, camera),
+    // i.e. 2 x N_kf table entries that are all copies of the rig's two cameras
+    std::vector<double> u_cam_K, u_cam_T, u_cam_sigma;
+    std::vector<int32_t> u_obs_cam;
+    std::vector<int> cam_map;   // caller's camera index -> stored camera index
+};
+
+// Host -> device uploads of one layout build are packed into ONE pinned staging buffer, copied with one
+// hipMemcpyAsync and scattered to their destinations by one kernel: ~25 small pageable copies cost ~15 us each.
+struct UploadItem { unsigned long long dst; unsigned long long off; unsigned long long bytes; };
+__global__ void k_scatter_uploads(const char* stage, const UploadItem* items, int n_items) {
+    for (int it = blockIdx.y; it < n_items; it += gridDim.y) {
+        const UploadItem u = items[it];
+        char* dst = (char*)u.dst;
+        const char* src = stage + u.off;
+        const unsigned long long words = u.bytes >> 3;  // staging offsets and device allocations are 8-byte aligned
+        for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (unsigned long long)gridDim.x * blockDim.x)
+            ((unsigned long long*)dst)[i] = ((const unsigned long long*)src)[i];
+        if (blockIdx.x == 0 && threadIdx.x < (u.bytes & 7)) dst[(words << 3) + threadIdx.x] = src[(words << 3) + threadIdx.x];
+    }
+}
+struct UploadBatch {
+    std::vector<UploadItem> items;
+    char* pinned = nullptr; size_t pinned_cap = 0, used = 0;   // sources are packed straight into pinned memory
+    char* dev = nullptr; size_t dev_cap = 0;
+    bool failed = false;
+    // flush() does not wait: the staged copy + scatter are stream work like the kernels that read their output. The pinned buffer is
+    // only touched again (next add / grow) after the event recorded behind the copy has fired — by then it normally has
+    hipEvent_t ev = nullptr;
+    bool in_flight = false;
+    void wait() { if (in_flight) { (void)hipEventSynchronize(ev); in_flight = false; } }
+    void reset() { wait(); items.clear(); used = 0; failed = false; }   // drop what an earlier, failed layout build left queued
+    void reserve(size_t bytes) {
+        if (bytes <= pinned_cap) return;
+        wait();
+        char* np = nullptr;
+        const size_t cap = bytes + bytes / 2 + 4096;
+        if (hipHostMalloc((void**)&np, cap, hipHostMallocDefault) != hipSuccess) { failed = true; return; }
+        if (pinned) { memcpy(np, pinned, used); (void)hipHostFree(pinned); }
+        pinned = np; pinned_cap = cap;
+    }
+    void add(void* dst, const void* src, size_t bytes) {
+        if (!bytes) return;
+        wait();
+        const size_t off = (used + 7) & ~(size_t)7;
+        reserve(off + bytes);
+        if (failed) return;
+        memcpy(pinned + off, src, bytes);
+        used = off + bytes;
+        items.push_back({(unsigned long long)dst, (unsigned long long)off, (unsigned long long)bytes});
+    }
+    hipError_t flush(hipStream_t stream) {
+        if (failed) { failed = false; items.clear(); used = 0; return hipErrorOutOfMemory; }
+        if (items.empty()) return hipSuccess;
+        const size_t data_bytes = (used + 7) & ~(size_t)7;
+        const size_t total = data_bytes + items.size() * sizeof(UploadItem);
+        reserve(total);
+        if (failed) { failed = false; items.clear(); used = 0; return hipErrorOutOfMemory; }
+        hipError_t e = hipSuccess;
+        // every error return drops the queue: callers that do not reset() afterwards (marginalize, sparsify) must not re-send it
+        auto drop = [&](hipError_t err) { items.clear(); used = 0; return err; };
+        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return drop(e);
+        if (dev_cap < total) {
+            if (dev) { (void)hipStreamSynchronize(stream); (void)hipFree(dev); }   // an earlier scatter may still read it
+            dev = nullptr; dev_cap = 0;
+            if ((e = hipMalloc((void**)&dev, total + total / 2)) != hipSuccess) return drop(e);
+            dev_cap = total + total / 2;
+        }
+        memcpy(pinned + data_bytes, items.data(), items.size() * sizeof(UploadItem));
+        if ((e = hipMemcpyAsync(dev, pinned, total, hipMemcpyHostToDevice, stream)) != hipSuccess) return drop(e);
+        hipLaunchKernelGGL(k_scatter_uploads, dim3(64, (unsigned)std::min<size_t>(items.size(), 64)), dim3(256), 0, stream, dev, (const UploadItem*)(dev + data_bytes), (int)items.size());
+        e = hipEventRecord(ev, stream);
+        in_flight = e == hipSuccess;
+        if (!in_flight) e = hipStreamSynchronize(stream);
+        items.clear(); used = 0;
+        return e;
+    }
+    ~UploadBatch() { wait(); if (ev) (void)hipEventDestroy(ev); if (pinned) (void)hipHostFree(pinned); if (dev) (void)hipFree(dev); }
+};
+
+struct DensePriorHost {
+    int n_full = 0, n = 0, kf_keep = -1, kf_col = 0;
+    bool resident = false;      // J, r0 = the handle's prior (PriorState), copied device to device
+    unsigned long long serial = 0;   // ... as it was when set_dense_prior named it
+    std::vector<double> J, r0;
+    std::vector<int> lmk_index, lmk_col;
+};
+
+// The handle's marginalisation prior: what the reference keeps in `_marginalization_last` inside the optimizer between
+// marginalize() and the next window solve / the next marginalize() (AOptimizer.h:88-90, …Analytic.cpp:627-660). Device
+// resident; the variables its columns refer to are named by the caller per window (it owns the id bookkeeping).
+struct PriorState {
+    bool valid = false;
+    int n_full = 0, n = 0, form = 0, cut_mode = 0;   // cut_mode: the SADVIO_EIG_CUT_* it was built with (sparsify applies the same cut)
+    DevBuf<double> J, r0;        // n_full x n row-major packed, n_full
+    DevBuf<double> Z;            // n_full x n with Z^T Z = Sigma_k (built by the first sparsify of this prior)
+    bool z_valid = false;
+    DevBuf<int> step_of;         // Cholesky form: pivot step of every column
+    DevBuf<double> H, g;         // J^T J = Ak and -J^T r0 = bk as the marginalisation that built the prior had them (full-rank Cholesky form only):
+    bool hg_valid = false;       // the next marginalize / the next window's dense prior take them instead of re-forming J^T J (n^3 flops)
+    unsigned long long serial = 0;   // bumped whenever the prior changes: a window that attached it checks it is still the same one
+};
+
+// Work buffers of marginalize / sparsify, kept in the handle: both run once per key-frame, and ~20 hipMalloc / hipFree pairs
+// per call cost more than the kernels between them.
+struct TriLevel { int first, count, max_m, max_n; };
+struct MargScratch {
+    DevBuf<double> A, b, G, V, ev, Vs, Ainv, T, Ak, bk, newJ, newr, lastJ, lastr, L, Tb, Zt, S, mi, jsel, lam, wtmp, Hl;
+    DevBuf<int> ditems, flag, sel, lastcol, piv_of, lc, piv_mm;
+    DevBuf<MargSmall> small;
+    DevBuf<NfrSpecC> spec;
+    std::vector<int> lcol, items, items_l, col;
+    std::vector<double> hev, hS;
+    struct TriPlan { DevBuf<TriNode> nodes; std::vector<TriLevel> levels; int leaves = 0; };
+    std::map<int, TriPlan> tri_plans;   // node tables of the triangular inverse, by padded size (m of Amm and n of the prior alternate)
+};
+
+struct LineSetHost {   // deep copy of a sadvio_line_set
+    std::vector<int64_t> id;
+    std::vector<double> T, model, meas;
+    std::vector<unsigned char> is_const;
+    std::vector<int> ptr, obs_kf, obs_cam;
+    int n() const { return (int)id.size(); }
+};
+
+// Host-side work arrays of build_layout, kept between calls: a sliding-window back end calls set_windows once per key-frame,
+// and ~2 MB of fresh std::vectors per call are ~500 page faults (more than the layout arithmetic itself).
+struct LayoutScratch {
+    std::vector<double> kf_T0, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_isig, lmk_p, obs_meas;
+    std::vector<int> kf_fidx, lmk_ob, lmk_oe, obs_kf, obs_cam, tile_kf, tile_row, tile_lmk, pack_order, pack_cut, pkf, pcam, run_max, idx, mark, add, kfs, slot_of, chunk_ob, chunk_lm, perm;
+    std::vector<unsigned char> lmk_const, obs_slot, obs_lslot;
+    std::vector<char> held;
+};
+
+// The diagnostic switches of DESIGN.md 4 (environment), read ONCE when the handle is created: none is needed in production, and none is
+// looked up again on a per-key-frame path (round 4 called getenv 39 times across set_windows / marginalize / solve).
+struct EnvCfg {
+    int debug = 0;
+    int lm = -1, pf_wg = -1;            // -1: not set
+    int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
+    double jacobi_tol = 1e-14;
+    bool marg_last_small = false, marg_eig_mm = false, marg_pivoted = false, marg_unpivoted = false, pchol_swap = false, pchol_strict = false,
+         jacobi_b4 = false, jacobi_plain = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false;
+    void read() {
+        auto on = [](const char* k) { return getenv(k) != nullptr; };
+        auto num = [](const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; };
+        debug = num("SADVIO_DEBUG", 0); lm = num("SADVIO_LM", -1); pf_wg = num("SADVIO_PF_WG", -1);
+        tile_rounds = num("SADVIO_TILE_ROUNDS", 0); lm_subs = num("SADVIO_LM_SUBS", 0); band_c = num("SADVIO_BAND_C", 0);
+        if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);
+        marg_last_small = on("SADVIO_MARG_LAST_SMALL"); marg_eig_mm = on("SADVIO_MARG_EIG_MM"); marg_pivoted = on("SADVIO_MARG_PIVOTED");
+        marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_swap = on("SADVIO_PCHOL_SWAP"); pchol_strict = on("SADVIO_PCHOL_STRICT");
+        jacobi_b4 = on("SADVIO_JACOBI_B4"); jacobi_plain = on("SADVIO_JACOBI_PLAIN"); no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
+        no_bcr = on("SADVIO_NO_BCR");
+        contig_tiles = on("SADVIO_CONTIG_TILES");   // A/B: single-round tiles as runs of consecutive landmarks (no packing, tile_pack.h)
+        imu_items = on("SADVIO_IMU_ITEMS");   // A/B: the IMU pairs' entries through k_solve's item loop (the pre-0.5 path) on one device too
+    }
+};
+
+struct sadvio_ba_handle {
+    EnvCfg env;
+    sadvio_ba_config cfg{};
+    LayoutScratch ls;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    // host mirrors
+    std::vector<HostWin> wins;
+    std::vector<Tile> tiles;
+    std::vector<PriorDev> priors;
+    std::vector<int> obs_perm;  // device observation position -> caller's observation index (within window)
+    std::vector<std::vector<PriorDev>> priors_per_win;
+    std::vector<std::vector<ImuDev>> imus_per_win;
+    std::vector<ImuDev> imus;
+    int n_kf_tot = 0, n_cam_tot = 0, n_lmk_tot = 0, n_obs_tot = 0, np_tot = 0;
+    long long s_tot = 0;
+    int factor_type = 0;
+    int max_n_kf = 0, max_npose = 0, max_np = 0, n_big = 0;
+    DevBuf<int> d_big_info;
+    DevBuf<double> d_big_M;     // inverse diagonal blocks of the wide-panel dense solver, 96 x 96 per 96 columns (+ the factors' tiles)
+    DevBuf<double> d_big_Lx;    // its out-of-place panels
+    DevBuf<double> d_big_linv;  // inverse pivot blocks of the banded solver, N * NB doubles per out-of-LDS window
+    DevBuf<double> d_coll_band; // band-packed copy of the reduced system for the sharded all-reduce
+    DevBuf<double> d_bcr;       // block-cyclic-reduction workspace of the long banded systems
+    DevBuf<double> d_big_mid;   // the two Schur complements on the middle block of the twisted banded factorisation
+    bool uploaded = false, solved = false;
+    bool defer = false, pending = false;   // begin_update .. commit_update: set_* calls only record, ONE layout build + staged upload at commit
+    UploadBatch up;   // pending host -> device uploads of the current layout build
+    // window sharded over several GPUs: collective hook (user callback or the built-in RCCL one)
+    int world = 1, rank = 0;
+    sadvio_allreduce_fn coll_fn = nullptr;
+    void* coll_ctx = nullptr;
+    RcclLib rccl;
+    long long red_total = 0;  // doubles in [S | gred | gfull | hdiag | rank_b], the buffer of the per-step all-reduce
+    DevBuf<double> d_rank_b, d_rank_s;
+    // dense marginalisation priors (host copies, one per window) and the layout they induce
+    std::vector<DensePriorHost> dprior_per_win;
+    PriorState prior;   // the handle's own prior (sadvio_ba_marginalize leaves it here)
+    MargScratch mg;
+    std::vector<SrcWin> src;                       // caller windows (deep copies)
+    std::vector<std::vector<char>> sp_elim;        // per window, per sparse factor: handled as pseudo-observations
+    std::vector<int> n_obs_user;                   // caller's observation count per window
+    std::vector<std::vector<sadvio_sparse_prior>> sparse_per_win;
+    std::vector<LineSetHost> lines_per_win;        // linexd landmarks
+    DevBuf<LineDev> d_lines;
+    DevBuf<LineObsDev> d_lobs;
+    DevBuf<double> d_xline, d_line_scratch;
+    int n_line_tot = 0, n_lobs_tot = 0;
+    DevBuf<SparseDev> d_sparse;
+    DevBuf<int> d_sp_list;
+    int n_sp_list = 0;   // sparse prior factors evaluated by sparse_factor_eval (all windows)
+    size_t n_sparse_tot = 0;
+    DevBuf<double> d_sp_scratch;
+    std::vector<unsigned char> h_lmk_const_user;  // as given by the caller
+    std::vector<int> h_lmk_ob, h_lmk_oe, h_kf_fidx, h_obs_kf;
+    bool user_lmk_const = false;
+    int n_kept = 0;
+    DevBuf<int> d_lmk_red, d_kept_obs, d_dp_ints;
+    DevBuf<double> d_dp_data;
+    int last_slots = 0;
+    // device buffers
+    DevBuf<WinDev> d_win;
+    DevBuf<Tile> d_tiles;
+    DevBuf<double> d_kf_T0, d_xp, d_xv, d_xba, d_xbg, d_kf_vel, d_kf_ba, d_kf_bg;
+    DevBuf<int> d_kf_fidx;
+    DevBuf<double> d_cam_K, d_cam_T, d_cam_isig;
+    DevBuf<double> d_lmk_p, d_xl, d_s_lmk;
+    DevBuf<unsigned char> d_lmk_const;
+    DevBuf<int> d_lmk_ob, d_lmk_oe, d_obs_kf, d_obs_cam, d_tile_kf, d_tile_row, d_tile_lmk;
+    DevBuf<int> d_pre_lane, d_pre_kf;     // first-round packets of the latency kernels (kernels.h: DevPtrs::pre_lane), few-tile submissions only
+    bool pre_ok = false, pre_dirty = false;
+    DevBuf<int> d_rank_col; DevBuf<double> d_rank_x;       // refine_rank_by_eigenvalue (guarded calls only): pivot column per step, the solved vectors
+    DevBuf<unsigned char> d_obs_slot, d_obs_lslot;
+    DevBuf<int> d_chunk_ob, d_chunk_lm, d_tile_perm;   // chunk tables of the throughput kernels (lm_kernels.h)
+    DevBuf<int> d_jac_ints;               // pivoting / rank of the Cholesky-preconditioned Jacobi
+    DevBuf<double> d_jac_dbl;             // its remaining diagonal + threshold
+    DevBuf<double> d_lm_hg, d_lm_dt, d_lm_sacc;
+    DevBuf<int> d_lm_sub;                 // work list of k_lm_pass (tile, sub-block), see DevPtrs
+    int lm_n_sub = 0, lm_ksub = 1, lm_sub_per_item = 8;   // sub-blocks per work item of k_lm_pass (8 = the whole tile: MAX tile = 512 landmarks)   // throughput path: elimination records, per-landmark H_ll | g_l and per-tile key-frame sums (both per delta buffer)
+    int lm_max_cam = 1;
+    int hidden_eig_count = 0;             // sparsify: priors of full rank by their pivots whose inverse showed an eigenvalue that may lie below the cut (SADVIO_DEBUG prints it)
+    int marg_stats[4] = {0, 0, 0, 0};     // Cholesky-form marginalisations: calls | took the unpivoted route | tried it and fell back | calls whose rank the eigenvalue refinement lowered
+    int lm_sub_obs = 0;                   // most observations of LM_PASS_THREADS consecutive landmarks of a tile (LDS staging of k_lm_pass)
+    bool gemm_run4 = false;               // a tile on the MFMA path holds runs of 3 - 4 observations on one key-frame (k_build<.., RARE = true> only)
+    bool lm_ok = false;                   // every tile is on the MFMA path and chunked: k_build_obs / k_lm_pass may run
+    long long lm_landmarks = 0;
+    DevBuf<double> d_ptab;
+    int max_tile_kf = 1, max_tile_free = 0, max_gemm_free = 0;
+    DevBuf<double> d_obs_meas;
+    DevBuf<PriorDev> d_priors;
+    DevBuf<double> d_prior_lin;   // [2][n_prior][PRIOR_LIN], see DevPtrs::prior_lin
+    DevBuf<ImuDev> d_imus;
+    DevBuf<double> d_imu_scratch;
+    DevBuf<double> d_S, d_gred, d_gfull, d_hdiag, d_delta, d_s_pose;
+    DevBuf<LmState> d_states;
+    DevBuf<double> d_trace;
+    DevBuf<long long> d_tstart;
+    DevBuf<IterAcc> d_acc;
+    DevBuf<FinalRec> d_final;
+    FinalRec* h_final = nullptr;  // pinned
+    double* h_deltas = nullptr; size_t h_deltas_cap = 0; bool deltas_cached = false;   // pinned copy of BOTH delta buffers, fetched by the first get_deltas after a solve
+    size_t h_final_n = 0;
+    std::vector<FinalRec> fin;    // last solve's records
+    DevBuf<TileAcc> d_tacc;
+    DevBuf<long long> d_dbg;
+    // hipGraph of one complete solve (all slots), re-captured whenever the launch parameters change
+    hipGraphExec_t graph_exec = nullptr;
+    std::vector<unsigned char> graph_key;
+    DevBuf<double> d_probe;
+    bool has_lmk_const = false;
+    // profiling
+    std::vector<KernelClass> kclasses;
+    hipStream_t side = nullptr;            // IMU factor evaluation runs here, concurrently with k_build / k_backsub
+    hipEvent_t ev_fork = nullptr, ev_lin = nullptr, ev_solved = nullptr, ev_cost = nullptr;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<int, int>> ev_used;  // (class, pool index)
+    size_t ev_next = 0;
+};
+
+namespace {
+
+int kclass_id(sadvio_ba_handle* h, const char* name) {
+    for (size_t i = 0; i < h->kclasses.size(); i++)
+        if (!strcmp(h->kclasses[i].name, name)) return (int)i;
+    KernelClass k; k.name = name;
+    h->kclasses.push_back(k);
+    return (int)h->kclasses.size() - 1;
+}
+
+struct ScopedTimer {
+    sadvio_ba_handle* h;
+    int pool = -1;
+    ScopedTimer(sadvio_ba_handle* h_, const char* name) : h(h_) {
+        if (!h->cfg.profile_kernels) return;
+        if (h->ev_next == h->ev_pool.size()) {
+            hipEvent_t a, b;
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
+            h->ev_pool.push_back({a, b});
+        }
+        pool = (int)h->ev_next++;
+        h->ev_used.push_back({kclass_id(h, name), pool});
+        (void)hipEventRecord(h->ev_pool[pool].first, h->stream);
+    }
+    ~ScopedTimer() {
+        if (pool >= 0) (void)hipEventRecord(h->ev_pool[pool].second, h->stream);
+    }
+};
+
+void collect_timers(sadvio_ba_handle* h) {
+    for (auto& u : h->ev_used) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, h->ev_pool[u.second].first, h->ev_pool[u.second].second) == hipSuccess) {
+            h->kclasses[u.first].total_ms += ms;
+            h->kclasses[u.first].launches += 1;
+        }
+    }
+    h->ev_used.clear();
+    h->ev_next = 0;
+}
+
+}  // namespace
