@@ -3,7 +3,7 @@
 // rankReveallingDecomposition, computeJacobiansAndResiduals}, marginalization.cpp:145-265,318-342,516-530).
 //
 //   A = sum J^T J, b = + sum J^T r over the blocks touching frame0, evaluated at zero deltas   (k_marg_*)
-//   Amm^+ by eigen-decomposition (lambda > cut), Ak = Arr - Arm Amm^+ Arm^T, bk likewise        (k_jacobi_*, k_gemm)
+//   Amm^+ by eigen-decomposition (lambda > cut), Ak = Arr - Arm Amm^+ Arm^T, bk likewise        (k_jacobi_*, k_mgemm)
 //   Ak = U Lambda U^T, J = Lambda^1/2 U^T, r0 = -Lambda^-1/2 U^T bk                             (k_jacobi_*, k_marg_prior)
 //
 // Eigen-solver: one-sided (Hestenes) Jacobi on the rows of G = A (symmetric, so rows = columns) with the
@@ -86,127 +86,18 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi_step(double* __restrict_
 // (no accumulation of rotations). On the rank-deficient, 10-decades-graded Schur complements of a marginalisation this takes
 // 9-10 sweeps where Jacobi on A itself takes 30+ (profiled on the config-3 problem).
 
-// Pivoted Cholesky in panels of PCH_NB columns (the LAPACK dpstrf scheme): the panel kernel (ONE workgroup - every step
-// needs the arg max of the remaining diagonal) picks the pivot, applies the symmetric swap to the trailing matrix S and to
-// the rows of G = L^T written so far, and forms row k of G from row k of S minus the contributions of the CURRENT panel's
-// rows only (<= 31 terms); the rank-PCH_NB update of the whole trailing matrix is k_pchol_syrk on all CUs. (One workgroup
-// doing the full left-looking dot products is bound by the L2 bandwidth of a single CU: 20 ms at n = 915 against 3.)
+// Pivoted Cholesky in panels (the LAPACK dpstrf scheme): a panel kernel (ONE workgroup - every step needs the arg max of the
+// remaining diagonal) picks the pivots and forms the panel's rows of G = L^T from the rows of S minus the contributions of the
+// CURRENT panel's rows only; the rank-NB update of the whole trailing matrix runs on all CUs (k_pchol_syrk_full / k_pchol_syrk_mma).
+// (One workgroup doing the full left-looking dot products is bound by the L2 bandwidth of a single CU: 20 ms at n = 915 against 3.)
 // S: n x n symmetric working copy (both triangles kept current), G: n x n row-major output, dg: remaining diagonal,
-// piv: permutation, ctl[0] = rank once the factorisation has stopped (else -1), ctl[1] = tau (as double bits in dctl).
+// ctl[0] = rank once the factorisation has stopped (else -1), dctl[0] = tau.
 constexpr int PCH_THREADS = 1024;
 constexpr int PCH_MAXN = 2048;
-constexpr int PCH_NB = 32;
 constexpr double PCH_THETA = 0.1;    // relaxed pivoting: a pivot is at least this fraction of the largest remaining diagonal
 constexpr int PCH_STRICT_TAIL = 32;   // relaxed pivoting (k_pchol_panel_rx): the last indices are pivoted one arg max at a time
-__global__ __launch_bounds__(PCH_THREADS) void k_pchol_panel(double* __restrict__ S, int n, double* __restrict__ G, int* __restrict__ piv,
-                                                             double* __restrict__ dg, int* __restrict__ ctl, double* __restrict__ dctl, int k0, double tau_rel) {
-    __shared__ double d[PCH_MAXN];
-    __shared__ double lk[PCH_NB];         // G[c][k] of the current panel's rows
-    __shared__ int pv[PCH_MAXN];
-    __shared__ double wmax[PCH_THREADS / 64];
-    __shared__ int widx[PCH_THREADS / 64];
-    __shared__ int s_j;
-    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
-    if (ctl[0] >= 0) return;              // the factorisation stopped in an earlier panel
-    for (int i = tid; i < n; i += PCH_THREADS) {
-        if (k0 == 0) { d[i] = S[(size_t)i * n + i]; pv[i] = i; } else { d[i] = dg[i]; pv[i] = piv[i]; }
-    }
-    __syncthreads();
-    if (k0 == 0 && tid == 0) { double m = 0.0; for (int i = 0; i < n; i++) m = fmax(m, d[i]); dctl[0] = tau_rel >= 0.0 ? tau_rel * m : -tau_rel; }
-    __syncthreads();
-    const double tau = dctl[0];
-    int rank = -1;
-    const int k1 = min(n, k0 + PCH_NB);
-    for (int k = k0; k < k1; k++) {
-        double best = -1.0; int bi = k;
-        for (int i = k + tid; i < n; i += PCH_THREADS) if (d[i] > best) { best = d[i]; bi = i; }
-        const double wm = wave_max(best);
-        const unsigned long long who = __ballot(best == wm);
-        const int src = __ffsll((long long)who) - 1;
-        const int wi = __builtin_amdgcn_readlane(bi, src);
-        if (ln == 0) { wmax[wv] = wm; widx[wv] = wi; }
-        __syncthreads();
-        if (tid == 0) {
-            double m = wmax[0]; int j = widx[0];
-            for (int q = 1; q < PCH_THREADS / 64; q++) if (wmax[q] > m) { m = wmax[q]; j = widx[q]; }
-            s_j = (m > tau && m > 0.0) ? j : -1;
-        }
-        __syncthreads();
-        const int j = s_j;
-        if (j < 0) { rank = k; break; }
-        if (j != k) {
-            // symmetric swap k <-> j of S (rows, then columns), the same column swap in the rows of G written so far
-            for (int i = tid; i < n; i += PCH_THREADS) { const double a = S[(size_t)k * n + i], b = S[(size_t)j * n + i]; S[(size_t)k * n + i] = b; S[(size_t)j * n + i] = a; }
-            __syncthreads();
-            for (int i = tid; i < n; i += PCH_THREADS) { const double a = S[(size_t)i * n + k], b = S[(size_t)i * n + j]; S[(size_t)i * n + k] = b; S[(size_t)i * n + j] = a; }
-            for (int c = tid; c < k; c += PCH_THREADS) { double* row = G + (size_t)c * n; const double a = row[k], b = row[j]; row[k] = b; row[j] = a; }
-            if (tid == 0) { const double t = d[k]; d[k] = d[j]; d[j] = t; const int q = pv[k]; pv[k] = pv[j]; pv[j] = q; }
-            __syncthreads();
-        }
-        if (tid < k - k0) lk[tid] = G[(size_t)(k0 + tid) * n + k];
-        __syncthreads();
-        const double lkk = sqrt(d[k]);
-        const double inv = 1.0 / lkk;
-        const int np = k - k0;
-        double* rowk = G + (size_t)k * n;
-        for (int i = tid; i < n; i += PCH_THREADS) {
-            double v = 0.0;
-            if (i > k) {
-                double s0 = S[(size_t)k * n + i];
-                for (int c = 0; c < np; c++) s0 -= G[(size_t)(k0 + c) * n + i] * lk[c];
-                v = s0 * inv;
-                d[i] -= v * v;
-            } else if (i == k) v = lkk;
-            rowk[i] = v;
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < n; i += PCH_THREADS) { dg[i] = d[i]; piv[i] = pv[i]; }
-    if (rank < 0 && k1 == n) rank = n;
-    if (rank >= 0) {
-        for (int c = rank; c < n; c++) for (int i = tid; i < n; i += PCH_THREADS) G[(size_t)c * n + i] = 0.0;
-        if (tid == 0) ctl[0] = rank;
-    }
-}
 
-// trailing update after a panel: S[i][j] -= sum_{c in panel} G[c][i] G[c][j] for i, j >= k1 (both triangles), 64 x 64 tiles
-__global__ __launch_bounds__(256) void k_pchol_syrk(double* __restrict__ S, int n, const double* __restrict__ G, const int* __restrict__ ctl, int k0) {
-    if (ctl[0] >= 0) return;
-    const int k1 = k0 + PCH_NB;
-    __shared__ double Ai[PCH_NB][64], Aj[PCH_NB][64];
-    const int ti = k1 + blockIdx.y * 64, tj = k1 + blockIdx.x * 64;
-    for (int e = threadIdx.x; e < PCH_NB * 64; e += 256) {
-        const int c = e / 64, x = e % 64;
-        Ai[c][x] = ti + x < n ? G[(size_t)(k0 + c) * n + ti + x] : 0.0;
-        Aj[c][x] = tj + x < n ? G[(size_t)(k0 + c) * n + tj + x] : 0.0;
-    }
-    __syncthreads();
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 4 x 4 micro-tile per thread
-    double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) acc[a][b] = 0.0;
-#pragma unroll 4
-    for (int c = 0; c < PCH_NB; c++) {
-        double vi[4], vj[4];
-#pragma unroll
-        for (int a = 0; a < 4; a++) { vi[a] = Ai[c][ty * 4 + a]; vj[a] = Aj[c][tx * 4 + a]; }
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) acc[a][b] += vi[a] * vj[b];
-    }
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int i = ti + ty * 4 + a, j = tj + tx * 4 + b;
-            if (i < n && j < n) S[(size_t)i * n + j] -= acc[a][b];
-        }
-}
-
-// The same factorisation WITHOUT data movement (the version used): the permutation stays implicit - G is stored by ORIGINAL
+// The factorisation moves NO data (no symmetric swaps): the permutation stays implicit - G is stored by ORIGINAL
 // column index (A = G^T G needs no permutation at all), a pivoted index just drops out of the arg max and gets zeros in the
 // later rows. Thread i owns index i (i + 1024 for n > 1024): its remaining diagonal, its "pivoted" flag and its entries of
 // the current panel's rows live in registers, so a column costs two barriers, the broadcast of the pivot's panel entries
@@ -877,9 +768,9 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi_mma(double* __restrict__
     JM_TS(7);
 }
 
-// eigen-pairs from the orthogonalised rows: lambda_i = |g_i|^2, v_i = g_i / |g_i| scattered back through the pivoting
+// eigen-pairs from the orthogonalised rows (stored by original column index): lambda_i = |g_i|^2, v_i = g_i / |g_i|
 // (rows >= rank: lambda = 0, v = 0 - they are below every cut and only ever multiplied by zero)
-__global__ __launch_bounds__(JAC_THREADS) void k_eig_from_rows(const double* __restrict__ G, const int* __restrict__ piv, const int* __restrict__ rank, int n,
+__global__ __launch_bounds__(JAC_THREADS) void k_eig_from_rows(const double* __restrict__ G, const int* __restrict__ rank, int n,
                                                                double* __restrict__ V, double* __restrict__ ev) {
     __shared__ double sh[4];
     const int i = blockIdx.x;
@@ -889,7 +780,7 @@ __global__ __launch_bounds__(JAC_THREADS) void k_eig_from_rows(const double* __r
     s = block_sum_256(s, sh);
     const bool live = i < *rank && s > 0.0;
     const double inv = live ? 1.0 / sqrt(s) : 0.0;
-    for (int k = threadIdx.x; k < n; k += JAC_THREADS) V[(size_t)i * n + (piv ? piv[k] : k)] = live ? g[k] * inv : 0.0;
+    for (int k = threadIdx.x; k < n; k += JAC_THREADS) V[(size_t)i * n + k] = live ? g[k] * inv : 0.0;
     if (threadIdx.x == 0) ev[i] = live ? s : 0.0;
 }
 
@@ -911,26 +802,6 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi_eigenvalues(const double
     for (int k = threadIdx.x; k < n; k += JAC_THREADS) s += G[(size_t)i * n + k] * V[(size_t)i * n + k];
     s = block_sum_256(s, sh);
     if (threadIdx.x == 0) ev[i] = s;
-}
-
-// C[i][j] = beta C[i][j] + alpha sum_k A(i,k) B(k,j) with arbitrary strides (covers every transpose); 16x16 tiles.
-__global__ __launch_bounds__(256) void k_gemm(double* C, long long ldc, const double* A, long long sai, long long sak,
-                                              const double* B, long long sbk, long long sbj, int M, int N, int K, double alpha,
-                                              double beta) {
-    __shared__ double As[16][17], Bs[16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int i = blockIdx.y * 16 + ty, j = blockIdx.x * 16 + tx;
-    double acc = 0.0;
-    for (int k0 = 0; k0 < K; k0 += 16) {
-        const int ka = k0 + tx, kb = k0 + ty;
-        As[ty][tx] = (i < M && ka < K) ? A[(size_t)i * sai + (size_t)ka * sak] : 0.0;
-        Bs[ty][tx] = (kb < K && j < N) ? B[(size_t)kb * sbk + (size_t)j * sbj] : 0.0;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 16; k++) acc += As[ty][k] * Bs[k][tx];
-        __syncthreads();
-    }
-    if (i < M && j < N) C[(size_t)i * ldc + j] = (beta == 0.0 ? 0.0 : beta * C[(size_t)i * ldc + j]) + alpha * acc;
 }
 
 // ---- FP64 matrix-core GEMM (round 4) -----------------------------------------------------------------------------------
@@ -979,7 +850,7 @@ __device__ __forceinline__ void mgemm_tile(double* __restrict__ C, long long ldc
         }
 }
 
-// C[i][j] = beta C[i][j] + alpha sum_k A(i,k) B(k,j), same calling convention as k_gemm; grid (ceil(N/64), ceil(M/64))
+// C[i][j] = beta C[i][j] + alpha sum_k A(i,k) B(k,j) with arbitrary element strides (covers every transpose); grid (ceil(N/64), ceil(M/64))
 __global__ __launch_bounds__(256) void k_mgemm(double* C, long long ldc, const double* A, long long sai, long long sak, const double* B, long long sbk,
                                                long long sbj, int M, int N, int K, double alpha, double beta) {
     __shared__ double As[64][17], Bs[64][17];
@@ -1411,12 +1282,7 @@ __global__ __launch_bounds__(JAC_THREADS) void k_marg_prior(const double* V, con
 // Everything is computed from the dense prior J = Lambda^1/2 U^T: lambda_c = |J_c|^2, U[:,c] = J_c / sqrt(lambda_c),
 // Sigma = Lambda^-1, so the covariance of an NFR factor with (sparse) Jacobian J_f is
 //   cov = (J_f U) Sigma (J_f U)^T = sum_c w_c w_c^T,  w_c = Jsel J_c[cidx] / lambda_c.
-struct NfrSpec {
-    int rows, cols;
-    int cidx[15];
-    double Jsel[225];  // rows x cols row-major
-};
-
+// (k_nfr_cov_z below, from Z with Z^T Z = Sigma_k.)
 __global__ __launch_bounds__(JAC_THREADS) void k_row_norm2(const double* J, int nf, int n, double* lam) {
     __shared__ double sh[4];
     const int c = blockIdx.x;
@@ -1426,33 +1292,7 @@ __global__ __launch_bounds__(JAC_THREADS) void k_row_norm2(const double* J, int 
     if (threadIdx.x == 0) lam[c] = s;
 }
 
-// one workgroup per factor: S[f] (15 x 15 slot, rows x rows used) = sum_c w_c w_c^T
-__global__ __launch_bounds__(JAC_THREADS) void k_nfr_cov(const double* J, int nf, int n, const double* lam, const NfrSpec* specs, double* S) {
-    __shared__ double acc[225];
-    const NfrSpec& sp = specs[blockIdx.x];
-    const int rows = sp.rows, cols = sp.cols;
-    for (int i = threadIdx.x; i < 225; i += JAC_THREADS) acc[i] = 0.0;
-    __syncthreads();
-    for (int c = threadIdx.x; c < nf; c += JAC_THREADS) {
-        const double il = 1.0 / lam[c];
-        double u[15], w[15];
-        for (int k = 0; k < cols; k++) u[k] = J[(size_t)c * n + sp.cidx[k]];
-        for (int a = 0; a < rows; a++) {
-            double s = 0.0;
-            for (int k = 0; k < cols; k++) s += sp.Jsel[a * cols + k] * u[k];
-            w[a] = s * il;
-        }
-        for (int a = 0; a < rows; a++)
-            for (int b = 0; b <= a; b++) atomic_add_f64(&acc[a * 15 + b], w[a] * w[b]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < rows * rows; i += JAC_THREADS) {
-        const int a = i / rows, b = i - a * rows;
-        S[(size_t)blockIdx.x * 225 + i] = a >= b ? acc[a * 15 + b] : acc[b * 15 + a];
-    }
-}
-
-// Round 4: the same covariances from Z with Z^T Z = Sigma_k (either form of the prior), compact factor descriptions — the
+// Round 4: the covariances from Z with Z^T Z = Sigma_k (either form of the prior), compact factor descriptions — the
 // selector matrices of a sparsification come from a table of at most four shapes (IMUPriordx 15 x 15, PoseToLandmark 3 x 9,
 // identity 3 x 3, [I -I] 3 x 6) instead of 225 doubles per factor: cov_f = (Jsel Z[:, cidx]^T)(..)^T, packed rows x rows at out_off.
 struct NfrSpecC {

@@ -12,9 +12,6 @@
 
 namespace {
 
-// ba_capi.hip: the wide-panel factorisation, shared with marginalisation
-void launch_wfac(sadvio_ba_handle* h, double* A, long long ld, int N, double* y, double* Lx, double* Ltw, double* M, int* info, const int* skip, long long* dbg);
-
 DevPtrs make_ptrs(sadvio_ba_handle* h, const SolveOpts& o, int state_stride) {
     DevPtrs P{};
     P.win = h->d_win.p; P.tiles = h->d_tiles.p;
@@ -57,6 +54,26 @@ DevPtrs make_ptrs(sadvio_ba_handle* h, const SolveOpts& o, int state_stride) {
     P.o = o;
     return P;
 }
+// Wide-panel factorisation (dense_chol.h): k_wchol_diag16 on the first 96 columns, then one k_wchol_step per further 96. The lower
+// triangle of the N x N matrix A (leading dimension ld) is destroyed, y rides along as its right-hand side (-> L^-1 y). Lx (N x N,
+// leading dimension ld): the panels below the diagonal blocks, out of place; Ltw: ceil(N / 96) * WD_LT doubles, the diagonal blocks'
+// tiles; M: ceil(N / 96) 96 x 96 inverses of the diagonal blocks for k_wchol_backstep (null: factor only). dbg: phase stamps of the
+// second k_wchol_step (SADVIO_DEBUG & 4096). Shared with marginalisation (marg_driver.h: run_wfac).
+void launch_wfac(sadvio_ba_handle* h, double* A, long long ld, int N, double* y, double* Lx, double* Ltw, double* M, int* info, const int* skip, long long* dbg) {
+    const int nsteps = (N + WD - 1) / WD;
+    const size_t lds_d = sizeof(double) * wd16_lds_doubles() + 64, lds_st = sizeof(double) * wdstep_lds_doubles() + 64;
+    (void)hipFuncSetAttribute((const void*)k_wchol_diag16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
+    (void)hipFuncSetAttribute((const void*)k_wchol_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_st);
+    hipLaunchKernelGGL(k_wchol_diag16, dim3(1), dim3(SOLVE_THREADS), lds_d, h->stream, A, ld, y, (double*)nullptr, N, 0, info, skip, Ltw);
+    for (int st = 0; st + 1 < nsteps; st++) {
+        const int c0 = st * WD, m = N - (c0 + WD);
+        const int nt = (m + CH_TS - 1) / CH_TS;
+        hipLaunchKernelGGL(k_wchol_step, dim3(nt * (nt + 1) / 2 + 2), dim3(SOLVE_THREADS), lds_st, h->stream, A, ld, Lx, y,
+                           Ltw + (size_t)st * WD_LT, Ltw + (size_t)(st + 1) * WD_LT, M ? M + (size_t)st * WD * WD : nullptr,
+                           M ? M + (size_t)(st + 1) * WD * WD : nullptr, N, c0, info, skip, st == 1 ? dbg : nullptr);
+    }
+}
+
 // The reduced system of an out-of-LDS window (N_p > MAX_LDS_NP) is factored and solved in HBM by one of five routes (dense_chol.h),
 // chosen once per solve call (BigPlan::choose).
 enum class BigRoute {

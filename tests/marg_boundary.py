@@ -1,4 +1,4 @@
-"""Marginalisation windows sized to sit on the route thresholds of sadvio_ba_marginalize (ba_capi.hip: run_pchol, run_jacobi_rows,
+"""Marginalisation windows sized to sit on the route thresholds of sadvio_ba_marginalize (marg_driver.h: run_pchol, run_jacobi_rows,
 run_jacobi, the Amm route) and of the dense prior kernels (kernels.h: k_prior_r / k_prior_m), and the float64 LAPACK reference of
 their prior: the oracle's A = sum J^T J, b = sum J^T r (oracle.marg_information, computeInformationAndGradient), then the Schur
 complement and the eigen-cut of marginalization.cpp:213-265,318-342,516-530 with np.linalg.eigh (twin.schur_prior, f64). The oracle's

@@ -120,7 +120,7 @@ def _pivoted_cholesky(A):
 
 
 def test_small_eigenvalue_from_the_trailing_pivot():
-    """Round 6 (ba_capi.hip: refine_rank_by_eigenvalue): the reference cuts the prior's rank by EIGENVALUE (lambda > 1e-12,
+    """Round 6 (marg_driver.h: refine_rank_by_eigenvalue): the reference cuts the prior's rank by EIGENVALUE (lambda > 1e-12,
     marginalization.cpp:318-342); a rank-revealing Cholesky sees pivots. With G in pivot order and x = G^-1 e_last, 1 / |x|^2 — the
     Rayleigh quotient of the near-null vector, d_last / (1 + |w|^2) — is the smallest eigenvalue to O(d / gap), with RELATIVE accuracy
     on a graded matrix whose double-precision eigen-decomposition only returns noise of size eps |A|: checked against mpmath at 50

@@ -105,21 +105,19 @@ def test_device_prior_feeds_the_next_solve(backend_cls, oracle_lib):
 
 
 @pytest.mark.parametrize("n_keep", [300, 400])
-@pytest.mark.parametrize("path", ["default", "swap_b4"])
-def test_large_prior_against_oracle_fixture(backend_cls, monkeypatch, n_keep, path):
+@pytest.mark.parametrize("path", ["default"])
+def test_large_prior_against_oracle_fixture(backend_cls, n_keep, path):
     """Config-3 sized priors against the ORACLE (tests/golden/config3_marg_ref.npz: oracle/marg.c on the same window,
-    marginalization.cpp:213-265,318-342,516-530): n = 915 takes the MFMA block Jacobi (k_jacobi_mma) + the register-resident
-    pivoted Cholesky (k_pchol_panel_np); n = 1 215 > 1 024 two indices per thread in the Cholesky and the 4-row block Jacobi;
-    `swap_b4` forces the data-moving Cholesky + 4-row Jacobi they replaced. Both must reproduce the oracle's Ak (diagonal,
-    spectrum, 32 probe products, every 32nd row), its J^T J, J^T r0 and -bk, with orthogonal rows."""
+    marginalization.cpp:213-265,318-342,516-530): n = 915 takes the relaxed pivoted Cholesky with one index per thread
+    (k_pchol_panel_rx<1, 32>) + the MFMA block Jacobi (k_jacobi_mma); n = 1 215 > 1 024 two indices per thread in the Cholesky
+    (k_pchol_panel_rx<2, 16>) and the VALU block Jacobi (k_jacobi_block<8>). Both must reproduce the oracle's Ak (diagonal,
+    spectrum, 32 probe products, every 32nd row), its J^T J, J^T r0 and -bk, with orthogonal rows. (`path` has one value: the
+    routes that `swap_b4` forced are retired.)"""
     import os
     from golden_util import GOLDEN, _window_checksum, check_prior_against_fixture, config3_marg_case
     z = np.load(os.path.join(GOLDEN, "config3_marg_ref.npz"))
     w, args = config3_marg_case(n_keep)
     assert _window_checksum(w) == str(z[f"k{n_keep}_checksum"]), "generator drift: regenerate tests/golden/config3_marg_ref.npz"
-    if path == "swap_b4":
-        monkeypatch.setenv("SADVIO_PCHOL_SWAP", "1")
-        monkeypatch.setenv("SADVIO_JACOBI_B4", "1")
     be = backend_cls(device=0)
     be.set_windows([w])
     g = be.marginalize(0, **args)

@@ -1,4 +1,4 @@
-"""GPU parity of sadvio_ba_marginalize on both sides of every size threshold of its routes (ba_capi.hip: run_pchol, run_jacobi_rows,
+"""GPU parity of sadvio_ba_marginalize on both sides of every size threshold of its routes (marg_driver.h: run_pchol, run_jacobi_rows,
 run_jacobi, the Amm route, the Cholesky form's limit), against the float64 LAPACK reference of tests/marg_boundary.py. The route a
 call took is invisible in its result; it is read from the sweep counts, marg_stats and the SADVIO_DEBUG=16384 lines ("block jacobi
 n ..." for the Cholesky-preconditioned block Jacobi, "jacobi n ..." for the plain one), which the handle reads once at creation."""

@@ -186,7 +186,7 @@ def check_sequence(log, stats, sides, tag, min_unpivoted):
                f"drift of the two trajectories after {len(log)} steps {log[-1]['drift']:.2e}")
     # STRICT bars on every step: the device decides the prior's rank by the reference's criterion - eigenvalues
     # above 1e-12 (marginalization.cpp:318-342), evaluated with relative accuracy on the trailing pivots of the rank-revealing Cholesky
-    # (ba_capi.hip: refine_rank_by_eigenvalue) - and so keeps the same directions as the oracle's eigen-decomposition, also at the two
+    # (marg_driver.h: refine_rank_by_eigenvalue) - and so keeps the same directions as the oracle's eigen-decomposition, also at the two
     # steps of the VIO dense sequence where an eigenvalue lies below the cut (exact values 3e-23 and 1.1e-14:
     # profiles/r06_rank_arbiter.txt). Round 5 ran this test with a loosened bar after step 13 (228 against 227 directions).
     for r in log:
