@@ -567,6 +567,43 @@ int sadvio_ba_nofov_scale(sadvio_ba_handle *h, const sadvio_nofov_problem *prob,
                           sadvio_solve_summary *summary, sadvio_nofov_result *res, double *lmk_delta3, double *gate_norm,
                           int32_t *inlier);
 
+/* ---- marginal covariances of a solved window ----
+ * No reference counterpart as one call; the quantities the pipeline is written to consume: Sigma_k of the NFR sparsification
+ * (marginalization.cpp:259-262), covdT of the ESKF (ESKFEstimator.cpp:180), the 6 x 6 covariance of an odometry message.
+ * Evaluated for window `w` after sadvio_ba_solve, at the solve's final accepted state (the linearisation origin composed with the
+ * deltas get_deltas returns): H = J^T J over every residual block of the window — Gauss-Newton, no LM damping, no Jacobi scaling;
+ * the visual factors under HuberLoss(opts.huber_a) of that solve, corrected as the solve corrects them (ceres::Covariance applies
+ * the loss by default) — restricted to the free parameters; Sigma = H^-1, of which only the blocks asked for are formed, by the
+ * solve's own elimination: S = H_pp - sum_l H_pl H_ll^-1 H_lp over the eliminated landmarks, Sigma_pp = S^-1 (unpivoted Cholesky,
+ * every pivot tested), Sigma_ll = H_ll^-1 + W_l Sigma_pp W_l^T with W_l = H_ll^-1 H_lp.
+ * Coordinates: the library's delta coordinates — a key-frame's block is over (w, t) of T_f_w = T_f_w0 * (exp(w), t)
+ * (geometry.h:198-203) followed, with has_imu, by v, ba, bg; a landmark's over its additive delta (geometry.h:205-210).
+ * sadvio_optimizer.hpp maps a key-frame block to the covariance of T_w_f in the order of a ROS pose message. */
+typedef struct sadvio_cov_request {
+    int32_t n_kf;
+    const int32_t *kf;      /* [n_kf] key-frame indices of the window */
+    int32_t n_pair;
+    const int32_t *pair_a;  /* [n_pair] cross blocks Sigma(a, b) between two key-frames: rows a, columns b */
+    const int32_t *pair_b;  /* [n_pair] */
+    int32_t n_lmk;          /* -1: every landmark of the window, in its order (`lmk` is not read) */
+    const int32_t *lmk;     /* [n_lmk] landmark indices of the window */
+} sadvio_cov_request;
+
+/* kf_cov: [n_kf][d][d], d = 6 (15 with has_imu), row-major, state order pose6 | v3 | ba3 | bg3; pair_cov: [n_pair][d][d];
+ * lmk_cov: [n_lmk][9]. A kf_const key-frame or lmk_const landmark has no row or column in H: its blocks are all zeros. A landmark
+ * kept in the reduced system (prior-kept, chained) has its block taken from Sigma_pp. A landmark whose H_ll is not positive
+ * definite (a single observation; a pivot within 64 ulps of its diagonal entry) is left out of H with its observations, gets nine
+ * NaNs and is counted in n_lmk_singular (among the landmarks asked for); the call still returns SADVIO_OK.
+ * Any output pointer may be NULL. The call waits for its own results; the solve's deltas, summary, trace and the handle's prior are
+ * left untouched (a get_deltas after it returns the same bits as before it), and two calls return the same bits (every sum is
+ * taken in a fixed order: no floating-point atomics).
+ * Returns SADVIO_E_STATE before a solve or inside a begin_update bracket; SADVIO_E_INVALID_ARG for an index out of range, for a
+ * window sharded over several GPUs, a window with line landmarks, or a batch the throughput kernels solved (the error text says
+ * which), and for a reduced system of 2047 columns or more; SADVIO_E_NOT_USABLE when the factorisation of S meets a pivot that is
+ * not safely positive (gauge not fixed: no constant key-frame and no prior) — the outputs are then untouched. */
+int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_request *rq, double *kf_cov, double *pair_cov,
+                         double *lmk_cov, int32_t *n_lmk_singular);
+
 /* Average device time in microseconds per kernel class since the last set_windows, measured
  * with hipEvents on the handle's stream (cfg.profile_kernels = 1). `names` receives pointers
  * to static strings. Returns the number of classes written (<= cap). */

@@ -16,6 +16,7 @@
 #include <stdexcept>
 #include <array>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "sadvio_ba.h"
@@ -160,6 +161,44 @@ inline Pose pose_inv(const Pose& a) {
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) c.R[3 * i + j] = a.R[3 * j + i];
     for (int i = 0; i < 3; i++) c.t[i] = -(c.R[3 * i] * a.t[0] + c.R[3 * i + 1] * a.t[1] + c.R[3 * i + 2] * a.t[2]);
     return c;
+}
+
+// Covariance of a key-frame's pose for a consumer that speaks T_w_f (a ROS odometry message: geometry_msgs/PoseWithCovariance,
+// parameters in the order x, y, z, rotation about the fixed X, Y, Z axes). The library's 6 x 6 block (sadvio_ba_covariance) is over
+// the delta coordinates (w, tau) of T_f_w, composed on the right (geometry.h:198-203; parametersBlock.hpp:34-37):
+//     T_f_w' = T_f_w (exp(w), tau):   R' = R exp(w),   t' = R tau + t.
+// With T_w_f = T_f_w^-1 = (Q, c), Q = R^T, c = -R^T t, the same perturbation reads
+//     Q' = exp(w)^T R^T = exp(-w) Q,          c' = -Q' t' = -exp(-w) (tau + R^T t) = exp(-w) (c - tau).
+// Orientation error about the fixed (world) axes, Q' = exp(theta) Q:  theta = -w (exactly). Position error in the world:
+//     dc = c' - c = exp(-w) (c - tau) - c = [c]x w - tau + O(2)        (exp(-w) c = c - w x c = c + [c]x w to first order).
+// So (dc, theta) = Jm (w, tau) with  Jm = [ [c]x  -I ; -I  0 ]  and  cov_ros = Jm cov_wt Jm^T. cov_wt36 and cov_ros36 are row-major
+// and may not alias. T_f_w is the key-frame's pose AFTER the solve's write-back (the state the covariance was evaluated at).
+inline void pose_covariance_jacobian(const Pose& T_f_w, double* Jm36) {
+    const Pose T_w_f = pose_inv(T_f_w);
+    const double* c = T_w_f.t;
+    const double Cx[9] = {0, -c[2], c[1], c[2], 0, -c[0], -c[1], c[0], 0};
+    for (int i = 0; i < 36; i++) Jm36[i] = 0.0;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Jm36[6 * i + j] = Cx[3 * i + j];
+        Jm36[6 * i + 3 + i] = -1.0;
+        Jm36[6 * (3 + i) + i] = -1.0;
+    }
+}
+inline void pose_covariance_ros(const Pose& T_f_w, const double* cov_wt36, double* cov_ros36) {
+    double Jm[36], T[36];
+    pose_covariance_jacobian(T_f_w, Jm);
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double v = 0.0;
+            for (int k = 0; k < 6; k++) v += Jm[6 * i + k] * cov_wt36[6 * k + j];
+            T[6 * i + j] = v;
+        }
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double v = 0.0;
+            for (int k = 0; k < 6; k++) v += T[6 * i + k] * Jm[6 * j + k];
+            cov_ros36[6 * i + j] = v;
+        }
 }
 
 // The problem of AngularAdjustmentCERESAnalytic::landmarkOptimizationNoFov (AngularAdjustmentCERESAnalytic.cpp:775-851) in the
@@ -493,6 +532,44 @@ class HipOptimizer {
         return true;
     }
 
+    // Marginal covariances of the last window solve of this optimizer (sadvio_ba_covariance), addressed by the snapshot's ids:
+    // frame_ids -> kf_cov [n][d][d] (d = block_dim(): 6, or 15 = pose6 | v | ba | bg after a VIO solve), frame_pairs -> pair_cov
+    // [n][d][d] (rows first, columns second), landmark_ids -> lmk_cov [n][9]; any output may be null. Blocks are over the library's
+    // delta coordinates at the written-back state; pose_covariance_ros maps a key-frame's leading 6 x 6 block to T_w_f. A frame that
+    // was constant in the solve or a landmark the solve held constant gives zeros; a landmark with a rank-deficient H_ll gives NaN and
+    // is counted in n_lmk_singular. Returns false (last_error says why) for an id the last window did not hold, when no window solve
+    // precedes the call (a chi2-gated solve that re-uploaded its window counts as none), and when the gauge is not fixed.
+    bool covariance(const std::vector<int64_t>& frame_ids, const std::vector<std::pair<int64_t, int64_t>>& frame_pairs,
+                    const std::vector<int64_t>& landmark_ids, std::vector<double>* kf_cov, std::vector<double>* pair_cov,
+                    std::vector<double>* lmk_cov, int* n_lmk_singular = nullptr) {
+        auto find = [](const std::vector<int64_t>& ids, int64_t id) {
+            for (size_t i = 0; i < ids.size(); i++) if (ids[i] == id) return (int32_t)i;
+            return (int32_t)-1;
+        };
+        std::vector<int32_t> kf, pa, pb, lm;
+        for (int64_t id : frame_ids) kf.push_back(find(_cov_kf_id, id));
+        for (const auto& pr : frame_pairs) { pa.push_back(find(_cov_kf_id, pr.first)); pb.push_back(find(_cov_kf_id, pr.second)); }
+        for (int64_t id : landmark_ids) lm.push_back(find(_cov_lmk_id, id));
+        for (const std::vector<int32_t>* v : {&kf, &pa, &pb, &lm})
+            for (int32_t i : *v) if (i < 0) { _err = "covariance: an id is not part of the last solved window"; return false; }
+        const size_t dd = (size_t)_cov_dim * _cov_dim;
+        std::vector<double> kc(dd * kf.size()), pc(dd * pa.size()), lc(9 * lm.size());
+        sadvio_cov_request rq{};
+        rq.n_kf = (int32_t)kf.size(); rq.kf = kf.data();
+        rq.n_pair = (int32_t)pa.size(); rq.pair_a = pa.data(); rq.pair_b = pb.data();
+        rq.n_lmk = (int32_t)lm.size(); rq.lmk = lm.data();
+        int32_t ns = 0;
+        const int rc = sadvio_ba_covariance(_h, 0, &rq, kf_cov && !kf.empty() ? kc.data() : nullptr, pair_cov && !pa.empty() ? pc.data() : nullptr,
+                                            lmk_cov && !lm.empty() ? lc.data() : nullptr, &ns);
+        if (rc != SADVIO_OK) { _err = sadvio_ba_last_error(_h); return false; }
+        if (kf_cov) kf_cov->swap(kc);
+        if (pair_cov) pair_cov->swap(pc);
+        if (lmk_cov) lmk_cov->swap(lc);
+        if (n_lmk_singular) *n_lmk_singular = ns;
+        return true;
+    }
+    int block_dim() const { return _cov_dim; }   // 6 or 15: of the last window solve
+
     bool has_prior() const { return _prior.valid; }
     int prior_rows() const { return _prior.n_full; }
     int prior_cols() const { return _prior.n; }
@@ -755,6 +832,7 @@ class HipOptimizer {
         if (rc == SADVIO_OK) rc = sadvio_ba_solve(_h, &opt, &_sum);
         if (rc != SADVIO_OK && rc != SADVIO_E_NOT_USABLE) { _err = sadvio_ba_last_error(_h); return false; }   // state untouched
         if (rc == SADVIO_E_NOT_USABLE) return false;
+        _cov_kf_id = F.kf_id; _cov_lmk_id = F.lmk_id; _cov_dim = vio ? 15 : 6;   // what covariance() addresses
         std::vector<double> dpose(6 * (size_t)nkf), dl(3 * (size_t)std::max(F.w.n_lmk, 1)), dv(3 * (size_t)nkf), dba(3 * (size_t)nkf), dbg(3 * (size_t)nkf);
         if (sadvio_ba_get_deltas(_h, 0, dpose.data(), dl.data(), dv.data(), dba.data(), dbg.data()) != SADVIO_OK) { _err = sadvio_ba_last_error(_h); return false; }
         for (int i = 0; i < nkf; i++) {                                                  // AOptimizer.cpp:329-332
@@ -810,6 +888,8 @@ class HipOptimizer {
     std::vector<sadvio_sparse_prior> _sparse;   // the sparsified prior (indices of the window it was built on)
     std::vector<int64_t> _sparse_lmk_id;        // [2 k], [2 k + 1]: ids of lmk0 / lmk1 of factor k
     int64_t _sparse_kf_id = -1;
+    std::vector<int64_t> _cov_kf_id, _cov_lmk_id;   // ids of the last solved window, in its order
+    int _cov_dim = 6;
 };
 
 }  // namespace sadvio

@@ -115,6 +115,11 @@ class PriorInfoC(C.Structure):
     _fields_ = [("valid", C.c_int32), ("n_full", C.c_int32), ("n", C.c_int32), ("form", C.c_int32)]
 
 
+class CovRequestC(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("kf", _ip), ("n_pair", C.c_int32), ("pair_a", _ip), ("pair_b", _ip), ("n_lmk", C.c_int32),
+                ("lmk", _ip)]
+
+
 PRIOR_RESIDENT = -1
 # SADVIO_EIG_CUT_*: the C ABI's default (a zero-initialised request) is the reference's absolute 1e-12; this harness and the
 # oracle's wrapper default to "noise_floor" because the parity tests compare n_full, which only that mode makes reproducible
@@ -407,6 +412,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                       C.POINTER(ViInitResultC), _dp]
     lib.sadvio_ba_nofov_scale.argtypes = [C.c_void_p, C.POINTER(NoFovProblemC), C.POINTER(SolveOptions), C.POINTER(SolveSummary),
                                           C.POINTER(NoFovResultC), _dp, _dp, _ip]
+    if hasattr(lib, "sadvio_ba_covariance"):   # an older build loaded through SADVIO_BA_LIB (A/B measurements) does not export it
+        lib.sadvio_ba_covariance.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CovRequestC), _dp, _dp, _dp, _ip]
     lib.sadvio_ba_landmark_chi2.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, _dp, _ip]
     lib.sadvio_ba_get_kernel_times.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), _dp, _lp]
     lib.sadvio_ba_last_error.argtypes = [C.c_void_p]
@@ -739,6 +746,34 @@ class Backend:
             self._check(rc, "nofov_scale")
         return {"rc": rc, "summary": s, "lambda": float(r.lambda_), "usable": bool(r.usable), "scale_fixed": bool(r.scale_fixed),
                 "n_inliers": int(r.n_inliers), "lmk_delta": dl, "gate_norm": gn, "inlier": inl}
+
+    def covariance(self, w: int = 0, kf=None, pairs=None, lmk=None, raw_rc: bool = False):
+        """Marginal covariances of window w at the last solve's final state (sadvio_ba_covariance).
+        kf: key-frame indices -> "kf" [n, d, d] (d = 6, 15 with IMU states); pairs: (a, b) index pairs -> "pair" [n, d, d], the
+        cross blocks Sigma(a, b); lmk: landmark indices, or "all" -> "lmk" [n, 3, 3]. "n_lmk_singular": landmarks among them whose
+        H_ll is not positive definite (their block is NaN). raw_rc=True returns {"rc", "error"} for a refused call instead of
+        raising; the outputs are then untouched (NaN-free zeros as allocated here)."""
+        win = self.windows[w] if 0 <= w < len(self.windows) else self.windows[0]   # (an index out of range is the library's to refuse)
+        d = 15 if win.has_imu else 6
+        rq = CovRequestC()
+        ka = np.ascontiguousarray([] if kf is None else kf, dtype=np.int32).reshape(-1)
+        pr = np.ascontiguousarray([] if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        all_lmk = isinstance(lmk, str) and lmk == "all"
+        la = np.ascontiguousarray([] if (lmk is None or all_lmk) else lmk, dtype=np.int32).reshape(-1)
+        n_l = win.n_lmk if all_lmk else len(la)
+        rq.n_kf, rq.kf = len(ka), ka.ctypes.data_as(_ip)
+        rq.n_pair, rq.pair_a, rq.pair_b = len(pa), pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip)
+        rq.n_lmk, rq.lmk = (-1 if all_lmk else len(la)), la.ctypes.data_as(_ip)
+        kc = np.zeros((len(ka), d, d)); pc = np.zeros((len(pa), d, d)); lc = np.zeros((n_l, 3, 3))
+        ns = C.c_int32(0)
+        rc = self.lib.sadvio_ba_covariance(self.h, w, C.byref(rq), _ptr(kc) if len(ka) else _dp(), _ptr(pc) if len(pa) else _dp(),
+                                           _ptr(lc) if n_l else _dp(), C.byref(ns))
+        if rc != SADVIO_OK and raw_rc:
+            msg = self.lib.sadvio_ba_last_error(self.h)
+            return {"rc": rc, "error": msg.decode() if msg else "", "kf": kc, "pair": pc, "lmk": lc}
+        self._check(rc, "covariance")
+        return {"rc": rc, "kf": kc, "pair": pc, "lmk": lc, "n_lmk_singular": int(ns.value)}
 
     def kernel_times(self):
         cap = 32

@@ -1415,6 +1415,7 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
     h->fin.assign(h->h_final, h->h_final + n_win);
     h->deltas_cached = false;
     h->last_slots = plan.slots;
+    h->cov_huber_a = o.huber_a; h->cov_use_lm = plan.use_lm;
     h->solved = true;
     int rc = SADVIO_OK;
     for (int w = 0; w < n_win; w++) {
@@ -1740,6 +1741,20 @@ int sadvio_ba_nofov_scale(sadvio_ba_handle* h, const sadvio_nofov_problem* pb, c
     }
     if (!usable) h->err = S.termination == SADVIO_TERM_FAILURE ? "nofov_scale: no usable solution" : "nofov_scale: lambda outside [0.5, 1.5]";
     return usable ? SADVIO_OK : SADVIO_E_NOT_USABLE;
+}
+
+}  // extern "C"
+
+#include "cov_driver.h"   // below marg_driver.h: the inversion of S is the unpivoted Cholesky + triangular inverse of sparsify's route
+
+extern "C" {
+
+// ---- marginal covariances of a solved window (no reference counterpart as one call: Sigma_k of Marginalization::sparsifyVIO,
+//      marginalization.cpp:259-262, and covdT of the ESKF, ESKFEstimator.cpp:180, are what the pipeline consumes) ----
+int sadvio_ba_covariance(sadvio_ba_handle* h, int32_t w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov,
+                         int32_t* n_lmk_singular) {
+    if (!h) return SADVIO_E_INVALID_ARG;
+    return cov_run(h, w, rq, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
 }
 
 int sadvio_ba_set_window(sadvio_ba_handle* h, const sadvio_flat_window* window) { return sadvio_ba_set_windows(h, 1, window); }

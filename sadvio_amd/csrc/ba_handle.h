@@ -218,6 +218,13 @@ struct MargScratch {
     std::map<int, TriPlan> tri_plans;   // node tables of the triangular inverse, by padded size (m of Amm and n of the prior alternate)
 };
 
+// Work buffers of sadvio_ba_covariance (cov_driver.h), kept in the handle like MargScratch: an odometry consumer calls it once per key-frame.
+struct CovScratch {
+    DevBuf<double> ptab, hll, hinv, ent_w, ent_hpp, S, Sig, lout, V, Lx, G, Z;
+    DevBuf<int> status, ent_n, ent_col, step_of;
+    std::vector<double> h_sig, h_lout;
+};
+
 struct LineSetHost {   // deep copy of a sadvio_line_set
     std::vector<int64_t> id;
     std::vector<double> T, model, meas;
@@ -297,6 +304,9 @@ struct sadvio_ba_handle {
     std::vector<DensePriorHost> dprior_per_win;
     PriorState prior;   // the handle's own prior (sadvio_ba_marginalize leaves it here)
     MargScratch mg;
+    CovScratch cv;
+    double cov_huber_a = 0.0;   // huber_a of the last solve: sadvio_ba_covariance corrects the visual factors as that solve did
+    bool cov_use_lm = false;    // ... and whether the throughput kernels ran it (covariance is then refused)
     std::vector<SrcWin> src;                       // caller windows (deep copies)
     std::vector<std::vector<char>> sp_elim;        // per window, per sparse factor: handled as pseudo-observations
     std::vector<int> n_obs_user;                   // caller's observation count per window

@@ -1,0 +1,196 @@
+// cov_driver.h — the host side of sadvio_ba_covariance as named steps
+//   cov_check -> cov_routes -> cov_assemble -> cov_invert -> cov_landmarks -> cov_read_back
+// The kernels are cov_kernels.h's; the factorisation of S and the triangular inverse are marg_driver.h's (factor_unpivoted,
+// prior_build_Z: the route sadvio_ba_sparsify takes to Sigma_k = Ak^-1), called as they are. Nothing of the solve is touched: the
+// delta buffers, the final records, the trace and the handle's prior are read only; the work buffers are the handle's CovScratch
+// and, inside the two borrowed routines, MargScratch.
+// Part of the library's single translation unit (ba_capi.hip, which includes it below marg_driver.h); not a public header.
+#pragma once
+#include "ba_handle.h"
+#include "cov_kernels.h"
+#include "marg_driver.h"
+
+namespace {
+
+// Everything a call decides, behind cov_check: the steps read it.
+struct CovRoutes {
+    int cur = 0;            // delta buffer holding the final accepted state
+    bool pix = true;        // pixel (else angular) visual factor
+    int Np = 0;             // columns of the reduced system; 0: every key-frame constant, nothing kept — Sigma_ll = H_ll^-1
+    bool kept = false;      // landmarks in the reduced system (k_cov_kept)
+    bool dense = false;     // a dense prior is attached (k_cov_dense)
+    bool want_lmk = false;  // landmark blocks asked for (k_cov_lmk)
+    int G = 16;             // lanes per landmark of k_cov_lmk: 16 up to 8 free key-frames, else 64
+    int n_lmk_out = 0;      // landmark blocks written
+};
+
+// 1. State and arguments. Host work only.
+int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov) {
+    if (h->world > 1) { h->err = "covariance: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
+    if (h->defer) { h->err = "covariance between begin_update and commit_update"; return SADVIO_E_STATE; }
+    if (!h->solved) { h->err = "covariance before solve"; return SADVIO_E_STATE; }
+    if (w < 0 || w >= (int)h->wins.size()) { h->err = "covariance: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (!rq) { h->err = "covariance: null request"; return SADVIO_E_INVALID_ARG; }
+    const WinDev& d = h->wins[w].d;
+    if (d.line_end > d.line_begin) { h->err = "covariance: the window carries line landmarks"; return SADVIO_E_INVALID_ARG; }
+    if (h->cov_use_lm) { h->err = "covariance: the batch was solved by the throughput kernels"; return SADVIO_E_INVALID_ARG; }
+    if (rq->n_kf < 0 || rq->n_pair < 0 || rq->n_lmk < -1 || (rq->n_kf > 0 && !rq->kf) || (rq->n_pair > 0 && (!rq->pair_a || !rq->pair_b)) ||
+        (rq->n_lmk > 0 && !rq->lmk)) { h->err = "covariance: request out of range"; return SADVIO_E_INVALID_ARG; }
+    for (int i = 0; i < rq->n_kf; i++)
+        if (rq->kf[i] < 0 || rq->kf[i] >= d.n_kf) { h->err = "covariance: key-frame index out of range"; return SADVIO_E_INVALID_ARG; }
+    for (int i = 0; i < rq->n_pair; i++)
+        if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) { h->err = "covariance: key-frame index of a pair out of range"; return SADVIO_E_INVALID_ARG; }
+    for (int i = 0; i < rq->n_lmk; i++)
+        if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) { h->err = "covariance: landmark index out of range"; return SADVIO_E_INVALID_ARG; }
+    if (d.Np + 1 > PCH_MAXN) { h->err = "covariance: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
+    (void)lmk_cov;
+    return SADVIO_OK;
+}
+
+CovRoutes cov_routes(const sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov) {
+    const WinDev& d = h->wins[w].d;
+    CovRoutes R;
+    R.cur = h->fin[w].s.cur;
+    R.pix = h->factor_type == SADVIO_FACTOR_PIXEL;
+    R.Np = d.Np;
+    R.kept = d.kept_end > d.kept_begin;
+    R.dense = d.dp_n_full > 0;
+    R.n_lmk_out = rq->n_lmk < 0 ? d.n_lmk : rq->n_lmk;
+    R.want_lmk = lmk_cov != nullptr && R.n_lmk_out > 0;
+    R.G = d.n_free_kf <= 8 ? 16 : 64;
+    return R;
+}
+
+CovDev cov_dev(sadvio_ba_handle* h, int w, const CovRoutes& R) {
+    CovScratch& V = h->cv;
+    CovDev C{};
+    C.w = w; C.cur = R.cur; C.Np = R.Np; C.huber_a = h->cov_huber_a;
+    C.ptab = V.ptab.p; C.hll = V.hll.p; C.hinv = V.hinv.p; C.status = V.status.p; C.ent_n = V.ent_n.p;
+    C.ent_col = V.ent_col.p; C.ent_w = V.ent_w.p; C.ent_hpp = V.ent_hpp.p;
+    C.S = V.S.p; C.Sig = V.Sig.p; C.lout = V.lout.p;
+    return C;
+}
+
+// 2. Allocate; linearise at x*; S = H_pp - sum_l H_pl H_ll^-1 H_lp, full symmetric, in V.S
+int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
+    const WinDev& d = h->wins[w].d;
+    CovScratch& V = h->cv;
+    const size_t nl = (size_t)std::max(d.n_lmk, 1), no = (size_t)std::max(d.n_obs, 1), nn = (size_t)std::max(R.Np, 1) * std::max(R.Np, 1);
+    HIP_TRY(V.ptab.alloc((size_t)h->n_kf_tot * POSE_TAB));
+    HIP_TRY(V.hll.alloc(6 * nl)); HIP_TRY(V.hinv.alloc(6 * nl)); HIP_TRY(V.status.alloc(nl)); HIP_TRY(V.ent_n.alloc(nl)); HIP_TRY(V.lout.alloc(9 * nl));
+    HIP_TRY(V.ent_col.alloc(no)); HIP_TRY(V.ent_w.alloc(COV_ENT_W * no)); HIP_TRY(V.ent_hpp.alloc(COV_ENT_HPP * no));
+    HIP_TRY(V.S.alloc(nn)); HIP_TRY(V.Sig.alloc(nn));
+    HIP_TRY(hipMemsetAsync(V.S.p, 0, sizeof(double) * nn, h->stream));
+    SolveOpts so{};
+    so.huber_a = h->cov_huber_a;
+    const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
+    const CovDev C = cov_dev(h, w, R);
+    ScopedTimer t(h, "cov_assemble");
+    const int n_tab = std::max(d.n_kf, d.n_lmk);
+    hipLaunchKernelGGL(k_cov_tables, dim3((n_tab + 255) / 256), dim3(256), 0, h->stream, P, C, V.ptab.p);
+    const int n_tiles = d.tile_end - d.tile_begin;
+    if (n_tiles > 0) hipLaunchKernelGGL(R.pix ? k_cov_assemble<0> : k_cov_assemble<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C);
+    if (R.Np == 0) return SADVIO_OK;
+    if (d.n_free_kf > 0) hipLaunchKernelGGL(k_cov_schur, dim3(d.n_free_kf * (d.n_free_kf + 1) / 2), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C);
+    if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
+    hipLaunchKernelGGL(k_cov_factors, dim3(1), dim3(64), 0, h->stream, P, C);
+    if (R.dense) hipLaunchKernelGGL(k_cov_dense, dim3((unsigned)(((long long)d.dp_n * d.dp_n + 255) / 256)), dim3(256), 0, h->stream, P, C);
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
+// 3. Sigma_pp = S^-1: unpivoted Cholesky with every pivot tested, triangular inverse Z = G^-T, Sigma_pp = Z^T Z.
+// usable = false: a pivot is not safely positive (gauge not fixed).
+int cov_invert(sadvio_ba_handle* h, const CovRoutes& R, bool& usable) {
+    usable = true;
+    if (R.Np == 0) return SADVIO_OK;
+    CovScratch& V = h->cv;
+    MargScratch& M = h->mg;
+    const int n = R.Np;
+    const size_t nn = (size_t)n * n;
+    HIP_TRY(V.V.alloc(nn)); HIP_TRY(V.Lx.alloc(nn)); HIP_TRY(V.G.alloc(nn)); HIP_TRY(V.Z.alloc(nn));
+    HIP_TRY(M.wtmp.alloc((size_t)n + 16)); HIP_TRY(M.flag.alloc(8));
+    ScopedTimer t(h, "cov_invert");   // (spans the one host wait of the pivot test)
+    HIP_TRY(hipMemcpyAsync(V.V.p, V.S.p, sizeof(double) * nn, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(M.wtmp.p, 0, sizeof(double) * ((size_t)n + 16), h->stream));
+    bool ok = false;
+    if (int rc = factor_unpivoted(h, V.V.p, n, M.wtmp.p + 8, V.Lx.p, V.S.p, (long long)n, pchol_tau(n, SADVIO_EIG_CUT_REFERENCE), V.G.p, V.step_of, ok)) {
+        if (rc == SADVIO_E_HIP) h->err = "covariance: HIP error in the unpivoted Cholesky";
+        return rc;
+    }
+    if (!ok) { usable = false; return SADVIO_OK; }
+    if (int rc = prior_build_Z(h, V.G.p, n, n, SADVIO_PRIOR_FORM_CHOLESKY, V.step_of.p, V.Z.p, SADVIO_EIG_CUT_REFERENCE)) return rc;
+    launch_mgemm(h, V.Sig.p, n, V.Z.p, 1LL, (long long)n, V.Z.p, (long long)n, 1LL, n, n, n, 1.0, 0.0);
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
+// 4. Sigma_ll of every landmark of the window
+int cov_landmarks(sadvio_ba_handle* h, int w, const CovRoutes& R) {
+    const WinDev& d = h->wins[w].d;
+    if (!R.want_lmk || d.n_lmk == 0) return SADVIO_OK;
+    SolveOpts so{};
+    const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
+    const CovDev C = cov_dev(h, w, R);
+    const int per = COV_THREADS / R.G;
+    ScopedTimer t(h, "k_cov_lmk");
+    hipLaunchKernelGGL(R.G == 16 ? k_cov_lmk<16> : k_cov_lmk<64>, dim3((d.n_lmk + per - 1) / per), dim3(COV_THREADS), 0, h->stream, P, C);
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
+// 5. One wait; the caller's blocks are picked from Sigma_pp and the landmark table on the host
+int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const CovRoutes& R, double* kf_cov, double* pair_cov, double* lmk_cov,
+                  int32_t* n_lmk_singular) {
+    const WinDev& d = h->wins[w].d;
+    CovScratch& V = h->cv;
+    const int n = R.Np, dpf = d.dpf;
+    std::vector<double>& sig = V.h_sig; std::vector<double>& lo = V.h_lout;
+    const bool want_pp = n > 0 && ((kf_cov && rq->n_kf > 0) || (pair_cov && rq->n_pair > 0));
+    int n_sing = 0;
+    if (want_pp) { sig.resize((size_t)n * n); HIP_TRY(hipMemcpyAsync(sig.data(), V.Sig.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, h->stream)); }
+    if (R.want_lmk) {
+        lo.resize(9 * (size_t)d.n_lmk);
+        HIP_TRY(hipMemcpyAsync(lo.data(), V.lout.p, sizeof(double) * 9 * (size_t)d.n_lmk, hipMemcpyDeviceToHost, h->stream));
+    }
+    std::vector<int> st;
+    if (n_lmk_singular && d.n_lmk > 0) {
+        st.resize(d.n_lmk);
+        HIP_TRY(hipMemcpyAsync(st.data(), V.status.p, sizeof(int) * (size_t)d.n_lmk, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->cfg.profile_kernels) collect_timers(h);
+    auto block = [&](int ka, int kb, double* out) {
+        const int fa = h->h_kf_fidx[d.kf_base + ka], fb = h->h_kf_fidx[d.kf_base + kb];
+        for (int i = 0; i < dpf; i++)
+            for (int j = 0; j < dpf; j++) out[i * dpf + j] = (fa >= 0 && fb >= 0 && n > 0) ? sig[(size_t)(fa * dpf + i) * n + fb * dpf + j] : 0.0;
+    };
+    if (kf_cov) for (int i = 0; i < rq->n_kf; i++) block(rq->kf[i], rq->kf[i], kf_cov + (size_t)i * dpf * dpf);
+    if (pair_cov) for (int i = 0; i < rq->n_pair; i++) block(rq->pair_a[i], rq->pair_b[i], pair_cov + (size_t)i * dpf * dpf);
+    if (R.want_lmk)
+        for (int i = 0; i < R.n_lmk_out; i++) memcpy(lmk_cov + 9 * (size_t)i, &lo[9 * (size_t)(rq->n_lmk < 0 ? i : rq->lmk[i])], 72);
+    if (n_lmk_singular) {   // among the landmarks asked for
+        for (int i = 0; i < R.n_lmk_out; i++) n_sing += st[rq->n_lmk < 0 ? i : rq->lmk[i]] == COV_LMK_SINGULAR ? 1 : 0;
+        *n_lmk_singular = n_sing;
+    }
+    return SADVIO_OK;
+}
+
+int cov_run(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov, int32_t* n_lmk_singular) {
+    if (int rc = cov_check(h, w, rq, lmk_cov)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    const CovRoutes R = cov_routes(h, w, rq, lmk_cov);
+    if (int rc = cov_assemble(h, w, R)) return rc;
+    bool usable = true;
+    if (int rc = cov_invert(h, R, usable)) return rc;
+    if (!usable) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->cfg.profile_kernels) collect_timers(h);
+        h->err = "covariance: the reduced information matrix is not positive definite (gauge not fixed: no constant key-frame, no prior)";
+        return SADVIO_E_NOT_USABLE;
+    }
+    if (int rc = cov_landmarks(h, w, R)) return rc;
+    return cov_read_back(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+}
+
+}  // namespace
