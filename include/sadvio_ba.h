@@ -413,6 +413,28 @@ int sadvio_ba_sparsify(sadvio_ba_handle *h, int32_t w, int32_t vio, int32_t n_fu
 int sadvio_ba_marginalize_relative(sadvio_ba_handle *h, int32_t w, int32_t kf_a, int32_t kf_b, int32_t eig_cut_mode, double *inf36,
                                    double *Ak144);
 
+/* The same for n_pair pairs of window `w` in ONE call: what a caller who turns a window into a pose graph asks for (every pair
+ * (k, k + 1), (k, k + 2) of a 500-key-frame window is ~1 000 factors). Pair i gives exactly what
+ * sadvio_ba_marginalize_relative(h, w, kf_a[i], kf_b[i], eig_cut_mode, ...) defines — the same landmark selection with its
+ * multiplicities, the same cuts, the same Sigma_k, J and inverse — computed by one kernel launch (one workgroup per pair, down to
+ * the 6 x 6 inverse) behind one host wait, with no device allocation per pair. Deterministic: every sum is taken in a fixed order
+ * (no floating-point atomics), two calls return the same bits, and a pair's bits depend neither on the other pairs of the batch
+ * nor on its position in it. Duplicate pairs are allowed.
+ * status[i] = SADVIO_OK, or SADVIO_E_REFUSED for a pair that shares no landmark or whose 6 x 6 covariance cannot be inverted (a
+ * pivot that is exactly zero or not finite); a refused pair has zeros in all its outputs and the call still returns SADVIO_OK.
+ * n_pair = 0 returns SADVIO_OK and touches nothing. Argument errors fail the whole call with nothing written, codes as for the
+ * single pair: SADVIO_E_INVALID_ARG for a null required pointer, an index out of range, kf_a[i] == kf_b[i], a bad eig_cut_mode, a
+ * window with IMU states, a sharded window; SADVIO_E_STATE before set_windows or between begin_update and commit_update.
+ * The solve's deltas, summaries and trace and the handle's prior are left untouched. */
+int sadvio_ba_marginalize_relative_batch(sadvio_ba_handle *h, int32_t w, int32_t n_pair,
+        const int32_t *kf_a, const int32_t *kf_b,   /* [n_pair] */
+        int32_t eig_cut_mode,                       /* SADVIO_EIG_CUT_* */
+        double *inf36,       /* [n_pair][36], required */
+        double *Ak144,       /* [n_pair][144] or NULL */
+        double *T_a_b,       /* [n_pair][12] or NULL: T_a_w T_w_b (R row-major 9 | t 3), the T_prior of the Relative6DPose factor */
+        int32_t *n_shared,   /* [n_pair] or NULL: landmarks the pair shares (distinct; m = 3 * sum of multiplicities is NOT this) */
+        int32_t *status);    /* [n_pair], required: SADVIO_OK | SADVIO_E_REFUSED */
+
 /* ---- one window spanning several GPUs (no reference counterpart: the reference is one process) ----
  * The landmarks of a window (with all their observations) are partitioned over `world` processes, one GPU each;
  * key-frames, cameras, pose priors and IMU factors are replicated. A marginalisation prior rides a sharded window in its

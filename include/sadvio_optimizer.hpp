@@ -531,6 +531,43 @@ class HipOptimizer {
         if (Ak144) std::memcpy(Ak144, Ak, sizeof(Ak));
         return true;
     }
+    // marginalizeRelative for every (frame0, frame1) of `frames` (indices into map.frames) in one call
+    // (sadvio_ba_marginalize_relative_batch): the snapshot is flattened and uploaded once, one kernel launch serves all pairs.
+    // inf36: [n][36] row-major, T_a_b (optional): [n][12] = T_frame0_frame1 (R row-major 9 | t 3), the T_prior of the pair's
+    // Relative6DPose factor, ok (optional): [n] 1 / 0. A refused pair (no shared landmark, singular covariance) has ok = 0 and
+    // zeros, as marginalizeRelative leaves a zero matrix. Returns false, with every output zero, when the call itself fails (a
+    // bad frame index, frame0 == frame1, a non-pinhole pixel camera).
+    bool marginalizeRelativeBatch(LocalMapSnapshot& map, const std::vector<std::pair<int, int>>& frames, std::vector<double>* inf36,
+                                  std::vector<double>* T_a_b = nullptr, std::vector<int>* ok = nullptr) {
+        const size_t n = frames.size();
+        const int nkf = (int)map.frames.size();
+        std::vector<double> inf_local;
+        std::vector<double>& inf = inf36 ? *inf36 : inf_local;
+        inf.assign(36 * n, 0.0);
+        if (T_a_b) T_a_b->assign(12 * n, 0.0);
+        if (ok) ok->assign(n, 0);
+        if (n == 0) return true;
+        std::vector<int32_t> a(n), b(n), st(n, 0);
+        for (size_t i = 0; i < n; i++) {
+            a[i] = frames[i].first; b[i] = frames[i].second;
+            if (a[i] < 0 || a[i] >= nkf || b[i] < 0 || b[i] >= nkf || a[i] == b[i]) { _err = "marginalizeRelativeBatch: bad frame index"; return false; }
+        }
+        Flat F;
+        flatten(map, 0, false, false, false, F);
+        if (F.non_pinhole_pixel) { _err = "pixel factor with a non-pinhole camera: use the angular backend"; return false; }
+        int rc = upload(F, false);
+        if (rc == SADVIO_OK)
+            rc = sadvio_ba_marginalize_relative_batch(_h, 0, (int32_t)n, a.data(), b.data(), _rel_eig_cut_mode, inf.data(), nullptr,
+                                                      T_a_b ? T_a_b->data() : nullptr, nullptr, st.data());
+        if (rc != SADVIO_OK) {
+            _err = sadvio_ba_last_error(_h);
+            inf.assign(36 * n, 0.0);
+            if (T_a_b) T_a_b->assign(12 * n, 0.0);
+            return false;
+        }
+        if (ok) for (size_t i = 0; i < n; i++) (*ok)[i] = st[i] == SADVIO_OK ? 1 : 0;
+        return true;
+    }
 
     // Marginal covariances of the last window solve of this optimizer (sadvio_ba_covariance), addressed by the snapshot's ids:
     // frame_ids -> kf_cov [n][d][d] (d = block_dim(): 6, or 15 = pose6 | v | ba | bg after a VIO solve), frame_pairs -> pair_cov

@@ -404,6 +404,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.sadvio_ba_set_lines.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LineSetC)]
     lib.sadvio_ba_get_line_deltas.argtypes = [C.c_void_p, C.c_int32, _dp]
     lib.sadvio_ba_marginalize_relative.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
+    if hasattr(lib, "sadvio_ba_marginalize_relative_batch"):   # (an older build loaded through SADVIO_BA_LIB does not export it)
+        lib.sadvio_ba_marginalize_relative_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, C.c_int32, _dp, _dp, _dp, _ip, _ip]
     lib.sadvio_ba_get_prior.argtypes = [C.c_void_p, C.POINTER(PriorInfoC), _dp, _dp]
     lib.sadvio_ba_marg_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.sadvio_ba_set_prior.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
@@ -652,6 +654,20 @@ class Backend:
             return None
         self._check(rc, "marginalize_relative")
         return inf, Ak
+
+    def marginalize_relative_batch(self, w: int, pairs, eig_cut: str = "noise_floor"):
+        """sadvio_ba_marginalize_relative_batch: the relative-pose information of every (kf_a, kf_b) of `pairs` in one call.
+        {"inf" [n, 6, 6], "Ak" [n, 12, 12], "T_a_b" [n, 12], "n_shared" [n], "status" [n]}; status[i] is SADVIO_OK or E_REFUSED
+        (nothing shared, or a covariance that cannot be inverted: zeros in that pair's outputs)."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        n = len(pr)
+        ka, kb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        inf = np.zeros((n, 6, 6)); Ak = np.zeros((n, 12, 12)); Tab = np.zeros((n, 12))
+        ns = np.zeros(n, dtype=np.int32); st = np.zeros(n, dtype=np.int32)
+        rc = self.lib.sadvio_ba_marginalize_relative_batch(self.h, w, n, ka.ctypes.data_as(_ip), kb.ctypes.data_as(_ip), EIG_CUT[eig_cut],
+                                                           _ptr(inf), _ptr(Ak), _ptr(Tab), ns.ctypes.data_as(_ip), st.ctypes.data_as(_ip))
+        self._check(rc, "marginalize_relative_batch")
+        return {"inf": inf, "Ak": Ak, "T_a_b": Tab, "n_shared": ns, "status": st}
 
     def sparsify(self, w: int, prior: dict, vio: bool, raw: bool = False):
         """NFR sparsification of a dense prior dict (as returned by marginalize; without "J": the handle's resident prior)

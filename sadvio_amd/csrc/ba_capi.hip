@@ -820,6 +820,7 @@ static int build_layout(sadvio_ba_handle* h) {
 #undef UP
     h->h_lmk_const_user = lmk_const; h->user_lmk_const = h->has_lmk_const;
     h->h_lmk_ob = lmk_ob; h->h_lmk_oe = lmk_oe; h->h_kf_fidx = kf_fidx; h->h_obs_kf = obs_kf;
+    h->rel.csr_win = -1;   // the per-key-frame landmark lists of marginalize_relative_batch describe the old layout
     lap("alloc+queue");
     int rc = layout_reduced(h);
     if (rc != SADVIO_OK) return rc;
@@ -1758,6 +1759,20 @@ int sadvio_ba_covariance(sadvio_ba_handle* h, int32_t w, const sadvio_cov_reques
 }
 
 int sadvio_ba_set_window(sadvio_ba_handle* h, const sadvio_flat_window* window) { return sadvio_ba_set_windows(h, 1, window); }
+
+}  // extern "C"
+
+#include "rel_driver.h"
+
+extern "C" {
+
+// ---- the relative-pose information of many key-frame pairs of one window in one call (no reference counterpart as one call: the
+//      reference's marginalizeRelative takes one pair, …Analytic.cpp:665-809) ----
+int sadvio_ba_marginalize_relative_batch(sadvio_ba_handle* h, int32_t w, int32_t n_pair, const int32_t* kf_a, const int32_t* kf_b, int32_t eig_cut_mode,
+                                         double* inf36, double* Ak144, double* T_a_b, int32_t* n_shared, int32_t* status) {
+    if (!h) return SADVIO_E_INVALID_ARG;
+    return rel_run(h, w, n_pair, kf_a, kf_b, eig_cut_mode, inf36, Ak144, T_a_b, n_shared, status);
+}
 
 int sadvio_ba_landmark_chi2(sadvio_ba_handle* h, int32_t w, const double* pose_delta6, const double* lmk_delta3, const double* image_wh,
                             double pixel_sigma, double* avg_chi2, int32_t* inlier) {

@@ -225,6 +225,16 @@ struct CovScratch {
     std::vector<double> h_sig, h_lout;
 };
 
+// Work buffers of sadvio_ba_marginalize_relative_batch (rel_driver.h), grown on demand, and the per-key-frame landmark lists of one
+// window: built by the first batch call on a layout, dropped with the layout (build_layout).
+struct RelScratch {
+    DevBuf<int> pairs, kf_ptr, kf_lmk, n_shared, status;   // pairs: [2][n_pair] kf_a | kf_b
+    DevBuf<double> inf, Ak, Tab;
+    std::vector<int> h_pairs, h_ptr, h_lmk, h_last;
+    int csr_win = -1;      // window the lists on the device describe (-1: none)
+    int n_kf_lmk = 0;
+};
+
 struct LineSetHost {   // deep copy of a sadvio_line_set
     std::vector<int64_t> id;
     std::vector<double> T, model, meas;
@@ -305,6 +315,7 @@ struct sadvio_ba_handle {
     PriorState prior;   // the handle's own prior (sadvio_ba_marginalize leaves it here)
     MargScratch mg;
     CovScratch cv;
+    RelScratch rel;
     double cov_huber_a = 0.0;   // huber_a of the last solve: sadvio_ba_covariance corrects the visual factors as that solve did
     bool cov_use_lm = false;    // ... and whether the throughput kernels ran it (covariance is then refused)
     std::vector<SrcWin> src;                       // caller windows (deep copies)
