@@ -626,6 +626,48 @@ typedef struct sadvio_cov_request {
 int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_request *rq, double *kf_cov, double *pair_cov,
                          double *lmk_cov, int32_t *n_lmk_singular);
 
+/* ---- marginal covariances of many windows of the solved batch in one call ----
+ * Item i is exactly what sadvio_ba_covariance(h, items[i].w, &items[i].rq, kf_cov, pair_cov, lmk_cov, &n_lmk_singular) defines: the
+ * same H (Gauss-Newton at the final accepted state, the Huber corrector of the last solve), the same singular-landmark rule (nine
+ * NaNs, counted), zeros for constant variables, prior-kept landmarks taken from Sigma_pp, the same coordinates and output shapes. A
+ * window may appear in several items; the items of a window share its work on the device.
+ * route (out) says how Sigma_pp = S^-1 was formed:
+ *   SADVIO_COV_ROUTE_NONE   N_p = 0 (every key-frame constant, nothing kept): Sigma_ll = H_ll^-1. Same bits as the single call.
+ *   SADVIO_COV_ROUTE_LDS    0 < N_p <= 176: S is factored, inverted and squared inside one workgroup's LDS, all such items of the
+ *                           call in a fixed number of launches behind ONE wait. Another factorisation order than the single
+ *                           call's: equal within rounding, not to the bit.
+ *   SADVIO_COV_ROUTE_DENSE  N_p > 176: the route of sadvio_ba_covariance, item by item. Same bits as the single call.
+ * The environment variable SADVIO_COV_BATCH_LDS=0 (read when the handle is created) sends every item with N_p > 0 down the DENSE
+ * route. The LDS and NONE items are processed in groups of windows whose work arrays stay under 1 GiB
+ * (SADVIO_COV_BATCH_SCRATCH_MB overrides the figure; a window larger than the budget is a group of its own); the grouping does not
+ * change a bit of the results.
+ * Unlike sadvio_ba_covariance, the call accepts a batch the throughput kernels solved (65 536 landmarks or more).
+ * status (out) is SADVIO_OK, or SADVIO_E_NOT_USABLE for an item whose S has a pivot that is not safely positive (not finite, not
+ * above 1e-12 / N_p, or below 1024 N_p eps of its diagonal entry of S: gauge not fixed). Such an item's outputs are untouched, the
+ * other items are unaffected and the call returns SADVIO_OK.
+ * Argument errors fail the whole call before anything is written, in any item, with the single call's codes: SADVIO_E_STATE before
+ * a solve or inside a begin_update bracket; SADVIO_E_INVALID_ARG for n_item < 0, null `items` with n_item > 0, an index out of
+ * range in any item, a handle sharded over several GPUs, a window with line landmarks, a reduced system of 2047 columns or more.
+ * n_item = 0 returns SADVIO_OK and touches nothing.
+ * No floating-point atomics: two calls return the same bits, and an item's bits depend neither on the other items of the call nor
+ * on its position among them. The solve's deltas, summaries, trace and the handle's prior are left untouched. */
+#define SADVIO_COV_ROUTE_NONE  0
+#define SADVIO_COV_ROUTE_LDS   1
+#define SADVIO_COV_ROUTE_DENSE 2
+
+typedef struct sadvio_cov_batch_item {
+    int32_t w;               /* in: window of the batch */
+    int32_t status;          /* out: SADVIO_OK | SADVIO_E_NOT_USABLE */
+    int32_t n_lmk_singular;  /* out: among the landmarks asked for */
+    int32_t route;           /* out: SADVIO_COV_ROUTE_* */
+    sadvio_cov_request rq;   /* in: as for sadvio_ba_covariance */
+    double *kf_cov;          /* out, caller-allocated, any may be NULL; shapes as for sadvio_ba_covariance */
+    double *pair_cov;
+    double *lmk_cov;
+} sadvio_cov_batch_item;
+
+int sadvio_ba_covariance_batch(sadvio_ba_handle *h, int32_t n_item, sadvio_cov_batch_item *items);
+
 /* Average device time in microseconds per kernel class since the last set_windows, measured
  * with hipEvents on the handle's stream (cfg.profile_kernels = 1). `names` receives pointers
  * to static strings. Returns the number of classes written (<= cap). */

@@ -120,6 +120,12 @@ class CovRequestC(C.Structure):
                 ("lmk", _ip)]
 
 
+class CovBatchItemC(C.Structure):
+    _fields_ = [("w", C.c_int32), ("status", C.c_int32), ("n_lmk_singular", C.c_int32), ("route", C.c_int32), ("rq", CovRequestC),
+                ("kf_cov", _dp), ("pair_cov", _dp), ("lmk_cov", _dp)]
+
+
+COV_ROUTE_NONE, COV_ROUTE_LDS, COV_ROUTE_DENSE = 0, 1, 2   # SADVIO_COV_ROUTE_*
 PRIOR_RESIDENT = -1
 # SADVIO_EIG_CUT_*: the C ABI's default (a zero-initialised request) is the reference's absolute 1e-12; this harness and the
 # oracle's wrapper default to "noise_floor" because the parity tests compare n_full, which only that mode makes reproducible
@@ -416,6 +422,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                           C.POINTER(NoFovResultC), _dp, _dp, _ip]
     if hasattr(lib, "sadvio_ba_covariance"):   # an older build loaded through SADVIO_BA_LIB (A/B measurements) does not export it
         lib.sadvio_ba_covariance.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CovRequestC), _dp, _dp, _dp, _ip]
+    if hasattr(lib, "sadvio_ba_covariance_batch"):   # (nor this one)
+        lib.sadvio_ba_covariance_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CovBatchItemC)]
     lib.sadvio_ba_landmark_chi2.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, _dp, _ip]
     lib.sadvio_ba_get_kernel_times.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), _dp, _lp]
     lib.sadvio_ba_last_error.argtypes = [C.c_void_p]
@@ -790,6 +798,54 @@ class Backend:
             return {"rc": rc, "error": msg.decode() if msg else "", "kf": kc, "pair": pc, "lmk": lc}
         self._check(rc, "covariance")
         return {"rc": rc, "kf": kc, "pair": pc, "lmk": lc, "n_lmk_singular": int(ns.value)}
+
+    def cov_batch_items(self, items, fill: float = 0.0):
+        """The sadvio_cov_batch_item array of `items` (dicts w=.., kf=.., pairs=.., lmk=.. with the meanings of covariance()) and the
+        output arrays it points to, allocated here and filled with `fill`: (array, one dict of "kf" / "pair" / "lmk" per item, the index
+        arrays to keep alive). A caller that repeats a call (scripts/gpu_time_covariance_batch.py) builds them once."""
+        arr = (CovBatchItemC * max(len(items), 1))()
+        keep, outs = [], []
+        for i, it in enumerate(items):
+            w = int(it.get("w", 0))
+            win = self.windows[w] if 0 <= w < len(self.windows) else self.windows[0]   # (an index out of range is the library's to refuse)
+            d = 15 if win.has_imu else 6
+            kf, pairs, lmk = it.get("kf"), it.get("pairs"), it.get("lmk")
+            ka = np.ascontiguousarray([] if kf is None else kf, dtype=np.int32).reshape(-1)
+            pr = np.ascontiguousarray([] if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+            pa, pb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+            all_lmk = isinstance(lmk, str) and lmk == "all"
+            la = np.ascontiguousarray([] if (lmk is None or all_lmk) else lmk, dtype=np.int32).reshape(-1)
+            n_l = win.n_lmk if all_lmk else len(la)
+            kc = np.full((len(ka), d, d), fill); pc = np.full((len(pa), d, d), fill); lc = np.full((n_l, 3, 3), fill)
+            a = arr[i]
+            a.w = w
+            a.rq.n_kf, a.rq.kf = len(ka), ka.ctypes.data_as(_ip)
+            a.rq.n_pair, a.rq.pair_a, a.rq.pair_b = len(pa), pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip)
+            a.rq.n_lmk, a.rq.lmk = (-1 if all_lmk else len(la)), la.ctypes.data_as(_ip)
+            a.kf_cov = _ptr(kc) if len(ka) else _dp()
+            a.pair_cov = _ptr(pc) if len(pa) else _dp()
+            a.lmk_cov = _ptr(lc) if n_l else _dp()
+            keep.append((ka, pa, pb, la))
+            outs.append({"kf": kc, "pair": pc, "lmk": lc})
+        return arr, outs, keep
+
+    def covariance_batch(self, items, raw_rc: bool = False, fill: float = 0.0):
+        """Marginal covariances of many windows of the solved batch in one call (sadvio_ba_covariance_batch).
+        items: dicts w=.., kf=.., pairs=.., lmk=.. with the meanings of covariance(); a window may appear in several items. Returns
+        one dict per item, shaped as covariance() returns, plus "status" (SADVIO_OK | E_NOT_USABLE: that item's outputs are
+        untouched) and "route" (COV_ROUTE_*). The outputs are allocated here, filled with `fill`. raw_rc=True returns
+        {"rc", "error", "items"} for a refused call instead of raising."""
+        n = len(items)
+        arr, outs, keep = self.cov_batch_items(items, fill)
+        rc = self.lib.sadvio_ba_covariance_batch(self.h, n, arr if n else C.POINTER(CovBatchItemC)())
+        if rc == SADVIO_OK:
+            for i, o in enumerate(outs):
+                o.update(rc=int(arr[i].status), status=int(arr[i].status), route=int(arr[i].route), n_lmk_singular=int(arr[i].n_lmk_singular))
+        if rc != SADVIO_OK and raw_rc:
+            msg = self.lib.sadvio_ba_last_error(self.h)
+            return {"rc": rc, "error": msg.decode() if msg else "", "items": outs}
+        self._check(rc, "covariance_batch")
+        return outs
 
     def kernel_times(self):
         cap = 32

@@ -1762,6 +1762,18 @@ int sadvio_ba_set_window(sadvio_ba_handle* h, const sadvio_flat_window* window) 
 
 }  // extern "C"
 
+#include "cov_batch_driver.h"   // below cov_driver.h: an item above the LDS cap goes through its steps
+
+extern "C" {
+
+// ---- the covariances of many windows of the solved batch in one call ----
+int sadvio_ba_covariance_batch(sadvio_ba_handle* h, int32_t n_item, sadvio_cov_batch_item* items) {
+    if (!h) return SADVIO_E_INVALID_ARG;
+    return covb_run(h, n_item, items);
+}
+
+}  // extern "C"
+
 #include "rel_driver.h"
 
 extern "C" {

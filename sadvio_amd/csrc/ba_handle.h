@@ -225,6 +225,28 @@ struct CovScratch {
     std::vector<double> h_sig, h_lout;
 };
 
+// Work buffers of sadvio_ba_covariance_batch (cov_batch_driver.h). The pools hold the work arrays (pool, ipool) and the results (rpool)
+// of one group of windows and only ever grow; the pinned block holds the unit tables and receives every group's results, one copy
+// per group, read after the call's one wait.
+struct CovBatchScratch {
+    DevBuf<double> pool, rpool, ptab;
+    DevBuf<int> ipool;
+    DevBuf<char> units;
+    char* pinned = nullptr; size_t pinned_cap = 0;
+    hipError_t pin(size_t bytes) {
+        if (bytes <= pinned_cap) return hipSuccess;
+        if (pinned) (void)hipHostFree(pinned);
+        pinned = nullptr; pinned_cap = 0;
+        hipError_t e = hipHostMalloc((void**)&pinned, bytes + bytes / 2, hipHostMallocDefault);
+        if (e == hipSuccess) pinned_cap = bytes + bytes / 2;
+        return e;
+    }
+    CovBatchScratch() = default;
+    CovBatchScratch(const CovBatchScratch&) = delete;
+    CovBatchScratch& operator=(const CovBatchScratch&) = delete;
+    ~CovBatchScratch() { if (pinned) (void)hipHostFree(pinned); }
+};
+
 // Work buffers of sadvio_ba_marginalize_relative_batch (rel_driver.h), grown on demand, and the per-key-frame landmark lists of one
 // window: built by the first batch call on a layout, dropped with the layout (build_layout).
 struct RelScratch {
@@ -258,6 +280,7 @@ struct EnvCfg {
     int debug = 0;
     int lm = -1, pf_wg = -1;            // -1: not set
     int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
+    int cov_batch_lds = 1, cov_batch_scratch_mb = 1024;   // sadvio_ba_covariance_batch: the in-LDS inverse (0: every item down the dense route, A/B) | scratch budget of one group
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false;
     void read() {
@@ -265,6 +288,7 @@ struct EnvCfg {
         auto num = [](const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; };
         debug = num("SADVIO_DEBUG", 0); lm = num("SADVIO_LM", -1); pf_wg = num("SADVIO_PF_WG", -1);
         tile_rounds = num("SADVIO_TILE_ROUNDS", 0); lm_subs = num("SADVIO_LM_SUBS", 0); band_c = num("SADVIO_BAND_C", 0);
+        cov_batch_lds = num("SADVIO_COV_BATCH_LDS", 1); cov_batch_scratch_mb = num("SADVIO_COV_BATCH_SCRATCH_MB", 1024);
         if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);
         marg_pivoted = on("SADVIO_MARG_PIVOTED"); marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
@@ -315,6 +339,7 @@ struct sadvio_ba_handle {
     PriorState prior;   // the handle's own prior (sadvio_ba_marginalize leaves it here)
     MargScratch mg;
     CovScratch cv;
+    CovBatchScratch cvb;
     RelScratch rel;
     double cov_huber_a = 0.0;   // huber_a of the last solve: sadvio_ba_covariance corrects the visual factors as that solve did
     bool cov_use_lm = false;    // ... and whether the throughput kernels ran it (covariance is then refused)

@@ -1,0 +1,286 @@
+// cov_batch_driver.h — the host side of sadvio_ba_covariance_batch as named steps
+//   covb_check -> covb_routes -> covb_groups -> covb_assemble -> covb_invert -> covb_landmarks -> covb_read_back
+// Item i is what sadvio_ba_covariance(h, items[i].w, &items[i].rq, ..) defines. The device works per UNIT, a window named by at least
+// one item: the items of a window share its assembly, its Sigma_pp and its landmark table, and differ only in the blocks the host
+// picks for them. Units whose N_p is at most COVB_CAP (route LDS) or zero (route NONE) are processed in groups whose work arrays
+// stay under the scratch budget; a group is one launch sequence on the handle's stream (cov_batch_kernels.h), its results go to
+// pinned host memory with one asynchronous copy, and the call waits once, after the last group. A unit above the cap (route DENSE)
+// goes item by item through cov_driver.h's steps as they are, with the wait that route has.
+//
+// After a solve by the throughput kernels (lm_kernels.h). sadvio_ba_covariance refuses such a batch; this call accepts it, on these
+// grounds. (i) Both solve paths keep two delta buffers per array and LmState::cur names the one holding the accepted state x: k_solve
+// (shared by both paths) writes the candidate poses to xp[1 - cur]; k_lm_pass reads xl[cur] and writes the candidate landmarks to
+// xl[1 - cur] exactly as k_backsub does on the latency path; k_decide (shared) is the only writer of cur and flips it when, and only
+// when, it accepts the candidate; the closing k_decide launch copies the state to FinalRec, which the host keeps in fin[w].s.
+// xp / xl (and xv, xba, xbg) at fin[w].s.cur are therefore the accepted state of window w on either path — the buffer get_deltas
+// reads. (ii) The kernels here read the window's arrays, the observation arrays and the Tile / tile_lmk lists only; build_layout
+// fills those for both paths (the throughput path adds chunk tables beside them, it replaces nothing).
+// Nothing of the solve is touched. Part of the library's single translation unit (ba_capi.hip); not a public header.
+#pragma once
+#include "cov_batch_kernels.h"
+#include "cov_driver.h"
+
+namespace {
+
+struct CovbUnit {
+    int w = 0;
+    CovRoutes R;
+    int route = COVB_ROUTE_NONE;
+    size_t bytes = 0;                             // work arrays of the unit, what the scratch budget counts
+    size_t nl = 1, no = 1, nn = 1;                // landmarks, observations, N_p^2 (at least 1 each)
+    size_t r_lout = 0, r_size = 0, r_off = 0;     // doubles: its landmark table | its result block | where that starts among the call's
+};
+// A unit's result block, one piece of device memory copied to the host in one go with its group's: Sigma_pp [nn] | lout [r_lout] |
+// landmark status [nl ints] | pivot flag [1 int]
+struct CovbGroup { int u0 = 0, u1 = 0; size_t doubles = 0, ints = 0, r_doubles = 0, r0 = 0; };
+
+// 1. State and arguments, with the codes and the order of sadvio_ba_covariance. Host work only; nothing is written on an error.
+int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* items) {
+    if (h->world > 1) { h->err = "covariance_batch: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
+    if (h->defer) { h->err = "covariance_batch between begin_update and commit_update"; return SADVIO_E_STATE; }
+    if (!h->solved) { h->err = "covariance_batch before solve"; return SADVIO_E_STATE; }
+    if (n_item < 0) { h->err = "covariance_batch: negative item count"; return SADVIO_E_INVALID_ARG; }
+    if (n_item > 0 && !items) { h->err = "covariance_batch: null items"; return SADVIO_E_INVALID_ARG; }
+    for (int it = 0; it < n_item; it++) {
+        const int w = items[it].w;
+        const sadvio_cov_request* rq = &items[it].rq;
+        if (w < 0 || w >= (int)h->wins.size()) { h->err = "covariance_batch: window out of range"; return SADVIO_E_INVALID_ARG; }
+        const WinDev& d = h->wins[w].d;
+        if (d.line_end > d.line_begin) { h->err = "covariance_batch: the window carries line landmarks"; return SADVIO_E_INVALID_ARG; }
+        if (rq->n_kf < 0 || rq->n_pair < 0 || rq->n_lmk < -1 || (rq->n_kf > 0 && !rq->kf) || (rq->n_pair > 0 && (!rq->pair_a || !rq->pair_b)) ||
+            (rq->n_lmk > 0 && !rq->lmk)) { h->err = "covariance_batch: request out of range"; return SADVIO_E_INVALID_ARG; }
+        for (int i = 0; i < rq->n_kf; i++)
+            if (rq->kf[i] < 0 || rq->kf[i] >= d.n_kf) { h->err = "covariance_batch: key-frame index out of range"; return SADVIO_E_INVALID_ARG; }
+        for (int i = 0; i < rq->n_pair; i++)
+            if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) { h->err = "covariance_batch: key-frame index of a pair out of range"; return SADVIO_E_INVALID_ARG; }
+        for (int i = 0; i < rq->n_lmk; i++)
+            if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) { h->err = "covariance_batch: landmark index out of range"; return SADVIO_E_INVALID_ARG; }
+        if (d.Np + 1 > PCH_MAXN) { h->err = "covariance_batch: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
+    }
+    return SADVIO_OK;
+}
+
+// 2. The route of every item; one unit per window that does not take the dense route
+void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, std::vector<CovbUnit>& units, std::vector<int>& unit_of) {
+    std::vector<int> of_win(h->wins.size(), -1);
+    unit_of.assign((size_t)n_item, -1);
+    for (int it = 0; it < n_item; it++) {
+        sadvio_cov_batch_item& I = items[it];
+        const WinDev& d = h->wins[I.w].d;
+        I.status = SADVIO_OK; I.n_lmk_singular = 0;
+        I.route = d.Np == 0 ? SADVIO_COV_ROUTE_NONE : (d.Np <= COVB_CAP && h->env.cov_batch_lds != 0 ? SADVIO_COV_ROUTE_LDS : SADVIO_COV_ROUTE_DENSE);
+        if (I.route == SADVIO_COV_ROUTE_DENSE) continue;
+        const CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
+        if (of_win[I.w] < 0) {
+            of_win[I.w] = (int)units.size();
+            CovbUnit U;
+            U.w = I.w; U.R = R; U.R.want_lmk = false; U.route = I.route;
+            U.nl = (size_t)std::max(d.n_lmk, 1); U.no = (size_t)std::max(d.n_obs, 1); U.nn = (size_t)std::max(d.Np, 1) * std::max(d.Np, 1);
+            U.bytes = sizeof(double) * (21 * U.nl + (COV_ENT_W + COV_ENT_HPP) * U.no + 2 * U.nn) + sizeof(int) * (2 * U.nl + U.no + 1);
+            units.push_back(U);
+        }
+        CovbUnit& U = units[of_win[I.w]];
+        U.R.want_lmk |= R.want_lmk;
+        unit_of[it] = of_win[I.w];
+    }
+}
+
+// An item above the cap: the steps of sadvio_ba_covariance, unchanged (cov_check's tests were made for every item by covb_check)
+int covb_dense_item(sadvio_ba_handle* h, sadvio_cov_batch_item& I) {
+    const CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
+    if (int rc = cov_assemble(h, I.w, R)) return rc;
+    bool usable = true;
+    if (int rc = cov_invert(h, R, usable)) return rc;
+    if (!usable) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->cfg.profile_kernels) collect_timers(h);
+        I.status = SADVIO_E_NOT_USABLE;
+        return SADVIO_OK;
+    }
+    if (int rc = cov_landmarks(h, I.w, R)) return rc;
+    return cov_read_back(h, I.w, &I.rq, R, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
+}
+
+// 3. Groups of consecutive units under the scratch budget (a unit larger than the budget is a group of its own); the pools, the
+// unit table and the pinned block are sized once, for the largest group and for all results, before anything is launched
+int covb_groups(sadvio_ba_handle* h, std::vector<CovbUnit>& units, std::vector<CovbGroup>& groups) {
+    CovBatchScratch& B = h->cvb;
+    const size_t budget = (size_t)std::max(h->env.cov_batch_scratch_mb, 0) << 20;
+    size_t used = 0, max_d = 1, max_i = 1, max_r = 1, r_tot = 0;
+    for (int u = 0; u < (int)units.size(); u++) {
+        CovbUnit& U = units[u];
+        if (groups.empty() || used + U.bytes > budget) { groups.push_back(CovbGroup{u, u, 0, 0, 0, r_tot}); used = 0; }
+        CovbGroup& g = groups.back();
+        U.r_lout = U.R.want_lmk ? 9 * U.nl : 0;
+        U.r_size = U.nn + U.r_lout + (U.nl + 1) / 2 + 1;
+        U.r_off = r_tot; r_tot += U.r_size;
+        g.u1 = u + 1; g.doubles += 12 * U.nl + (COV_ENT_W + COV_ENT_HPP) * U.no + U.nn; g.ints += U.nl + U.no; g.r_doubles += U.r_size;
+        used += U.bytes;
+        max_d = std::max(max_d, g.doubles); max_i = std::max(max_i, g.ints); max_r = std::max(max_r, g.r_doubles);
+    }
+    HIP_TRY(B.pool.alloc(max_d)); HIP_TRY(B.ipool.alloc(max_i)); HIP_TRY(B.rpool.alloc(max_r));
+    HIP_TRY(B.ptab.alloc((size_t)h->n_kf_tot * POSE_TAB));
+    HIP_TRY(B.units.alloc(sizeof(CovUnit) * units.size()));
+    HIP_TRY(B.pin(sizeof(CovUnit) * units.size() + sizeof(double) * r_tot));
+    return SADVIO_OK;
+}
+
+// the call's result blocks in the pinned block, behind the unit tables
+double* covb_host_results(sadvio_ba_handle* h, const std::vector<CovbUnit>& units) { return (double*)(h->cvb.pinned + sizeof(CovUnit) * units.size()); }
+
+// 4. One group: the unit table; linearise every unit at its x*; every S, full symmetric
+int covb_assemble(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const CovbGroup& g, const DevPtrs& P, const CovUnit*& d_units) {
+    CovBatchScratch& B = h->cvb;
+    const int nu = g.u1 - g.u0;
+    CovUnit* tab = (CovUnit*)B.pinned + g.u0;
+    // the work pool: every S of the group first (one memset), then unit after unit; the result pool: block after block
+    size_t s_tot = 0;
+    for (int u = g.u0; u < g.u1; u++) s_tot += units[u].nn;
+    double* pd = B.pool.p + s_tot; double* ps = B.pool.p;
+    int* pi = B.ipool.p;
+    int mx_tab = 1, mx_tiles = 0, mx_schur = 0, mx_dense = 0;
+    bool any_kept = false, any_np = false;
+    for (int u = g.u0; u < g.u1; u++) {
+        const CovbUnit& U = units[u];
+        const WinDev& d = h->wins[U.w].d;
+        const size_t nl = U.nl, no = U.no, nn = U.nn;
+        CovUnit& T = tab[u - g.u0];
+        memset(&T, 0, sizeof(T));
+        CovDev& C = T.C;
+        C.w = U.w; C.cur = U.R.cur; C.Np = U.R.Np; C.huber_a = h->cov_huber_a;
+        C.ptab = B.ptab.p;
+        C.S = ps; ps += nn;
+        C.hll = pd; pd += 6 * nl; C.hinv = pd; pd += 6 * nl;
+        C.ent_w = pd; pd += COV_ENT_W * no; C.ent_hpp = pd; pd += COV_ENT_HPP * no;
+        C.ent_n = pi; pi += nl; C.ent_col = pi; pi += no;
+        double* pr = B.rpool.p + (U.r_off - g.r0);
+        T.sig = pr; C.Sig = pr; C.lout = pr + nn;
+        C.status = (int*)(pr + nn + U.r_lout);
+        T.bad = C.status + 2 * ((nl + 1) / 2);
+        T.route = U.route;
+        T.G = U.R.want_lmk && d.n_lmk > 0 ? U.R.G : 0;
+        mx_tab = std::max(mx_tab, (std::max(d.n_kf, d.n_lmk) + 255) / 256);
+        mx_tiles = std::max(mx_tiles, d.tile_end - d.tile_begin);
+        if (U.R.Np > 0) {
+            any_np = true;
+            mx_schur = std::max(mx_schur, d.n_free_kf * (d.n_free_kf + 1) / 2);
+            any_kept |= U.R.kept;
+            if (U.R.dense) mx_dense = std::max(mx_dense, (int)(((long long)d.dp_n * d.dp_n + 255) / 256));
+        }
+    }
+    d_units = (const CovUnit*)B.units.p + g.u0;
+    HIP_TRY(hipMemcpyAsync((void*)d_units, tab, sizeof(CovUnit) * nu, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(B.pool.p, 0, sizeof(double) * s_tot, h->stream));
+    const bool pix = h->factor_type == SADVIO_FACTOR_PIXEL;
+    ScopedTimer t(h, "covb_assemble");
+    hipLaunchKernelGGL(k_covb_tables, dim3(mx_tab, nu), dim3(256), 0, h->stream, P, d_units, B.ptab.p);
+    if (mx_tiles > 0) hipLaunchKernelGGL(pix ? k_covb_assemble<0> : k_covb_assemble<1>, dim3(mx_tiles, nu), dim3(COV_THREADS), 0, h->stream, P, d_units);
+    if (any_np) {
+        if (mx_schur > 0) hipLaunchKernelGGL(k_covb_schur, dim3(mx_schur, nu), dim3(COV_SCHUR_THREADS), 0, h->stream, P, d_units);
+        if (any_kept) hipLaunchKernelGGL(pix ? k_covb_kept<0> : k_covb_kept<1>, dim3(nu), dim3(64), 0, h->stream, P, d_units);
+        hipLaunchKernelGGL(k_covb_factors, dim3(nu), dim3(64), 0, h->stream, P, d_units);
+        if (mx_dense > 0) hipLaunchKernelGGL(k_covb_dense, dim3(mx_dense, nu), dim3(256), 0, h->stream, P, d_units);
+    }
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
+// 5. Sigma_pp of every unit of the group with N_p > 0: one workgroup each, in LDS. A failed pivot test sets the unit's flag on the
+// device; the host reads it behind the call's one wait.
+int covb_invert(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const CovbGroup& g, const CovUnit* d_units) {
+    int nb = 0;
+    for (int u = g.u0; u < g.u1; u++)
+        if (units[u].route == COVB_ROUTE_LDS) nb = std::max(nb, (units[u].R.Np + 15) / 16);
+    if (nb == 0) return SADVIO_OK;
+    (void)hipFuncSetAttribute((const void*)k_cov_inv_lds, hipFuncAttributeMaxDynamicSharedMemorySize, covb_lds_bytes(COVB_CAP / 16));
+    ScopedTimer t(h, "k_cov_inv_lds");
+    hipLaunchKernelGGL(k_cov_inv_lds, dim3(g.u1 - g.u0), dim3(COVB_THREADS), covb_lds_bytes(nb), h->stream, d_units);
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
+// 6. Sigma_ll of every landmark of the units that were asked for landmark blocks; then the group's results on their way to the host
+int covb_landmarks(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const CovbGroup& g, const DevPtrs& P, const CovUnit* d_units) {
+    CovBatchScratch& B = h->cvb;
+    const int nu = g.u1 - g.u0;
+    int blocks[2] = {0, 0};   // G = 16 | 64
+    for (int u = g.u0; u < g.u1; u++) {
+        const CovbUnit& U = units[u];
+        const WinDev& d = h->wins[U.w].d;
+        if (!U.R.want_lmk || d.n_lmk == 0) continue;
+        const int per = COV_THREADS / U.R.G;
+        int& b = blocks[U.R.G == 16 ? 0 : 1];
+        b = std::max(b, (d.n_lmk + per - 1) / per);
+    }
+    {
+        ScopedTimer t(h, "k_covb_lmk");
+        if (blocks[0]) hipLaunchKernelGGL(k_covb_lmk<16>, dim3(blocks[0], nu), dim3(COV_THREADS), 0, h->stream, P, d_units);
+        if (blocks[1]) hipLaunchKernelGGL(k_covb_lmk<64>, dim3(blocks[1], nu), dim3(COV_THREADS), 0, h->stream, P, d_units);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(covb_host_results(h, units) + g.r0, B.rpool.p, sizeof(double) * g.r_doubles, hipMemcpyDeviceToHost, h->stream));
+    return SADVIO_OK;
+}
+
+// 7. The call's one wait; every item's blocks are picked from its unit's Sigma_pp and landmark table on the host, as cov_read_back
+// picks them. An item whose unit failed the pivot test gets its status and nothing else.
+int covb_read_back(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, const std::vector<CovbUnit>& units, const std::vector<int>& unit_of) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->cfg.profile_kernels) collect_timers(h);
+    for (int it = 0; it < n_item; it++) {
+        if (unit_of[it] < 0) continue;
+        sadvio_cov_batch_item& I = items[it];
+        const CovbUnit& U = units[unit_of[it]];
+        const double* sig = covb_host_results(h, units) + U.r_off;
+        const double* lo = sig + U.nn;
+        const int* st = (const int*)(lo + U.r_lout);
+        if (st[2 * ((U.nl + 1) / 2)] != 0) { I.status = SADVIO_E_NOT_USABLE; continue; }
+        const WinDev& d = h->wins[I.w].d;
+        const sadvio_cov_request* rq = &I.rq;
+        const int n = U.R.Np, dpf = d.dpf;
+        auto block = [&](int ka, int kb, double* out) {
+            const int fa = h->h_kf_fidx[d.kf_base + ka], fb = h->h_kf_fidx[d.kf_base + kb];
+            for (int i = 0; i < dpf; i++)
+                for (int j = 0; j < dpf; j++) out[i * dpf + j] = (fa >= 0 && fb >= 0 && n > 0) ? sig[(size_t)(fa * dpf + i) * n + fb * dpf + j] : 0.0;
+        };
+        if (I.kf_cov) for (int i = 0; i < rq->n_kf; i++) block(rq->kf[i], rq->kf[i], I.kf_cov + (size_t)i * dpf * dpf);
+        if (I.pair_cov) for (int i = 0; i < rq->n_pair; i++) block(rq->pair_a[i], rq->pair_b[i], I.pair_cov + (size_t)i * dpf * dpf);
+        const int n_out = rq->n_lmk < 0 ? d.n_lmk : rq->n_lmk;
+        int n_sing = 0;
+        if (I.lmk_cov && rq->n_lmk < 0) memcpy(I.lmk_cov, lo, 72 * (size_t)n_out);
+        for (int i = 0; i < n_out; i++) {
+            const int l = rq->n_lmk < 0 ? i : rq->lmk[i];
+            if (I.lmk_cov && rq->n_lmk >= 0) memcpy(I.lmk_cov + 9 * (size_t)i, lo + 9 * (size_t)l, 72);
+            n_sing += st[l] == COV_LMK_SINGULAR ? 1 : 0;
+        }
+        I.n_lmk_singular = n_sing;
+    }
+    return SADVIO_OK;
+}
+
+int covb_run(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items) {
+    if (int rc = covb_check(h, n_item, items)) return rc;
+    if (n_item == 0) return SADVIO_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    std::vector<CovbUnit> units;
+    std::vector<int> unit_of;
+    covb_routes(h, n_item, items, units, unit_of);
+    for (int it = 0; it < n_item; it++)
+        if (items[it].route == SADVIO_COV_ROUTE_DENSE)
+            if (int rc = covb_dense_item(h, items[it])) return rc;
+    if (units.empty()) return SADVIO_OK;
+    std::vector<CovbGroup> groups;
+    if (int rc = covb_groups(h, units, groups)) return rc;
+    SolveOpts so{};
+    so.huber_a = h->cov_huber_a;
+    const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
+    for (const CovbGroup& g : groups) {
+        const CovUnit* d_units = nullptr;
+        if (int rc = covb_assemble(h, units, g, P, d_units)) return rc;
+        if (int rc = covb_invert(h, units, g, d_units)) return rc;
+        if (int rc = covb_landmarks(h, units, g, P, d_units)) return rc;
+    }
+    return covb_read_back(h, n_item, items, units, unit_of);
+}
+
+}  // namespace
