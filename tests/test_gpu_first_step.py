@@ -1,0 +1,96 @@
+"""The first LM step of every reduced-solve route against the 50-digit step (tests/step_helpers.py).
+
+One solve of ONE iteration per case: k_solve<0, false> (VO, N_p = 6 .. 174 at every size where chol16.h's c16_solve branches),
+k_solve<0, true> (VIO and kept landmarks), and the five out-of-LDS routes of solve_driver.h at their boundary sizes. The step must lie
+within TOL_FACTOR x max(E_REF, FLOOR) of the 50-digit one, where E_REF is the float64 oracle's own distance from it
+(tests/test_step_reference_cpu.py keeps that table honest and proves that this bar sees a single unrefined reciprocal square root, a
+dropped rank-4 product and a missing damping term); the trace row of the step must carry the 50-digit model cost change and cost to
+1e-11. The whole-solve tests hold the same code to 1e-6 only.
+
+Every case prints its measured multiples (`FIRST_STEP ...`, run with -s) before it asserts; DESIGN.md section 2 records them."""
+import numpy as np
+import pytest
+
+import step_helpers as sh
+from sadvio_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+SWITCHES = ("SADVIO_BAND_C", "SADVIO_NO_BCR")
+_device = {}      # case name -> deltas of the device's step (the route-against-route test reuses them)
+
+
+def run_case(backend_cls, monkeypatch, case, front=()):
+    """(summary, deltas, trace) of one iteration on the case's window, stored behind the windows `front` of one batch. The
+    switches are set before the handle is created: it reads them once, in create."""
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in case.env.items():
+        monkeypatch.setenv(k, v)
+    w = sh.case_window(case)
+    i = len(front)
+    be = backend_cls(device=0)
+    try:
+        be.set_windows(list(front) + [w])
+        s = be.solve(capi.gn_options(1))[i]
+        d = be.get_deltas(i)
+        tr = be.get_trace(i)
+    finally:
+        be.close()
+    return s, d, tr
+
+
+def check_case(case, oracle_lib, s, d, tr, n_win=1, tag=""):
+    w = sh.case_window(case)
+    lay = sh.layout(w)
+    assert lay["Nr"] == case.np_
+    assert sh.free_kf_observations(w).min() >= 10
+    route = sh.expected_route(lay["Nr"], lay["dpf"], sh.band_rows(w), n_win, int(case.env.get("SADVIO_BAND_C", 0)),
+                              case.env.get("SADVIO_NO_BCR") == "1")
+    assert route == ("lds" if case.route.startswith("lds") else case.route), route
+    if route in ("band", "band_twisted", "bcr"):
+        assert sh.band_rows(w) == 3 * lay["dpf"] == (sh.half_bandwidth(w) + 1) * lay["dpf"]     # band = 1: three key-frames
+    ref = sh.reference(case, oracle_lib)
+    e = sh.step_error(d, ref, w)
+    unit = [max(v, sh.FLOOR) for v in sh.E_REF[case.window]]
+    mcc_rel = abs(tr[1][7] / ref["model_cost_change"] - 1) if len(tr) > 1 else np.inf
+    cost_rel = abs(tr[1][0] / ref["cost"] - 1) if len(tr) > 1 else np.inf
+    print(f"FIRST_STEP {case.name}{tag} Np {case.np_} {case.route} e_ref {sh.E_REF[case.window][0]:.1e} {sh.E_REF[case.window][1]:.1e} "
+          f"multiple pose {e[0] / unit[0]:.2f} lmk {e[1] / unit[1]:.2f} mcc {mcc_rel:.1e} cost {cost_rel:.1e} steps {s.num_successful_steps}")
+    assert s.num_successful_steps == 1          # the oracle accepts this step (test_step_reference_cpu.py): a rejection is a failure
+    bar_p, bar_l = sh.bars(case)
+    assert e[0] <= bar_p, ("pose part", e[0], bar_p)
+    assert e[1] <= bar_l, ("landmark part", e[1], bar_l)
+    assert np.isclose(tr[1][7], ref["model_cost_change"], rtol=1e-11, atol=0)
+    assert np.isclose(tr[1][0], ref["cost"], rtol=1e-11, atol=0)
+
+
+@pytest.mark.parametrize("case", sh.CASES, ids=[c.name for c in sh.CASES])
+def test_first_step_against_50_digits(backend_cls, oracle_lib, monkeypatch, case):
+    s, d, tr = run_case(backend_cls, monkeypatch, case)
+    _device[case.name] = d
+    check_case(case, oracle_lib, s, d, tr)
+
+
+def test_first_step_at_window_index_2_of_a_batch(backend_cls, oracle_lib, monkeypatch):
+    """k_solve runs one workgroup per window: the N_p = 114 window behind two decoys, at the same bar."""
+    import batch_helpers as bh
+    case = sh.CASE[sh.BATCH_CASE]
+    s, d, tr = run_case(backend_cls, monkeypatch, case, front=(bh.decoy(sh.PIXEL, "a"), bh.decoy(sh.PIXEL, "b")))
+    check_case(case, oracle_lib, s, d, tr, n_win=3, tag="@2")
+
+
+@pytest.mark.parametrize("n", [384, 402, 582])
+def test_bcr_and_the_band_solver_agree(backend_cls, oracle_lib, monkeypatch, n):
+    """The same window through block cyclic reduction and, with SADVIO_NO_BCR=1, through the sliding band solver: within
+    TOL_FACTOR x E_REF of each other (each is held to that bar against the 50-digit step by the test above)."""
+    a, b = sh.CASE[f"bcr{n}"], sh.CASE[f"nobcr{n}"]
+    w = sh.case_window(a)
+    da = _device.get(a.name) or run_case(backend_cls, monkeypatch, a)[1]
+    db = _device.get(b.name) or run_case(backend_cls, monkeypatch, b)[1]
+    ref = sh.reference(a, oracle_lib)
+    bar_p, bar_l = sh.bars(a)
+    ep = np.abs(sh.pose_part(da, w) - sh.pose_part(db, w)).max() / np.abs(sh.pose_part(ref, w)).max()
+    el = np.abs(da["lmk"] - db["lmk"]).max() / np.abs(ref["lmk"]).max()
+    print(f"FIRST_STEP bcr{n} against nobcr{n}: pose {ep / bar_p * sh.TOL_FACTOR:.2f} lmk {el / bar_l * sh.TOL_FACTOR:.2f}")
+    assert ep <= bar_p and el <= bar_l

@@ -126,7 +126,9 @@ def test_dense_reduced_system_edge_sizes(backend_cls, oracle_lib, n_keep):
     """The wide-panel dense solver (look-ahead panel loop, per-step back-substitution) at N_p = 75 + 3 n_keep = 192 (two panels
     exactly), 285 / 288 / 291 (three short of / exactly / three beyond a multiple of the 96-column panel) and 384: the last
     block's clamped loads sit at the end of the matrix (a fault found on a window at the end of the S allocation). N_p = 183,
-    below two panels, takes the 32-column panel solver (k_chol_panel / k_chol_update / k_chol_backsolve)."""
+    below two panels, takes the 32-column panel solver (k_chol_panel / k_chol_update / k_chol_backsolve). These are whole solves at
+    the 1e-6 bar; tests/test_gpu_first_step.py holds one step of both solvers (N_p = 180 / 186 and 192 / 198) to 64 x the float64
+    oracle's own distance from a 50-digit step."""
     w = make_vio_window(n_kf=6, n_lmk=900, seed=100 + n_keep)
     w.dense_prior = random_prior(w, n_keep, w.n_kf - 2, np.random.default_rng(n_keep), rank_deficit=3)
     compare(backend_cls, oracle_lib, w, capi.reference_options(), vio=True)
