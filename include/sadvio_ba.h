@@ -509,6 +509,48 @@ int sadvio_ba_linearize(sadvio_ba_handle *h, int32_t w, const double *pose_delta
 int sadvio_ba_landmark_chi2(sadvio_ba_handle *h, int32_t w, const double *pose_delta6, const double *lmk_delta3,
                             const double *image_wh, double pixel_sigma, double *avg_chi2, int32_t *inlier);
 
+/* The same gate for rigs whose cameras are not pinholes: every observation is projected by its camera's OWN model,
+ * as ALandmark::chi2err does through ImageSensor::project (Camera.cpp:26-52, fisheye.cpp:127-172, 195-240,
+ * DoubleSphere.cpp:33-78; restated on the host by project_camera of sadvio_cameras.hpp, which the device follows line
+ * for line). `models` = one entry per camera of window `w` in the caller's camera order; fx fy cx cy are the window's
+ * cam_K. Validity tests (a failed projection counts 1000): pinhole z < 0.1; the three fisheye laws z < 0.01; omni and
+ * double sphere return early with u = v = 0 when z < 0.1 and test the cone z <= -w d (w from alpha <= 0.5 or > 0.5);
+ * all models test [0,width]x[0,height] and finiteness. Omni applies p + distort(p) once when `distortion` is set.
+ *
+ * Measured pixel: `obs_uv` ([n_obs][2], the caller's observation order of the window) is used as it stands on both
+ * factor types (the reference compares with the feature's pixel). NULL: a pixel window uses obs_meas; an angular window
+ * uses the model's projection of the stored bearing with no validity test applied to it (a pinhole: K b / b_z + c, the
+ * expression of sadvio_ba_landmark_chi2). CAVEAT: Fisheye's ray is 0/0 at the principal point (Fisheye::getRayCamera
+ * divides by the radius), so the bearing stored for such a feature carries no pixel: a caller with features at the
+ * principal point of a fisheye camera passes `obs_uv`.
+ *
+ * Everything else is sadvio_ba_landmark_chi2: deltas (NULL = zeros), `pixel_sigma`, inlier = (n_obs >= 2 && !(avg > 2)),
+ * pseudo-observations of sparse prior factors are skipped. `obs_chi2` ([n_obs], caller's order, or NULL) receives each
+ * observation's term of the sum (1000 for a failed projection). A table of pinholes gives avg_chi2 the bits of
+ * sadvio_ba_landmark_chi2 with image_wh = the models' (width, height).
+ * Errors: SADVIO_E_STATE before set_windows or between begin_update and commit_update; SADVIO_E_INVALID_ARG for a null
+ * `models`, an unknown kind, a window out of range, or two cameras that the handle stores once (same K, T_s_f, sigma)
+ * whose models or image sizes differ (all fields are compared). The solve's deltas, summaries, trace and the handle's
+ * prior are untouched; outputs are written on success only. */
+#define SADVIO_CAM_PINHOLE 0
+#define SADVIO_CAM_FISHEYE_EQUIDISTANT 1
+#define SADVIO_CAM_FISHEYE_EQUISOLID 2
+#define SADVIO_CAM_FISHEYE_STEREOGRAPHIC 3
+#define SADVIO_CAM_OMNI 4
+#define SADVIO_CAM_DOUBLE_SPHERE 5
+typedef struct sadvio_camera_model {
+    int32_t kind;         /* SADVIO_CAM_* */
+    int32_t distortion;   /* Omni only: 1 = apply D */
+    double width, height; /* image bounds (the image_wh of sadvio_ba_landmark_chi2) */
+    double rmax;          /* Fisheye::_rmax */
+    double xi, alpha;     /* Omni / DoubleSphere */
+    double D[4];          /* k1 k2 p1 p2 */
+} sadvio_camera_model;
+
+int sadvio_ba_landmark_chi2_models(sadvio_ba_handle *h, int32_t w, const double *pose_delta6, const double *lmk_delta3,
+                                   const sadvio_camera_model *models, const double *obs_uv, double pixel_sigma,
+                                   double *avg_chi2, int32_t *inlier, double *obs_chi2);
+
 /* ---- visual-inertial initialisation: AOptimizer::VIInit (AOptimizer.cpp:448-581) ----
  * Unknowns: the gravity direction r_wi (2 parameters, R_w_i = exp_so3((r0, r1, 0)), :464-466, :537), one velocity
  * delta per frame that an IMUFactorInit touches (:459-463), the log-scale lambda (:478-481; constant unless

@@ -655,6 +655,10 @@ class HipOptimizer {
     // every window handed to the backend is also written to <dir>/window_NNNNNN.sadvio (include/sadvio_io.hpp)
     void set_dump_dir(const std::string& dir) { _dump_dir = dir; _dump_count = 0; }
 
+    // ALandmark::sanityCheck of maps with non-pinhole cameras: off (default) = the host loop host_chi2_gate; on = the device
+    // gate sadvio_ba_landmark_chi2_models, with the models of CameraModel::intrinsics() and the features' own pixels
+    void set_device_model_gate(bool on) { _device_model_gate = on; }
+
   private:
     struct Flat {   // the flattened window + the vectors it points into
         sadvio_flat_window w{};
@@ -663,6 +667,8 @@ class HipOptimizer {
         std::vector<uint8_t> kf_const, lc;
         std::vector<int> cam_base, lmk_src;
         std::vector<double> cam_wh;       // image size per flat camera (sanityCheck)
+        std::vector<sadvio_camera_model> cam_model;   // the model per flat camera, the feature's pixel per observation:
+        std::vector<double> obs_uv;                   // what sadvio_ba_landmark_chi2_models takes (sanityCheck on non-pinhole rigs)
         int n_non_kf_obs = 0;             // features skipped because their frame is not a key-frame
         int n_bad_camera = 0;             // features skipped because their camera index is not one of the frame's sensors
         bool any_non_pinhole = false, non_pinhole_pixel = false;
@@ -708,6 +714,15 @@ class HipOptimizer {
                 F.cam_T.insert(F.cam_T.end(), c.T_s_f.R, c.T_s_f.R + 9); F.cam_T.insert(F.cam_T.end(), c.T_s_f.t, c.T_s_f.t + 3);
                 F.cam_sigma.push_back(_angular ? 1.5 / (0.5 * (c.fx + c.fy)) : 1.0);    // …Analytic.h:46 / Angular….cpp:283
                 F.cam_wh.push_back(c.width > 0 ? c.width : 2.0 * c.cx); F.cam_wh.push_back(c.height > 0 ? c.height : 2.0 * c.cy);
+                const CameraIntrinsics ci = c.intrinsics();
+                static_assert((int)CameraKind::Pinhole == SADVIO_CAM_PINHOLE && (int)CameraKind::FisheyeEquidistant == SADVIO_CAM_FISHEYE_EQUIDISTANT &&
+                              (int)CameraKind::FisheyeEquisolid == SADVIO_CAM_FISHEYE_EQUISOLID && (int)CameraKind::FisheyeStereographic == SADVIO_CAM_FISHEYE_STEREOGRAPHIC &&
+                              (int)CameraKind::Omni == SADVIO_CAM_OMNI && (int)CameraKind::DoubleSphere == SADVIO_CAM_DOUBLE_SPHERE, "CameraKind follows SADVIO_CAM_*");
+                sadvio_camera_model cm{};
+                cm.kind = (int32_t)ci.kind; cm.distortion = ci.distortion ? 1 : 0; cm.width = ci.width; cm.height = ci.height;
+                cm.rmax = ci.rmax; cm.xi = ci.xi; cm.alpha = ci.alpha;
+                for (int a = 0; a < 4; a++) cm.D[a] = ci.D[a];
+                F.cam_model.push_back(cm);
             }
         }
         for (int l = 0; l < (int)map.landmarks.size(); l++) {
@@ -721,6 +736,7 @@ class HipOptimizer {
                 if (ft.camera < 0 || ft.camera >= (int)map.frames[ft.frame].cameras.size()) { F.n_bad_camera++; continue; }   // a feature of a sensor the frame does not carry
                 const CameraModel& c = map.frames[ft.frame].cameras[ft.camera];
                 F.obs_kf.push_back(ft.frame); F.obs_cam.push_back(F.cam_base[ft.frame] + ft.camera);
+                F.obs_uv.push_back(ft.u); F.obs_uv.push_back(ft.v);
                 if (_angular) {                                                          // getRayCamera of the feature's camera model
                     double b[3] = {0.0, 0.0, 1.0};
                     ray_camera(c.intrinsics(), ft.u, ft.v, b);
@@ -900,7 +916,11 @@ class HipOptimizer {
                 if (sadvio_ba_set_windows(_h, 1, &Fall.w) != SADVIO_OK) { _err = sadvio_ba_last_error(_h); return false; }
                 G = &Fall;
             }
-            if (F.any_non_pinhole) host_chi2_gate(map, F, inlier);   // the device gate projects with K only
+            if (F.any_non_pinhole && _device_model_gate) {           // every feature through its own camera model, on the device
+                if (sadvio_ba_landmark_chi2_models(_h, 0, nullptr, nullptr, G->cam_model.data(), G->obs_uv.data(), 1.0, nullptr, inlier.data(), nullptr) != SADVIO_OK) {
+                    _err = sadvio_ba_last_error(_h); return false;
+                }
+            } else if (F.any_non_pinhole) host_chi2_gate(map, F, inlier);   // sadvio_ba_landmark_chi2 projects with K only
             else if (sadvio_ba_landmark_chi2(_h, 0, nullptr, nullptr, G->cam_wh.data(), 1.0, nullptr, inlier.data()) != SADVIO_OK) {
                 _err = sadvio_ba_last_error(_h); return false;
             }
@@ -916,6 +936,7 @@ class HipOptimizer {
     std::string _dump_dir;
     int _dump_count = 0;
     int _skipped_bad_camera = 0;
+    bool _device_model_gate = false;
     int _eig_cut_mode = SADVIO_EIG_CUT_REFERENCE, _rel_eig_cut_mode = SADVIO_EIG_CUT_NOISE_FLOOR, _prior_form = SADVIO_PRIOR_FORM_CHOLESKY;
     sadvio_ba_handle* _h = nullptr;
     sadvio_solve_summary _sum{};

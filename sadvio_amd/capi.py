@@ -134,6 +134,30 @@ EIG_CUT = {"reference": 0, "noise_floor": 1}
 PRIOR_FORM = {"eigen": 0, "cholesky": 1}          # SADVIO_PRIOR_FORM_*
 
 
+class CameraModelC(C.Structure):
+    """sadvio_camera_model: one camera of sadvio_ba_landmark_chi2_models (fx fy cx cy come from the window's cam_K)."""
+    _fields_ = [("kind", C.c_int32), ("distortion", C.c_int32), ("width", C.c_double), ("height", C.c_double),
+                ("rmax", C.c_double), ("xi", C.c_double), ("alpha", C.c_double), ("D", C.c_double * 4)]
+
+
+CAM_PINHOLE, CAM_FISHEYE_EQUIDISTANT, CAM_FISHEYE_EQUISOLID, CAM_FISHEYE_STEREOGRAPHIC, CAM_OMNI, CAM_DOUBLE_SPHERE = range(6)
+
+
+def camera_models_c(models):
+    """A (CameraModelC * n) array from CameraModelC instances or dicts with its fields (absent fields: 0, rmax 1)."""
+    arr = (CameraModelC * max(1, len(models)))()
+    for i, m in enumerate(models):
+        if isinstance(m, CameraModelC):
+            C.memmove(C.byref(arr[i]), C.byref(m), C.sizeof(CameraModelC))
+            continue
+        a = arr[i]
+        a.kind, a.distortion = int(m["kind"]), int(m.get("distortion", 0))
+        a.width, a.height, a.rmax = float(m["width"]), float(m["height"]), float(m.get("rmax", 1.0))
+        a.xi, a.alpha = float(m.get("xi", 0.0)), float(m.get("alpha", 0.0))
+        a.D[:] = [float(x) for x in m.get("D", (0.0, 0.0, 0.0, 0.0))]
+    return arr
+
+
 class MargResultC(C.Structure):
     _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("n_full", C.c_int32), ("kf_col", C.c_int32),
                 ("sweeps_mm", C.c_int32), ("sweeps_k", C.c_int32)]
@@ -425,6 +449,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "sadvio_ba_covariance_batch"):   # (nor this one)
         lib.sadvio_ba_covariance_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CovBatchItemC)]
     lib.sadvio_ba_landmark_chi2.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, _dp, _ip]
+    if hasattr(lib, "sadvio_ba_landmark_chi2_models"):   # (an older build loaded through SADVIO_BA_LIB does not export it)
+        lib.sadvio_ba_landmark_chi2_models.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, C.POINTER(CameraModelC), _dp, C.c_double,
+                                                       _dp, _ip, _dp]
     lib.sadvio_ba_get_kernel_times.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), _dp, _lp]
     lib.sadvio_ba_last_error.argtypes = [C.c_void_p]
     lib.sadvio_ba_last_error.restype = C.c_char_p
@@ -746,6 +773,29 @@ class Backend:
         self._check(self.lib.sadvio_ba_landmark_chi2(self.h, w, _ptr(pd), _ptr(ld), _ptr(wh), pixel_sigma, _ptr(avg),
                                                      inl.ctypes.data_as(_ip)), "landmark_chi2")
         return avg, inl
+
+    def landmark_chi2_models(self, w: int, models, pose_delta=None, lmk_delta=None, obs_uv=None, pixel_sigma=0.0,
+                             want_obs=False, raw_rc=False):
+        """(avg_chi2[n_lmk], inlier[n_lmk][, obs_chi2[n_obs]]) — the gate of landmark_chi2 with every observation projected by
+        its camera's own model (sadvio_ba_landmark_chi2_models). models: one CameraModelC / dict per camera of window w;
+        obs_uv: [n_obs, 2] measured pixels in the window's observation order, or None. raw_rc: the return code comes first and
+        nothing raises (outputs are NaN / -1 filled, so that an untouched output shows)."""
+        win = self.windows[w] if 0 <= w < len(self.windows) else None
+        n_lmk, n_obs = (win.n_lmk, win.n_obs) if win is not None else (0, 0)
+        avg = np.full(n_lmk, np.nan) if raw_rc else np.zeros(n_lmk)
+        inl = np.full(n_lmk, -1, dtype=np.int32) if raw_rc else np.zeros(n_lmk, dtype=np.int32)
+        obs = (np.full(n_obs, np.nan) if raw_rc else np.zeros(n_obs)) if want_obs else None
+        pd = None if pose_delta is None else np.ascontiguousarray(pose_delta, dtype=np.float64)
+        ld = None if lmk_delta is None else np.ascontiguousarray(lmk_delta, dtype=np.float64)
+        uv = None if obs_uv is None else np.ascontiguousarray(obs_uv, dtype=np.float64)
+        arr = None if models is None else camera_models_c(models)
+        rc = self.lib.sadvio_ba_landmark_chi2_models(self.h, w, _ptr(pd), _ptr(ld), arr, _ptr(uv), pixel_sigma, _ptr(avg),
+                                                     inl.ctypes.data_as(_ip), _ptr(obs))
+        out = (avg, inl, obs) if want_obs else (avg, inl)
+        if raw_rc:
+            return (rc,) + out
+        self._check(rc, "landmark_chi2_models")
+        return out
 
     def vi_init(self, T_f_w, vel, factors, opts: SolveOptions = None, **kw):
         """AOptimizer::VIInit (AOptimizer.cpp:448-581) on the device; see make_viinit_problem for the arguments."""

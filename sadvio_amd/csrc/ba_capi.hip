@@ -1830,6 +1830,82 @@ int sadvio_ba_landmark_chi2(sadvio_ba_handle* h, int32_t w, const double* pose_d
     return SADVIO_OK;
 }
 
+static_assert(CAM_PINHOLE == SADVIO_CAM_PINHOLE && CAM_FISHEYE_EQUIDISTANT == SADVIO_CAM_FISHEYE_EQUIDISTANT && CAM_FISHEYE_EQUISOLID == SADVIO_CAM_FISHEYE_EQUISOLID &&
+              CAM_FISHEYE_STEREOGRAPHIC == SADVIO_CAM_FISHEYE_STEREOGRAPHIC && CAM_OMNI == SADVIO_CAM_OMNI && CAM_DOUBLE_SPHERE == SADVIO_CAM_DOUBLE_SPHERE,
+              "device_math.h restates the SADVIO_CAM_* kinds");
+
+int sadvio_ba_landmark_chi2_models(sadvio_ba_handle* h, int32_t w, const double* pose_delta6, const double* lmk_delta3, const sadvio_camera_model* models,
+                                   const double* obs_uv, double pixel_sigma, double* avg_chi2, int32_t* inlier, double* obs_chi2) {
+    if (!h) return SADVIO_E_INVALID_ARG;
+    if (!h->uploaded) { h->err = "landmark_chi2_models before set_windows"; return SADVIO_E_STATE; }
+    if (h->defer) { h->err = "landmark_chi2_models between begin_update and commit_update"; return SADVIO_E_STATE; }
+    if (w < 0 || w >= (int)h->wins.size()) { h->err = "landmark_chi2_models: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (!models) { h->err = "landmark_chi2_models: null model table"; return SADVIO_E_INVALID_ARG; }
+    const WinDev& d = h->wins[w].d;
+    const SrcWin& S = h->src[w];
+    // model and image bounds per stored camera (identical cameras are stored once; they must agree on both)
+    std::vector<double> wh(2 * (size_t)d.n_cam, -1.0);
+    std::vector<CamModelDev> md(std::max(d.n_cam, 1));
+    for (int c = 0; c < S.v.n_cam; c++) {
+        const sadvio_camera_model& m = models[c];
+        if (m.kind < SADVIO_CAM_PINHOLE || m.kind > SADVIO_CAM_DOUBLE_SPHERE) { h->err = "landmark_chi2_models: unknown camera kind"; return SADVIO_E_INVALID_ARG; }
+        const int u = S.cam_map[c];
+        CamModelDev q{};
+        q.rmax = m.rmax; q.xi = m.xi; q.alpha = m.alpha; q.kind = m.kind; q.distortion = m.distortion;
+        for (int i = 0; i < 4; i++) q.D[i] = m.D[i];
+        if (wh[2 * u] >= 0.0 && (wh[2 * u] != m.width || wh[2 * u + 1] != m.height || memcmp(&md[u], &q, sizeof(q)))) {
+            h->err = "landmark_chi2_models: cameras with identical (K, T_s_f, sigma) differ in model or image size"; return SADVIO_E_INVALID_ARG;
+        }
+        wh[2 * u] = m.width; wh[2 * u + 1] = m.height; md[u] = q;
+    }
+    if (d.n_lmk == 0) return SADVIO_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    // scratch: [wh | models | uv | xp | xl | obs | out] (the solved state of the handle stays readable); everything up to obs is
+    // staged on the host and goes up in ONE copy, obs | out come back in one. The tables hold this window's cameras only.
+    constexpr size_t MD = sizeof(CamModelDev) / sizeof(double);
+    const size_t n_wh = 2 * (size_t)d.n_cam, n_md = MD * (size_t)d.n_cam, n_ob = (size_t)d.n_obs, n_uv = obs_uv ? 2 * n_ob : 0;
+    const size_t n_xp = 6 * (size_t)d.n_kf, n_xl = 3 * (size_t)d.n_lmk, n_out = 2 * (size_t)d.n_lmk, n_up = n_wh + n_md + n_uv + n_xp + n_xl + n_ob;
+    HIP_TRY(h->d_probe.alloc(n_up + n_out));
+    double* d_wh = h->d_probe.p; double* d_md = d_wh + n_wh; double* d_uv = d_md + n_md; double* d_sxp = d_uv + n_uv; double* d_sxl = d_sxp + n_xp;
+    double* d_ob = d_sxl + n_xl;
+    std::vector<double> up(n_up, 0.0);   // deltas NULL = zeros; obs = 0 where no landmark lists the observation
+    memcpy(up.data(), wh.data(), sizeof(double) * n_wh);
+    memcpy(up.data() + n_wh, md.data(), sizeof(double) * n_md);
+    if (obs_uv)                          // the measured pixels in the stored observation order (obs_perm: stored position -> caller's index)
+        for (int a = 0; a < d.n_obs; a++) {
+            const int src = h->obs_perm[d.obs_base + a];
+            if (src >= 0) { up[n_wh + n_md + 2 * (size_t)a] = obs_uv[2 * (size_t)src]; up[n_wh + n_md + 2 * (size_t)a + 1] = obs_uv[2 * (size_t)src + 1]; }
+        }
+    if (pose_delta6) memcpy(up.data() + n_wh + n_md + n_uv, pose_delta6, sizeof(double) * n_xp);
+    if (lmk_delta3) memcpy(up.data() + n_wh + n_md + n_uv + n_xp, lmk_delta3, sizeof(double) * n_xl);
+    HIP_TRY(hipMemcpyAsync(d_wh, up.data(), sizeof(double) * n_up, hipMemcpyHostToDevice, h->stream));
+    SolveOpts o{};
+    DevPtrs P = make_ptrs(h, o, 1);
+    P.xp = d_sxp - 6 * (ptrdiff_t)d.kf_base; P.xl = d_sxl - 3 * (ptrdiff_t)d.lmk_base;  // the kernel indexes globally
+    const double* k_wh = d_wh - 2 * (ptrdiff_t)d.cam_base;                               // ... the camera tables too
+    const CamModelDev* k_md = (const CamModelDev*)d_md - (ptrdiff_t)d.cam_base;
+    const int blocks = (d.n_lmk + 63) / 64;
+    const double isig = pixel_sigma > 0.0 ? 1.0 / pixel_sigma : (h->factor_type == SADVIO_FACTOR_PIXEL ? 0.0 : 1.0);  // 0: cam_isig
+    const double* k_uv = obs_uv ? d_uv : nullptr;
+    if (h->factor_type == SADVIO_FACTOR_PIXEL) hipLaunchKernelGGL(k_lmk_chi2_models<0>, dim3(blocks), dim3(64), 0, h->stream, P, w, k_wh, k_md, k_uv, isig, d_ob + n_ob, d_ob);
+    else hipLaunchKernelGGL(k_lmk_chi2_models<1>, dim3(blocks), dim3(64), 0, h->stream, P, w, k_wh, k_md, k_uv, isig, d_ob + n_ob, d_ob);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> hb(n_ob + n_out);   // obs | out
+    HIP_TRY(hipMemcpyAsync(hb.data(), d_ob, sizeof(double) * hb.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const double* h_out = hb.data() + n_ob;
+    for (int l = 0; l < d.n_lmk; l++) {
+        if (avg_chi2) avg_chi2[l] = h_out[2 * (size_t)l];
+        if (inlier) inlier[l] = (h_out[2 * (size_t)l + 1] >= 2.0 && !(h_out[2 * (size_t)l] > 2.0)) ? 1 : 0;
+    }
+    if (obs_chi2)
+        for (int a = 0; a < d.n_obs; a++) {
+            const int src = h->obs_perm[d.obs_base + a];
+            if (src >= 0) obs_chi2[src] = hb[(size_t)a];
+        }
+    return SADVIO_OK;
+}
+
 int sadvio_ba_get_kernel_times(sadvio_ba_handle* h, int32_t cap, const char** names, double* avg_us, int64_t* launches) {
     if (!h) return SADVIO_E_INVALID_ARG;
     int n = 0;

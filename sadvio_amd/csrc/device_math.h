@@ -803,4 +803,69 @@ __device__ __noinline__ void line_angular_factor(const double* T0, const double*
     }
 }
 
+// ---- camera models of the chi2 gate (ALandmark::chi2err projects with the feature's own sensor) ----
+// One entry per STORED camera of the handle; fx fy cx cy stay in cam_K, the image bounds in the gate's wh table.
+enum { CAM_PINHOLE = 0, CAM_FISHEYE_EQUIDISTANT = 1, CAM_FISHEYE_EQUISOLID = 2, CAM_FISHEYE_STEREOGRAPHIC = 3, CAM_OMNI = 4, CAM_DOUBLE_SPHERE = 5 };
+struct CamModelDev {
+    double rmax, xi, alpha, D[4];
+    int kind, distortion;
+};
+static_assert(sizeof(CamModelDev) == 64, "the model table is laid out in the FP64 probe scratch");
+
+// project(T_w_lmk, model, scale, p2ds) of each ImageSensor for a point p in the CAMERA frame: the arithmetic of
+// project_camera (include/sadvio_cameras.hpp) line for line, with each model's own validity tests (Camera.cpp:26-52,
+// fisheye.cpp:127-172, 195-240, DoubleSphere.cpp:33-78). K = fx fy cx cy, wh = width height. Returns the verdict
+// (false = the feature counts 1000); (u, v) is what the reference leaves in p2ds either way.
+__device__ inline bool project_model(const CamModelDev& c, const double* K, const double* wh, const double* p, double& u, double& v) {
+    const double x = p[0], y = p[1], z = p[2];
+    bool ok;
+    switch (c.kind) {
+    case CAM_PINHOLE:
+        u = (K[0] * x + K[2] * z) / z; v = (K[1] * y + K[3] * z) / z;
+        ok = !(z < 0.1);
+        break;
+    case CAM_FISHEYE_EQUIDISTANT:
+    case CAM_FISHEYE_EQUISOLID:
+    case CAM_FISHEYE_STEREOGRAPHIC: {
+        const double r = sqrt(x * x + y * y + z * z), theta = acos(z / r), al = atan2(y, x);
+        double rd;
+        if (c.kind == CAM_FISHEYE_EQUIDISTANT) rd = K[0] * theta;
+        else if (c.kind == CAM_FISHEYE_EQUISOLID) rd = 2.0 * K[0] * sin(theta / 2.0);
+        else rd = 2.0 * K[0] * tan(theta / 2.0);
+        u = rd * cos(al) * c.rmax + K[2]; v = rd * sin(al) * c.rmax + K[3];
+        ok = !(z < 0.01);
+        break;
+    }
+    case CAM_OMNI: {
+        if (z < 0.1) { u = v = 0.0; return false; }
+        const double d = sqrt(x * x + y * y + z * z), zz = z + c.xi * d;
+        double px = x / zz, py = y / zz;
+        if (c.distortion) {   // Omni::distort returns p + d (fisheye.cpp:176-193)
+            const double k1 = c.D[0], k2 = c.D[1], p1 = c.D[2], p2 = c.D[3];
+            const double mx2 = px * px, my2 = py * py, mxy = px * py, rho2 = mx2 + my2, rad = k1 * rho2 + k2 * rho2 * rho2;
+            const double dx = px * rad + 2.0 * p1 * mxy + p2 * (rho2 + 2.0 * mx2), dy = py * rad + 2.0 * p2 * mxy + p1 * (rho2 + 2.0 * my2);
+            px += dx; py += dy;
+        }
+        u = K[0] * px / (1.0 - c.alpha) + K[2]; v = K[1] * py / (1.0 - c.alpha) + K[3];
+        const double w = c.alpha <= 0.5 ? c.alpha / (1.0 - c.alpha) : (1.0 - c.alpha) / c.alpha;
+        ok = !(z <= -w * d);
+        break;
+    }
+    case CAM_DOUBLE_SPHERE: {
+        if (z < 0.1) { u = v = 0.0; return false; }
+        const double d1 = sqrt(x * x + y * y + z * z), zs = c.xi * d1 + z, d2 = sqrt(x * x + y * y + zs * zs);
+        const double den = c.alpha * d2 + (1.0 - c.alpha) * zs;
+        u = K[0] * (x / den) + K[2]; v = K[1] * (y / den) + K[3];
+        const double w1 = c.alpha <= 0.5 ? c.alpha / (1.0 - c.alpha) : (1.0 - c.alpha) / c.alpha;
+        const double w2 = (w1 + c.xi) / sqrt(2.0 * w1 * c.xi + c.xi * c.xi + 1.0);
+        ok = !(z <= -w2 * d1);
+        break;
+    }
+    default:   // the host refuses an unknown kind before the launch
+        u = v = 0.0;
+        return false;
+    }
+    return ok && !(u < 0.0 || v < 0.0 || u > wh[0] || v > wh[1]) && isfinite(u) && isfinite(v);
+}
+
 }  // namespace sadvio

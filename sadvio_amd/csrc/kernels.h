@@ -3251,4 +3251,60 @@ __global__ void k_lmk_chi2(DevPtrs P, int w, const double* wh, double inv_sigma_
     out[2 * l + 1] = (double)n;
 }
 
+// The same gate with every observation projected by its camera's own model (project_model, device_math.h): what
+// ALandmark::chi2err computes on the fisheye / omni / double-sphere rigs. Pose composition and accumulation order are
+// k_lmk_chi2's. wh / models are indexed by stored camera (global), uv and obs_out by the observation's position in the
+// window. uv = the measured pixels (null: obs_meas on pixel windows, the model's projection of the stored bearing on
+// angular ones — for a pinhole k_lmk_chi2's own K b / b_z + c, so that a pinhole-only table reproduces it to the bit).
+template <int FACTOR>
+__global__ void k_lmk_chi2_models(DevPtrs P, int w, const double* wh, const CamModelDev* models, const double* uv, double inv_sigma_px,
+                                  double* out, double* obs_out) {
+    const WinDev W = P.win[w];
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= W.n_lmk) return;
+    const long long gl = W.lmk_base + l;
+    const double pw[3] = {P.lmk_p[3 * gl] + P.xl[3 * gl], P.lmk_p[3 * gl + 1] + P.xl[3 * gl + 1], P.lmk_p[3 * gl + 2] + P.xl[3 * gl + 2]};
+    double sum = 0.0;
+    int n = 0;
+    for (int o = P.lmk_ob[gl]; o < P.lmk_oe[gl]; o++) {
+        const int kf = P.obs_kf[o], cam = P.obs_cam[o];
+        const long long a = o - W.obs_base;
+        if (cam < 0) {  // pseudo-observation of a sparse prior factor
+            if (obs_out) obs_out[a] = 0.0;
+            continue;
+        }
+        double d6[6], dR[9], R[9], pf[3], pc[3];
+        for (int i = 0; i < 6; i++) d6[i] = P.xp[6 * (long long)kf + i];
+        const double* T0 = P.kf_T0 + 12 * (long long)kf;
+        so3_exp(d6, dR);
+        m3_mul(T0, dR, R);
+        double t[3];
+        m3_vec(T0, d6 + 3, t);
+        m3_vec(R, pw, pf);
+        for (int i = 0; i < 3; i++) pf[i] += t[i] + T0[9 + i];
+        const double* Ts = P.cam_T + 12 * (long long)cam;
+        m3_vec(Ts, pf, pc);
+        for (int i = 0; i < 3; i++) pc[i] += Ts[9 + i];
+        const double* K = P.cam_K + 4 * (long long)cam;
+        const CamModelDev M = models[cam];
+        double u, v, mu, mv;
+        const bool ok = project_model(M, K, wh + 2 * (long long)cam, pc, u, v);
+        if (uv) { mu = uv[2 * a]; mv = uv[2 * a + 1]; }
+        else if (FACTOR == 0) { mu = P.obs_meas[2 * (long long)o]; mv = P.obs_meas[2 * (long long)o + 1]; }
+        else {
+            const double* b = P.obs_meas + 3 * (long long)o;
+            if (M.kind == CAM_PINHOLE) { mu = K[0] * b[0] / b[2] + K[2]; mv = K[1] * b[1] / b[2] + K[3]; }
+            else project_model(M, K, wh + 2 * (long long)cam, b, mu, mv);   // the pixel only: no validity test on a measurement
+        }
+        const double is = inv_sigma_px > 0.0 ? inv_sigma_px : P.cam_isig[cam];
+        const double e0 = (u - mu) * is, e1 = (v - mv) * is;
+        const double term = ok ? e0 * e0 + e1 * e1 : 1000.0;
+        sum += term;
+        if (obs_out) obs_out[a] = term;
+        n++;
+    }
+    out[2 * l] = n ? sum / (double)n : 0.0;
+    out[2 * l + 1] = (double)n;
+}
+
 }  // namespace sadvio
