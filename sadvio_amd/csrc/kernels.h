@@ -107,10 +107,11 @@ struct DevPtrs {
 #define SADVIO_TS(slot_, idx_) do { if ((P.debug & 4096) && blockIdx.x == 0 && threadIdx.x == 0 && slot == (slot_)) P.dbg_ts[idx_] = wall_clock64(); } while (0)
 #define SADVIO_TS_PTR(cond_) ((cond_) ? P.dbg_ts : nullptr)
 // Per-workgroup record of one k_build launch (slot 3): | start | end | XCC id << 32 | HW_ID (gfx9 layout: SIMD 5:4, CU 11:8, SH 12,
-// SE 15:13) | - | behind the 128 phase slots. Shows which workgroups share a CU and when each of them ends (scripts/gpu_time_tiles.py).
+// SE 15:13) | waves whose 8 landmarks list the same key-frames in the same lanes (`uniform`) << 32, most head lanes in a wave | behind the 128 phase slots. Shows which workgroups share a CU and when each of them ends (scripts/gpu_time_tiles.py).
 constexpr int DBG_WG_MAX = 1024, DBG_WG_BASE = 128, DBG_SLOTS = DBG_WG_BASE + 4 * DBG_WG_MAX;
 #define SADVIO_WG_TS(slot_, which_) do { if ((P.debug & 4096) && blockIdx.x < DBG_WG_MAX && threadIdx.x == 0 && slot == (slot_)) { \
         P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + (which_)] = wall_clock64(); \
+        if ((which_) == 0) P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + 3] = 0; \
         if ((which_) == 0) P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + 2] = ((long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)); } } while (0)
 #else
 #define SADVIO_TS(slot_, idx_) do { } while (0)
@@ -302,7 +303,7 @@ __device__ __forceinline__ double xor32_sum(double v) {
     auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
     return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
 }
-__device__ __forceinline__ int xor16_other(int v) {  // the value held by lane ^ 16
+__device__ __forceinline__ int xor16_other(int v) {  // the value held by lane ^ 16 (SADVIO_KERNEL_TS builds: the tile-sum counters of k_build)
     auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
     return (int)((threadIdx.x & 16) ? a[0] : a[1]);
 }
@@ -322,13 +323,6 @@ __device__ __forceinline__ double group_sum(double v, int G) {
     if (G >= 64) v = xor32_sum(v);
     return v;
 }
-// Sum over the 64 / 8 groups of a wave, lane q of every group receives the total of lanes q (G = 8 only).
-__device__ __forceinline__ double across_groups8_sum(double v) {
-    v += dpp_f64<0x128>(v);  // row_ror:8 (xor 8)
-    v = xor16_sum(v);
-    return xor32_sum(v);
-}
-
 // ceres::HuberLoss(a) + Corrector (rho'' <= 0 branch): returns rho(|r|^2) and the scale sqrt(rho') for r and J.
 __device__ __forceinline__ double huber_rho(double a, double s, double& scale) {
     scale = 1.0;
@@ -688,7 +682,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
     double cost_part = 0.0, fixed_part = 0.0, gmax_part = 0.0;
     // MFMA path: a tile may hold several rounds of landmarks per wave (batched windows: fewer, larger tiles amortise the
     // table staging, the merge and the flush). The Y E^T products accumulate in registers across the rounds; the
-    // block-diagonal / gradient sums go to the tile with ds_add_f64 (one lane per entry and wave after the DPP sums).
+    // block-diagonal / gradient sums go to the tile with ds_add_f64 from the head lane of every run of observations on one key-frame.
     typedef double d4 __attribute__((ext_vector_type(4)));
     d4 accs[3] = {(d4){0.0, 0.0, 0.0, 0.0}, (d4){0.0, 0.0, 0.0, 0.0}, (d4){0.0, 0.0, 0.0, 0.0}};  // <= 2 x 2 lower tile pairs (Nt <= 32)
     for (int base = wv * lpw; base < nl; base += BUILD_WAVES * lpw) {
@@ -746,9 +740,11 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
             // (2) Y / E go with plain stores into wave-private strips [row][k], k = 4 * landmark + c: distinct
             //     landmarks own distinct k, so nothing collides; sum_l Y_l E_l^T is then a K-contraction on the
             //     FP64 matrix cores (one v_mfma_f64_16x16x4_f64 chain per 16x16 block);
-            // (3) the block-diagonal part and the gradients are summed across the wave's 8 landmarks with DPP /
-            //     v_permlane swaps when all of them see the same key-frames in the same lanes (the common case for
-            //     landmarks created together), else with ds_add_f64.
+            // (3) the block-diagonal part and the gradients go to the tile with ds_add_f64 from the run heads. (Until tile sums were
+            //     stamped, a wave whose 8 landmarks list the same key-frames in the same lanes - 3 of 4 waves on config 2 - summed them
+            //     across its groups with DPP / v_permlane swaps first and added from one group: ~ 330 more VALU instructions on a wave
+            //     that is bound by instruction issue, to spare LDS adds that cost it nothing: those waves were the workgroup's last by
+            //     0.8 us. docs/KERNEL_HISTORY.md "Tile sums".)
             constexpr int Kw = 32, KS = Kw + 2;   // G == 8 on this path: 8 landmarks per wave and round
             double* Yb = wstage;
             const double* Eb = Yb;
@@ -817,10 +813,18 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
             }
             // block-diagonal part D = Jp^T Jp (21) + reduced / full gradient (6 + 6)
             {
-                const int rowu = vrow ? L.row : -1;
-                int mism = (dpp_i32<0x128>(rowu) != rowu) | (xor16_other(rowu) != rowu) | (xor32_other(rowu) != rowu);
-                const bool uniform = (G == 8) && (__ballot(mism) == 0ull);
-                const bool adder = head && (!uniform || grp == 0);   // uniform: the wave's 8 landmarks were summed with DPP
+#ifdef SADVIO_KERNEL_TS
+                {   // how full the wave is, and whether its 8 landmarks list the same key-frames in the same lanes (`uniform`)
+                    const int rowu = vrow ? L.row : -1;
+                    const int mism = (dpp_i32<0x128>(rowu) != rowu) | (xor16_other(rowu) != rowu) | (xor32_other(rowu) != rowu);
+                    const bool uniform = (G == 8) && (__ballot(mism) == 0ull);
+                    const int nheads = __popcll(__ballot(head));
+                    if ((P.debug & 4096) && slot == 3 && blockIdx.x < DBG_WG_MAX && ln == 0) {
+                        atomicMax((int*)&P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + 3], nheads);
+                        if (uniform) atomicAdd((int*)&P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + 3] + 1, 1);
+                    }
+                }
+#endif
 #pragma unroll
                 for (int i = 0; i < 6; i++) {
                     const double j0 = vrow ? L.Jp[i] : 0.0, j1 = vrow ? L.Jp[6 + i] : 0.0;
@@ -831,8 +835,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
                         const double vn = dpp_f64<0x101>(v);
                         if (has_follower) v += vn;
                         if (RARE) { const double vn2 = dpp_f64<0x102>(v); if (has_follower2) v += vn2; }
-                        if (uniform) v = across_groups8_sum(v);
-                        if (adder) { atomic_add_f64(&Stile[tri(myrow + i, myrow + j)], v); if (i == j) atomic_add_f64(&hdT[myrow + i], v); }
+                        if (head) { atomic_add_f64(&Stile[tri(myrow + i, myrow + j)], v); if (i == j) atomic_add_f64(&hdT[myrow + i], v); }
                     }
                 }
 #pragma unroll
@@ -845,8 +848,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
                         const double grn2 = dpp_f64<0x102>(gr), gfn2 = dpp_f64<0x102>(gf);
                         if (has_follower2) { gr += grn2; gf += gfn2; }
                     }
-                    if (uniform) { gr = across_groups8_sum(gr); gf = across_groups8_sum(gf); }
-                    if (adder) { atomic_add_f64(&gT[myrow + i], gr); atomic_add_f64(&gfT[myrow + i], gf); }
+                    if (head) { atomic_add_f64(&gT[myrow + i], gr); atomic_add_f64(&gfT[myrow + i], gf); }
                 }
             }
     SADVIO_TS(3, 39);

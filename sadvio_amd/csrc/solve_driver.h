@@ -577,6 +577,15 @@ void print_debug_stamps(sadvio_ba_handle* h, int n_tiles) {
             fprintf(stderr, "[sadvio dbg] k_build wg %zu start %.2f end %.2f xcc %d se %u sh %u cu %u simd %u\n", b, (wg[4 * b] - wg[0]) * 0.01, (wg[4 * b + 1] - wg[0]) * 0.01,
                     (int)((wg[4 * b + 2] >> 32) & 15), (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 15, (hw >> 4) & 3);
         }
+    // the tile sums of that launch: how many waves are `uniform` (8 landmarks with the same key-frames in the same lanes), and the head lanes of each workgroup's fullest wave
+    long long uni = 0, over32 = 0, hmax = 0, hsum = 0;
+    for (size_t b = 0; b < wg.size() / 4; b++) {
+        const long long heads = wg[4 * b + 3] & 0xffffffffLL;
+        uni += wg[4 * b + 3] >> 32; hmax = std::max(hmax, heads); hsum += heads; over32 += heads > 32;
+    }
+    if (!wg.empty())
+        fprintf(stderr, "[sadvio dbg] k_build tile sums: %lld uniform waves in %zu workgroups; most head lanes in a wave %lld (mean of the workgroups' fullest waves %.1f), workgroups with a wave above 32 heads %lld\n",
+                uni, wg.size() / 4, hmax, (double)hsum / (double)(wg.size() / 4), over32);
 #endif
 }
 
