@@ -7,265 +7,7 @@
 // There is no CPU fallback: without a gfx950 device every compute call fails.
 #include "ba_handle.h"
 #include "solve_driver.h"
-
-namespace {
-
-// J^T of a dense prior, once per upload (J is constant during the solve); H = J^T J is a k_mgemm launch (FP64 matrix cores:
-// the one-thread-per-entry loop this replaces took 0.92 ms at n = 915, more than the layout build itself).
-__global__ void k_dense_prior_prepare(const double* J, double* Jt, int nf, int n) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < (long long)nf * n) {
-        const int i = (int)(idx / n), a = (int)(idx - (long long)i * n);
-        Jt[(size_t)a * nf + i] = J[idx];
-    }
-}
-
-// H = the symmetric matrix whose lower triangle is A's (the marginalisation's Ak, read like Eigen reads it)
-__global__ void k_sym_from_lower(const double* __restrict__ A, int n, double* __restrict__ H) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)n * n) return;
-    const int i = (int)(idx / n), j = (int)(idx - (long long)i * n);
-    H[idx] = i >= j ? A[idx] : A[(size_t)j * n + i];
-}
-
-// Layout of the reduced systems of all windows: [free key-frames (dpf each) | prior-kept landmarks (3 each)].
-// Called by set_windows and again by set_dense_prior (kept landmarks enlarge the reduced system).
-int layout_reduced(sadvio_ba_handle* h) {
-    const int n_windows = (int)h->wins.size();
-    // a resident prior that changed after it was attached is refused BEFORE anything is queued in h->up: a non-fatal return with
-    // items in the batch would scatter them, stale, with the next successful flush (the device buffers are grow-only)
-    for (int w = 0; w < n_windows && w < (int)h->dprior_per_win.size(); w++) {
-        const DensePriorHost& D = h->dprior_per_win[w];
-        if (D.n_full > 0 && D.resident && (!h->prior.valid || h->prior.serial != D.serial || h->prior.n_full != D.n_full || h->prior.n != D.n)) {
-            h->up.reset();
-            h->err = "the handle's prior changed after set_dense_prior(SADVIO_PRIOR_RESIDENT) attached it to a window: attach it again"; return SADVIO_E_STATE;
-        }
-    }
-    int red_b = 0; long long s_b = 0;
-    h->max_np = 0; h->n_big = 0;
-    std::vector<int> lmk_red(std::max(h->n_lmk_tot, 1), -1);
-    std::vector<unsigned char> lmk_const = h->h_lmk_const_user;
-    std::vector<int> kept, dp_ints;
-    std::vector<SparseDev> sparse;
-    std::vector<int> sp_list;
-    std::vector<LineDev> lines;
-    std::vector<LineObsDev> lobs;
-    long long dp_total = 0;   // doubles of d_dp_data: per window [J | J^T | J^T J | r0 | dx | r | cost slot]
-    bool any_red = false;
-    struct Prep { long long off; int nf, n, w; };
-    std::vector<Prep> preps;
-    for (int w = 0; w < n_windows; w++) {
-        WinDev& d = h->wins[w].d;
-        const DensePriorHost& D = h->dprior_per_win[w];
-        int n_red = 0;
-        d.dp_n_full = d.dp_n = 0; d.dp_off = 0; d.dp_int_off = 0;
-        d.kept_begin = (int)kept.size() / 3;
-        if (D.n_full > 0) {
-            const int n = D.n, nf = D.n_full;
-            std::vector<int> kind(n, -1), index(n, 0), col(n, -1);
-            if (D.kf_keep >= 0) {
-                const int g = d.kf_base + D.kf_keep, fi = h->h_kf_fidx[g];
-                for (int q = 0; q < 15; q++) {
-                    const int a = D.kf_col + q;
-                    if (q < 6) { kind[a] = 0; index[a] = 6 * g + q; }
-                    else { kind[a] = 1 + (q - 6) / 3; index[a] = 3 * g + (q - 6) % 3; }
-                    col[a] = (fi >= 0 && q < d.dpf) ? fi * d.dpf + q : -1;
-                }
-            }
-            for (size_t i = 0; i < D.lmk_index.size(); i++) {
-                if (D.lmk_col[i] < 0) continue;
-                const int gl = d.lmk_base + D.lmk_index[i];
-                const bool is_const = lmk_const[gl] == 1;
-                if (!is_const) {
-                    lmk_red[gl] = d.dpf * d.n_free_kf + 3 * n_red; n_red++;
-                    lmk_const[gl] = 2; any_red = true;
-                    for (int o = h->h_lmk_ob[gl]; o < h->h_lmk_oe[gl]; o++) { kept.push_back(o); kept.push_back(gl); kept.push_back(w); }
-                }
-                for (int a = 0; a < 3; a++) {
-                    kind[D.lmk_col[i] + a] = 4; index[D.lmk_col[i] + a] = 3 * gl + a;
-                    col[D.lmk_col[i] + a] = is_const ? -1 : lmk_red[gl] + a;
-                }
-            }
-            d.dp_n_full = nf; d.dp_n = n;
-            d.dp_int_off = (int)dp_ints.size();
-            dp_ints.insert(dp_ints.end(), kind.begin(), kind.end());
-            dp_ints.insert(dp_ints.end(), index.begin(), index.end());
-            dp_ints.insert(dp_ints.end(), col.begin(), col.end());
-            d.dp_off = dp_total;
-            preps.push_back({d.dp_off, nf, n, w});
-            dp_total += (long long)nf * n + (long long)n * nf + (long long)n * n + nf + n + nf + 2 + 3LL * ((nf + 3) / 4);   // J, Jt, H (device-filled), r0, dx, r scratch, cost slot, -, row-block partial sums (sharded windows)
-            dp_total += dp_total & 1;
-        }
-        // landmarks touched by sparse prior factors stay in the reduced system as well
-        d.sp_begin = (int)sparse.size();
-        d.spl_begin = (int)sp_list.size();
-        for (size_t sk = 0; sk < h->sparse_per_win[w].size(); sk++) {
-            const sadvio_sparse_prior& s = h->sparse_per_win[w][sk];
-            SparseDev o{};
-            o.type = s.type; o.win = w;
-            const bool elim = w < (int)h->sp_elim.size() && sk < h->sp_elim[w].size() && h->sp_elim[w][sk];
-            if (elim) {
-                // rides the Schur elimination as two pseudo-observations of its landmark: only its constants are needed
-                o.type = 4; o.kf = d.kf_base + s.kf; o.lmk0 = d.lmk_base + s.lmk0; o.lmk1 = -1;
-                memcpy(o.delta, s.delta, 24); memcpy(o.W, s.sqrt_inf, sizeof(o.W));
-                sparse.push_back(o);
-                continue;
-            }
-            o.kf = s.kf >= 0 ? d.kf_base + s.kf : -1;
-            const bool rel = s.type == SADVIO_SPARSE_RELATIVE_POSE;
-            if (rel) { o.type = 5; o.kf2 = d.kf_base + s.kf_b; }   // internal type 4 is the pseudo-observation form above
-            const int ls[2] = {(s.type == SADVIO_SPARSE_IMU_PRIOR || rel) ? -1 : s.lmk0, s.type == SADVIO_SPARSE_LMK_TO_LMK ? s.lmk1 : -1};
-            int gls[2] = {-1, -1};
-            for (int q = 0; q < 2; q++) {
-                if (ls[q] < 0) continue;
-                const int gl = d.lmk_base + ls[q];
-                gls[q] = gl;
-                if (lmk_const[gl] == 1 || lmk_red[gl] >= 0) continue;
-                lmk_red[gl] = d.dpf * d.n_free_kf + 3 * n_red; n_red++;
-                lmk_const[gl] = 2; any_red = true;
-                for (int ob = h->h_lmk_ob[gl]; ob < h->h_lmk_oe[gl]; ob++) { kept.push_back(ob); kept.push_back(gl); kept.push_back(w); }
-            }
-            o.lmk0 = gls[0]; o.lmk1 = gls[1];
-            memcpy(o.T_prior, s.T_prior, sizeof(o.T_prior)); memcpy(o.v_prior, s.v_prior, 24); memcpy(o.ba_prior, s.ba_prior, 24);
-            memcpy(o.bg_prior, s.bg_prior, 24); memcpy(o.delta, s.delta, 24); memcpy(o.W, s.sqrt_inf, sizeof(o.W));
-            sp_list.push_back((int)sparse.size());
-            sparse.push_back(o);
-        }
-        d.sp_end = (int)sparse.size();
-        d.spl_end = (int)sp_list.size();
-        d.kept_end = (int)kept.size() / 3;
-        d.n_red = n_red;
-        d.Np = d.n_free_kf * d.dpf + 3 * n_red;
-        // linexd landmarks: 6 columns each after the kept landmarks
-        d.line_begin = (int)lines.size(); d.lobs_begin = (int)lobs.size();
-        if (w < (int)h->lines_per_win.size()) {
-            const LineSetHost& LS = h->lines_per_win[w];
-            for (int l = 0; l < LS.n(); l++) {
-                LineDev o{};
-                memcpy(o.T, &LS.T[12 * (size_t)l], 96); memcpy(o.model, &LS.model[6 * (size_t)l], 48);
-                o.win = w; o.col = -1;
-                if (!(LS.is_const.size() && LS.is_const[l])) { o.col = d.Np; d.Np += 6; }
-                const int ms = d.factor_type == SADVIO_FACTOR_PIXEL ? 4 : 6;
-                for (int ob = LS.ptr[l]; ob < LS.ptr[l + 1]; ob++) {
-                    LineObsDev q{};
-                    q.line = (int)lines.size(); q.kf = d.kf_base + LS.obs_kf[ob]; q.cam = d.cam_base + h->src[w].cam_map[LS.obs_cam[ob]]; q.win = w;
-                    memcpy(q.meas, &LS.meas[(size_t)ms * ob], sizeof(double) * ms);
-                    lobs.push_back(q);
-                }
-                lines.push_back(o);
-            }
-        }
-        d.line_end = (int)lines.size(); d.lobs_end = (int)lobs.size();
-        // reduced systems that fit LDS are kept as a packed lower triangle (16-byte aligned); larger ones as a
-        // full row-major matrix (lower triangle used) that the library factorisation works on in place
-        d.ld = d.Np > MAX_LDS_NP ? d.Np : 0;
-        d.S_off = s_b; d.red_off = red_b;
-        red_b += d.Np; s_b += d.ld ? (((long long)d.Np * d.Np + 1) & ~1LL) : (long long)c16_size(d.Np);   // LDS-sized systems: the tile-packed image of chol16.h
-        if (d.ld) h->n_big++; else h->max_np = std::max(h->max_np, d.Np);
-        for (int ti = d.tile_begin; ti < d.tile_end; ti++) {
-            Tile& t = h->tiles[ti];
-            t.Np = d.Np; t.red_off = d.red_off; t.S_off = d.S_off; t.ld = d.ld;
-        }
-    }
-    h->np_tot = red_b; h->s_tot = s_b;
-    h->n_kept = (int)kept.size() / 3;
-    h->has_lmk_const = h->user_lmk_const || any_red;
-    // one allocation [S | gred | gfull | hdiag | rank_b]: a window sharded over several GPUs all-reduces it whole
-    const long long nrb = (long long)n_windows * h->world * 4;
-    h->red_total = s_b + 3LL * red_b + nrb;
-    HIP_TRY(h->d_S.alloc((size_t)std::max<long long>(h->red_total, 1)));
-    h->d_gred.set_view(h->d_S.p + s_b, (size_t)red_b); h->d_gfull.set_view(h->d_gred.p + red_b, (size_t)red_b);
-    h->d_hdiag.set_view(h->d_gfull.p + red_b, (size_t)red_b); h->d_rank_b.set_view(h->d_hdiag.p + red_b, (size_t)nrb);
-    HIP_TRY(h->d_rank_s.alloc((size_t)nrb));
-    HIP_TRY(h->d_delta.alloc((size_t)std::max(red_b, 1))); HIP_TRY(h->d_s_pose.alloc((size_t)std::max(red_b, 1)));
-    HIP_TRY(hipMemsetAsync(h->d_S.p, 0, sizeof(double) * (size_t)std::max<long long>(h->red_total, 1), h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_rank_s.p, 0, sizeof(double) * (size_t)nrb, h->stream));
-    HIP_TRY(h->d_sparse.alloc(std::max<size_t>(sparse.size(), 1))); HIP_TRY(h->d_sp_scratch.alloc(2 * std::max<size_t>(sparse.size(), 1) * SPARSE_J)); h->n_sparse_tot = sparse.size();
-    h->up.add(h->d_sparse.p, sparse.data(), sparse.size() * sizeof(SparseDev));
-    HIP_TRY(h->d_sp_list.alloc(std::max<size_t>(sp_list.size(), 1)));
-    h->n_sp_list = (int)sp_list.size();
-    h->up.add(h->d_sp_list.p, sp_list.data(), sp_list.size() * sizeof(int));
-    h->n_line_tot = (int)lines.size(); h->n_lobs_tot = (int)lobs.size();
-    HIP_TRY(h->d_lines.alloc(std::max<size_t>(lines.size(), 1))); HIP_TRY(h->d_lobs.alloc(std::max<size_t>(lobs.size(), 1)));
-    HIP_TRY(h->d_xline.alloc(std::max<size_t>(12 * lines.size(), 1))); HIP_TRY(h->d_line_scratch.alloc(std::max<size_t>(lobs.size(), 1) * LINE_ROW));
-    h->up.add(h->d_lines.p, lines.data(), lines.size() * sizeof(LineDev));
-    h->up.add(h->d_lobs.p, lobs.data(), lobs.size() * sizeof(LineObsDev));
-    if (kept.empty()) kept.assign(3, 0);
-    if (dp_ints.empty()) dp_ints.push_back(0);
-    HIP_TRY(h->d_tiles.alloc(h->tiles.size())); HIP_TRY(h->d_lmk_red.alloc(lmk_red.size())); HIP_TRY(h->d_lmk_const.alloc(lmk_const.size()));
-    HIP_TRY(h->d_kept_obs.alloc(kept.size())); HIP_TRY(h->d_dp_ints.alloc(dp_ints.size())); HIP_TRY(h->d_dp_data.alloc((size_t)std::max<long long>(dp_total, 1)));
-#define UP(dst, src) h->up.add((dst).p, (src).data(), (src).size() * sizeof((src)[0]))
-    UP(h->d_tiles, h->tiles); UP(h->d_lmk_red, lmk_red); UP(h->d_lmk_const, lmk_const); UP(h->d_kept_obs, kept);
-    UP(h->d_dp_ints, dp_ints);
-#undef UP
-    // the dense priors' data never exists as one host array: scratch parts are zeroed on the device, J and r0 come from the
-    // caller's copy (staged upload) or from the handle's prior (device to device, no PCIe traffic)
-    if (!preps.empty()) HIP_TRY(hipMemsetAsync(h->d_dp_data.p, 0, sizeof(double) * (size_t)dp_total, h->stream));
-    for (const Prep& pr : preps) {
-        const DensePriorHost& D = h->dprior_per_win[pr.w];
-        double* J = h->d_dp_data.p + pr.off;
-        double* r0 = J + 2 * (size_t)pr.nf * pr.n + (size_t)pr.n * pr.n;
-        if (D.resident) {
-            if (!h->prior.valid || h->prior.serial != D.serial || h->prior.n_full != pr.nf || h->prior.n != pr.n) {
-                h->err = "the handle's prior changed after set_dense_prior(SADVIO_PRIOR_RESIDENT) attached it to a window: attach it again"; return SADVIO_E_STATE;
-            }
-            HIP_TRY(hipMemcpyAsync(J, h->prior.J.p, sizeof(double) * (size_t)pr.nf * pr.n, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(r0, h->prior.r0.p, sizeof(double) * (size_t)pr.nf, hipMemcpyDeviceToDevice, h->stream));
-        } else {
-            h->up.add(J, D.J.data(), sizeof(double) * (size_t)pr.nf * pr.n);
-            h->up.add(r0, D.r0.data(), sizeof(double) * (size_t)pr.nf);
-        }
-    }
-    if (!preps.empty()) HIP_TRY(h->up.flush(h->stream));  // the prepare kernels read J on the device
-    for (const Prep& pr : preps) {
-        double* J = h->d_dp_data.p + pr.off;
-        double* Jt = J + (size_t)pr.nf * pr.n;
-        double* H = Jt + (size_t)pr.n * pr.nf;
-        const long long items = (long long)pr.nf * pr.n;
-        hipLaunchKernelGGL(k_dense_prior_prepare, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, h->stream, J, Jt, pr.nf, pr.n);
-        if (h->dprior_per_win[pr.w].resident && h->prior.hg_valid && h->prior.n == pr.n)
-            hipLaunchKernelGGL(k_sym_from_lower, dim3((unsigned)(((long long)pr.n * pr.n + 255) / 256)), dim3(256), 0, h->stream, h->prior.H.p, pr.n, H);   // H = Ak of the marginalisation
-        else
-        hipLaunchKernelGGL(k_mgemm, dim3((pr.n + 63) / 64, (pr.n + 63) / 64), dim3(256), 0, h->stream, H, (long long)pr.n, J, 1LL, (long long)pr.n, J, (long long)pr.n, 1LL,
-                           pr.n, pr.n, pr.nf, 1.0, 0.0);
-    }
-    return SADVIO_OK;
-}
-
-int upload_priors(sadvio_ba_handle* h) {
-    h->priors.clear();
-    for (size_t w = 0; w < h->wins.size(); w++) {
-        h->wins[w].d.prior_begin = (int)h->priors.size();
-        for (auto& p : h->priors_per_win[w]) h->priors.push_back(p);
-        h->wins[w].d.prior_end = (int)h->priors.size();
-    }
-    HIP_TRY(h->d_priors.alloc(h->priors.size()));
-    HIP_TRY(h->d_prior_lin.alloc(2 * h->priors.size() * (size_t)PRIOR_LIN));
-    if (!h->priors.empty())
-        h->up.add(h->d_priors.p, h->priors.data(), h->priors.size() * sizeof(PriorDev));
-    h->imus.clear();
-    for (size_t w = 0; w < h->wins.size(); w++) {
-        h->wins[w].d.imu_begin = (int)h->imus.size();
-        for (auto& f : h->imus_per_win[w]) { h->imus.push_back(f); h->imus.back().win = (int)w; }
-        h->wins[w].d.imu_end = (int)h->imus.size();
-    }
-    HIP_TRY(h->d_imus.alloc(h->imus.size()));
-    HIP_TRY(h->d_imu_scratch.alloc(2 * h->imus.size() * (size_t)IMU_ROW));
-    if (!h->imus.empty())
-        h->up.add(h->d_imus.p, h->imus.data(), h->imus.size() * sizeof(ImuDev));
-    std::vector<WinDev> wd(h->wins.size());
-    for (size_t w = 0; w < h->wins.size(); w++) wd[w] = h->wins[w].d;
-    h->up.add(h->d_win.p, wd.data(), wd.size() * sizeof(WinDev));
-    HIP_TRY(h->up.flush(h->stream));  // one staged copy + scatter for everything queued since the layout build began
-    if (h->pre_ok && h->pre_dirty) {
-        hipLaunchKernelGGL(k_pre_packets, dim3((unsigned)h->tiles.size()), dim3(BUILD_THREADS), 0, h->stream, h->d_tiles.p, h->d_lmk_ob.p, h->d_lmk_oe.p, h->d_tile_kf.p,
-                           h->d_tile_lmk.p, h->d_kf_fidx.p, (int4*)h->d_pre_lane.p, (int2*)h->d_pre_kf.p);
-        h->pre_dirty = false;
-    }
-    return SADVIO_OK;
-}
-
-}  // namespace
+#include "layout_driver.h"
 
 extern "C" {
 
@@ -311,6 +53,7 @@ int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
     if (hipSetDevice(dev) != hipSuccess) return SADVIO_E_HIP;
     auto* h = new sadvio_ba_handle();
     h->env.read();
+    h->up.trace = (h->env.debug & 8192) != 0;
     if (cfg) h->cfg = *cfg;
     h->device = dev;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return SADVIO_E_HIP; }
@@ -336,527 +79,13 @@ void sadvio_ba_destroy(sadvio_ba_handle* h) {
     delete h;
 }
 
-// (Re)build the device layout from the stored caller windows + the current factor lists: concatenation, the
-// per-landmark observation order, pseudo-observations of eliminable pose-to-landmark factors, tiles, reduced layout.
-static int build_layout(sadvio_ba_handle* h) {
-    const bool dbg_t = (h->env.debug & 8192) != 0;
-    auto t_start = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) { if (dbg_t) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[sadvio dbg] build_layout %-14s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_start).count()); t_start = t; } };
-    const int n_windows = (int)h->src.size();
-    HIP_TRY(hipSetDevice(h->device));
-    h->solved = false;
-    h->up.reset();
-    h->wins.assign(n_windows, HostWin());
-    h->tiles.clear();
-    h->sp_elim.assign(n_windows, {});
-    h->n_obs_user.assign(n_windows, 0);
-    // which sparse factors ride the Schur elimination as pseudo-observations: PoseToLandmark factors whose landmark is
-    // free and not held in the reduced system for another reason (dense prior, landmark prior / landmark chain factor)
-    std::vector<sadvio_flat_window> views(n_windows);
-    int sp_global = 0;
-    for (int w = 0; w < n_windows; w++) {
-        SrcWin& S = h->src[w];
-        const auto& sp = h->sparse_per_win[w];
-        h->sp_elim[w].assign(sp.size(), 0);
-        h->n_obs_user[w] = S.v.n_obs;
-        views[w] = S.v;
-        {
-            std::vector<int> cmap(S.v.n_cam, -1);
-            S.u_cam_K.clear(); S.u_cam_T.clear(); S.u_cam_sigma.clear();
-            for (int c = 0; c < S.v.n_cam; c++) {
-                const double sg = S.cam_sigma.empty() ? 1.0 : S.cam_sigma[c];
-                const int nu = (int)S.u_cam_sigma.size();
-                for (int u = 0; u < nu && cmap[c] < 0; u++)
-                    if (!memcmp(&S.u_cam_K[4 * u], &S.cam_K[4 * c], 32) && !memcmp(&S.u_cam_T[12 * u], &S.cam_T[12 * c], 96) && S.u_cam_sigma[u] == sg) cmap[c] = u;
-                if (cmap[c] < 0) {
-                    cmap[c] = nu;
-                    S.u_cam_K.insert(S.u_cam_K.end(), &S.cam_K[4 * c], &S.cam_K[4 * c] + 4);
-                    S.u_cam_T.insert(S.u_cam_T.end(), &S.cam_T[12 * c], &S.cam_T[12 * c] + 12);
-                    S.u_cam_sigma.push_back(sg);
-                }
-            }
-            S.u_obs_cam.resize(S.obs_cam.size());
-            for (size_t o = 0; o < S.obs_cam.size(); o++) S.u_obs_cam[o] = cmap[S.obs_cam[o]];
-            S.cam_map = cmap;
-            views[w].n_cam = (int32_t)S.u_cam_sigma.size();
-            views[w].cam_K = S.u_cam_K.data(); views[w].cam_T_s_f = S.u_cam_T.data(); views[w].cam_sigma = S.u_cam_sigma.data();
-            views[w].obs_cam = S.u_obs_cam.data();
-        }
-        if (sp.empty()) { S.a_src.clear(); continue; }   // no sparse factors: nothing rides the elimination as a pseudo-observation
-        auto& held = h->ls.held;
-        held.assign(std::max(S.v.n_lmk, 1), 0);
-        const DensePriorHost& D = h->dprior_per_win[w];
-        for (size_t i = 0; i < D.lmk_index.size(); i++) if (D.n_full > 0 && D.lmk_col[i] >= 0) held[D.lmk_index[i]] = 1;
-        for (const auto& s : sp) {
-            if (s.type == SADVIO_SPARSE_LMK_PRIOR) held[s.lmk0] = 1;
-            if (s.type == SADVIO_SPARSE_LMK_TO_LMK) { held[s.lmk0] = 1; held[s.lmk1] = 1; }
-        }
-        std::vector<std::vector<int>> extra(S.v.n_lmk);  // per landmark: global sparse-factor indices to append
-        bool any = false;
-        for (size_t k = 0; k < sp.size(); k++) {
-            const auto& s = sp[k];
-            if (s.type != SADVIO_SPARSE_POSE_TO_LMK || held[s.lmk0]) continue;
-            if (!S.lmk_const.empty() && S.lmk_const[s.lmk0]) continue;
-            h->sp_elim[w][k] = 1;
-            extra[s.lmk0].push_back(sp_global + (int)k);
-            any = true;
-        }
-        sp_global += (int)sp.size();
-        if (any) {
-            const int ms = S.v.factor_type == SADVIO_FACTOR_PIXEL ? 2 : 3;
-            S.a_ptr.assign(1, 0); S.a_kf.clear(); S.a_cam.clear(); S.a_src.clear(); S.a_meas.clear();
-            for (int l = 0; l < S.v.n_lmk; l++) {
-                for (int o = S.lmk_obs_ptr[l]; o < S.lmk_obs_ptr[l + 1]; o++) {
-                    S.a_kf.push_back(S.obs_kf[o]); S.a_cam.push_back(S.u_obs_cam[o]); S.a_src.push_back(o);
-                    for (int q = 0; q < ms; q++) S.a_meas.push_back(S.obs_meas[(size_t)ms * o + q]);
-                }
-                for (int gfi : extra[l])
-                    for (int half = 0; half < 2; half++) {
-                        const auto& s = sp[gfi - (sp_global - (int)sp.size())];
-                        S.a_kf.push_back(s.kf); S.a_cam.push_back(-1 - (2 * gfi + half)); S.a_src.push_back(-1);
-                        for (int q = 0; q < ms; q++) S.a_meas.push_back(0.0);
-                    }
-                S.a_ptr.push_back((int32_t)S.a_kf.size());
-            }
-            views[w].n_obs = (int32_t)S.a_kf.size();
-            views[w].lmk_obs_ptr = S.a_ptr.data(); views[w].obs_kf = S.a_kf.data(); views[w].obs_cam = S.a_cam.data();
-            views[w].obs_meas = S.a_meas.data();
-        } else {
-            S.a_src.clear();
-        }
-    }
-    lap("views");
-    const sadvio_flat_window* wins = views.data();
-    h->factor_type = wins[0].factor_type;
-    int kf_b = 0, cam_b = 0, lmk_b = 0, obs_b = 0;
-    h->max_n_kf = h->max_npose = h->max_np = 0; h->n_big = 0;
-    h->has_lmk_const = false;
-    for (int w = 0; w < n_windows; w++) {
-        const sadvio_flat_window& F = wins[w];
-        // a pose-graph window (relative-pose factors only) has no cameras, landmarks or observations
-        if (F.n_kf <= 0 || F.n_cam < 0 || F.n_lmk < 0 || F.n_obs < 0 || !F.kf_T_f_w || (F.n_cam > 0 && (!F.cam_K || !F.cam_T_s_f)) ||
-            (F.n_obs > 0 && F.n_cam == 0) ||
-            (F.n_lmk > 0 && (!F.lmk_p || !F.lmk_obs_ptr)) || (F.n_obs > 0 && (!F.obs_kf || !F.obs_cam || !F.obs_meas))) {
-            h->err = "set_windows: missing array in window " + std::to_string(w);
-            return SADVIO_E_INVALID_ARG;
-        }
-        if (F.factor_type != h->factor_type || (F.factor_type != SADVIO_FACTOR_PIXEL && F.factor_type != SADVIO_FACTOR_ANGULAR)) {
-            h->err = "set_windows: all windows of a batch must share one factor_type";
-            return SADVIO_E_INVALID_ARG;
-        }
-        if (F.n_lmk > 0 && (F.lmk_obs_ptr[0] != 0 || F.lmk_obs_ptr[F.n_lmk] != F.n_obs)) {
-            h->err = "set_windows: lmk_obs_ptr is not a CSR over n_obs";
-            return SADVIO_E_INVALID_ARG;
-        }
-        if (F.lmk_const) h->has_lmk_const = true;
-        HostWin& H = h->wins[w];
-        WinDev& d = H.d;
-        memset(&d, 0, sizeof(d));
-        d.n_kf = F.n_kf; d.n_cam = F.n_cam; d.n_lmk = F.n_lmk; d.n_obs = F.n_obs;
-        d.kf_base = kf_b; d.cam_base = cam_b; d.lmk_base = lmk_b; d.obs_base = obs_b;
-        d.factor_type = F.factor_type; d.has_imu = F.has_imu;
-        d.dpf = F.has_imu ? 15 : 6;
-        int nfree = 0;
-        for (int k = 0; k < F.n_kf; k++)
-            if (!(F.kf_const && F.kf_const[k])) nfree++;
-        d.n_free_kf = nfree;
-        d.Npose = nfree * 6;
-        d.Np = nfree * d.dpf;
-        H.kf_id.assign(F.n_kf, 0); H.lmk_id.assign(F.n_lmk, 0);
-        for (int k = 0; k < F.n_kf; k++) H.kf_id[k] = F.kf_id ? F.kf_id[k] : k;
-        for (int l = 0; l < F.n_lmk; l++) H.lmk_id[l] = F.lmk_id ? F.lmk_id[l] : l;
-        kf_b += F.n_kf; cam_b += F.n_cam; lmk_b += F.n_lmk; obs_b += F.n_obs;
-        h->max_n_kf = std::max(h->max_n_kf, F.n_kf);
-        h->max_npose = std::max(h->max_npose, d.Npose);
-    }
-    h->n_kf_tot = kf_b; h->n_cam_tot = cam_b; h->n_lmk_tot = lmk_b; h->n_obs_tot = obs_b;
-
-    lap("  validate");
-    // concatenate
-    LayoutScratch& ls = h->ls;
-    auto& kf_T0 = ls.kf_T0; auto& kf_vel = ls.kf_vel; auto& kf_ba = ls.kf_ba; auto& kf_bg = ls.kf_bg; auto& kf_fidx = ls.kf_fidx;
-    auto& cam_K = ls.cam_K; auto& cam_T = ls.cam_T; auto& cam_isig = ls.cam_isig; auto& lmk_p = ls.lmk_p; auto& lmk_const = ls.lmk_const;
-    auto& lmk_ob = ls.lmk_ob; auto& lmk_oe = ls.lmk_oe; auto& obs_kf = ls.obs_kf; auto& obs_cam = ls.obs_cam; auto& obs_meas = ls.obs_meas;
-    auto& tile_kf = ls.tile_kf; auto& tile_row = ls.tile_row; auto& tile_lmk = ls.tile_lmk; auto& obs_slot = ls.obs_slot;
-    kf_T0.resize(12 * (size_t)kf_b); kf_vel.assign(3 * (size_t)kf_b, 0.0); kf_ba.assign(3 * (size_t)kf_b, 0.0); kf_bg.assign(3 * (size_t)kf_b, 0.0);
-    kf_fidx.resize(kf_b);
-    cam_K.resize(4 * (size_t)cam_b); cam_T.resize(12 * (size_t)cam_b); cam_isig.resize(cam_b);
-    lmk_p.resize(3 * (size_t)lmk_b);
-    lmk_const.assign(std::max(lmk_b, 1), 0);
-    lmk_ob.resize(std::max(lmk_b, 1)); lmk_oe.resize(std::max(lmk_b, 1)); obs_kf.resize(std::max(obs_b, 1)); obs_cam.resize(std::max(obs_b, 1));
-    const int ms = h->factor_type == SADVIO_FACTOR_PIXEL ? 2 : 3;
-    obs_meas.resize((size_t)ms * std::max(obs_b, 1));
-    tile_kf.clear(); tile_row.clear(); tile_lmk.clear();
-    obs_slot.assign(std::max(obs_b, 1), 0);
-    h->obs_perm.assign(std::max(obs_b, 1), 0);
-    h->max_tile_kf = 1; h->max_tile_free = 0; h->max_gemm_free = 0; h->gemm_run4 = false;
-    for (int w = 0; w < n_windows; w++) {
-        const sadvio_flat_window& F = wins[w];
-        WinDev& d = h->wins[w].d;
-        memcpy(&kf_T0[12 * (size_t)d.kf_base], F.kf_T_f_w, sizeof(double) * 12 * F.n_kf);
-        if (F.kf_vel) memcpy(&kf_vel[3 * (size_t)d.kf_base], F.kf_vel, sizeof(double) * 3 * F.n_kf);
-        if (F.kf_ba) memcpy(&kf_ba[3 * (size_t)d.kf_base], F.kf_ba, sizeof(double) * 3 * F.n_kf);
-        if (F.kf_bg) memcpy(&kf_bg[3 * (size_t)d.kf_base], F.kf_bg, sizeof(double) * 3 * F.n_kf);
-        int fi = 0;
-        for (int k = 0; k < F.n_kf; k++) kf_fidx[d.kf_base + k] = (F.kf_const && F.kf_const[k]) ? -1 : fi++;
-        memcpy(&cam_K[4 * (size_t)d.cam_base], F.cam_K, sizeof(double) * 4 * F.n_cam);
-        memcpy(&cam_T[12 * (size_t)d.cam_base], F.cam_T_s_f, sizeof(double) * 12 * F.n_cam);
-        for (int c = 0; c < F.n_cam; c++) cam_isig[d.cam_base + c] = 1.0 / (F.cam_sigma ? F.cam_sigma[c] : 1.0);
-        if (F.n_lmk) memcpy(&lmk_p[3 * (size_t)d.lmk_base], F.lmk_p, sizeof(double) * 3 * F.n_lmk);
-        for (int l = 0; l < F.n_lmk; l++) {
-            lmk_const[d.lmk_base + l] = F.lmk_const ? F.lmk_const[l] : 0;
-            lmk_ob[d.lmk_base + l] = d.obs_base + F.lmk_obs_ptr[l];
-            lmk_oe[d.lmk_base + l] = d.obs_base + F.lmk_obs_ptr[l + 1];
-            if (F.lmk_obs_ptr[l + 1] < F.lmk_obs_ptr[l]) { h->err = "set_windows: CSR not monotone"; return SADVIO_E_INVALID_ARG; }
-        }
-        lap("  concat");
-        // Observations of a landmark are stored sorted by key-frame (stable), so that the (at most two) cameras
-        // of one key-frame sit in adjacent lanes; the landmark / key-frame order of the window is untouched and
-        // obs_perm maps device position -> caller position for the per-observation probe.
-        auto& pkf = ls.pkf; auto& pcam = ls.pcam; auto& run_max = ls.run_max; auto& idx = ls.idx;
-        pkf.resize(std::max(F.n_obs, 1)); pcam.resize(std::max(F.n_obs, 1));
-        run_max.assign(std::max(F.n_lmk, 1), 0);
-        const bool has_asrc = !h->src[w].a_src.empty();
-        const int32_t* asrc = has_asrc ? h->src[w].a_src.data() : nullptr;
-        // first pass (integers only): is every landmark's list already key-frame sorted (what a flattening in frame order
-        // produces)? Its longest same-key-frame run either way.
-        bool all_sorted = true;
-        int hb_win = 0;   // largest spread of free key-frame indices one landmark couples (half bandwidth of the reduced system)
-        const int* fidx_w = kf_fidx.data() + d.kf_base;
-        for (int l = 0; l < F.n_lmk; l++) {
-            const int o0 = F.lmk_obs_ptr[l], o1 = F.lmk_obs_ptr[l + 1];
-            int run = 0, rm = 0, prev = -1, lo = 1 << 30, hi = -1;
-            for (int o = o0; o < o1; o++) {
-                const int kf = F.obs_kf[o];
-                if (kf < prev) { all_sorted = false; }
-                run = (kf == prev) ? run + 1 : 1;
-                rm = std::max(rm, run);
-                prev = kf;
-                const int fi = fidx_w[kf];
-                if (fi >= 0) { lo = std::min(lo, fi); hi = std::max(hi, fi); }
-            }
-            run_max[l] = rm;
-            if (hi >= 0) hb_win = std::max(hb_win, hi - lo);
-        }
-        h->wins[w].hb_lmk = hb_win;
-        if (all_sorted) {
-            // bulk path: the device order IS the caller's order — whole-array copies
-            const int kb = d.kf_base, cb = d.cam_base, ob = d.obs_base, n = F.n_obs;
-            for (int o = 0; o < n; o++) { pkf[o] = F.obs_kf[o]; obs_kf[ob + o] = kb + F.obs_kf[o]; }
-            for (int o = 0; o < n; o++) { const int c = F.obs_cam[o]; pcam[o] = c; obs_cam[ob + o] = c < 0 ? c : cb + c; }
-            if (has_asrc) for (int o = 0; o < n; o++) h->obs_perm[ob + o] = asrc[o];
-            else for (int o = 0; o < n; o++) h->obs_perm[ob + o] = o;
-            if (n) memcpy(&obs_meas[(size_t)ms * ob], F.obs_meas, sizeof(double) * (size_t)ms * n);
-        } else
-        for (int l = 0; l < F.n_lmk; l++) {
-            const int o0 = F.lmk_obs_ptr[l], o1 = F.lmk_obs_ptr[l + 1], k_n = o1 - o0;
-            // tracks are short: insertion sort (stable) on packed keys (key-frame << 8 | position) held in a local array —
-            // no indirection through the caller's arrays inside the sort; longer tracks take the index sort
-            int key[64];
-            const int32_t* okf = F.obs_kf + o0;
-            if (k_n <= 64 && F.n_kf < (1 << 22)) {
-                for (int k = 0; k < k_n; k++) key[k] = (okf[k] << 8) | k;
-                for (int a = 1; a < k_n; a++) {
-                    const int v = key[a];
-                    int b = a - 1;
-                    while (b >= 0 && key[b] > v) { key[b + 1] = key[b]; b--; }
-                    key[b + 1] = v;
-                }
-            } else {
-                idx.resize(k_n);
-                for (int k = 0; k < k_n; k++) idx[k] = k;
-                std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return okf[a] < okf[b]; });
-            }
-            int run = 0, rm = 0, prev = -1;
-            const int kb = d.kf_base, cb = d.cam_base, ob = d.obs_base;
-            for (int k = 0; k < k_n; k++) {
-                const int rel = k_n <= 64 && F.n_kf < (1 << 22) ? (key[k] & 255) : idx[k];
-                const int src = o0 + rel, dst = o0 + k;
-                const int kf = okf[rel], c = F.obs_cam[src];
-                pkf[dst] = kf; pcam[dst] = c;
-                h->obs_perm[ob + dst] = has_asrc ? asrc[src] : src;  // -1: pseudo-observation
-                obs_kf[ob + dst] = kb + kf;
-                obs_cam[ob + dst] = c < 0 ? c : cb + c;
-                const double* m = F.obs_meas + (size_t)ms * src;
-                double* md = &obs_meas[(size_t)ms * (ob + dst)];
-                md[0] = m[0]; md[1] = m[1]; if (ms == 3) md[2] = m[2];
-                run = (kf == prev) ? run + 1 : 1;
-                rm = std::max(rm, run);
-                prev = kf;
-            }
-            run_max[l] = rm;
-        }
-        lap("  sort+permute");
-        lap("  half-bandwidth");
-        // tiles: runs of consecutive landmarks. Every landmark gets a group of G lanes (G = pow2 >= the
-        // tile's largest observation count); a workgroup of BUILD_WAVES waves holds BUILD_WAVES * 64 / G
-        // landmarks per round. A tile is cut when its key-frame list would exceed the LDS tile capacity.
-        if (F.n_cam > MAX_WIN_CAM) { h->err = "set_windows: more than 8 distinct cameras per window"; return SADVIO_E_INVALID_ARG; }
-        // rounds per tile: one for a single window (most workgroups = lowest latency); a large batch gets fewer, larger tiles
-        // (~2048 = 4 per resident workgroup slot) so that table staging, merge and flush are paid once per several rounds
-        int tile_rounds = 1;
-        {
-            long long l_tot = 0;
-            for (int ww = 0; ww < n_windows; ww++) l_tot += views[ww].n_lmk;
-            tile_rounds = (int)std::min<long long>(16, std::max<long long>(1, (l_tot + 32LL * 2048 - 1) / (32LL * 2048)));
-            if (h->env.tile_rounds > 0) tile_rounds = h->env.tile_rounds;
-        }
-        d.tile_begin = (int)h->tiles.size();
-        // Single-round tiles of the latency kernels are packed (tile_pack.h): a tile lists its landmarks, so that a few outlier tracks
-        // do not cut the runs around them. Multi-round tiles, sharded ranks and layouts that build the throughput path's chunk tables
-        // (consecutive landmarks throughout) keep the contiguous cut.
-        bool want_lm_w = lmk_b >= 65536;
-        if (h->env.lm >= 0) want_lm_w = h->env.lm != 0;
-        const bool packed = n_windows == 1 && tile_rounds == 1 && F.n_lmk > 0 && h->world == 1 && !h->coll_fn && !want_lm_w && !h->env.contig_tiles;
-        auto& order = ls.pack_order; auto& cut = ls.pack_cut;
-        if (packed) {
-            for (int l = 0; l < F.n_lmk; l++)
-                if (F.lmk_obs_ptr[l + 1] - F.lmk_obs_ptr[l] > MAX_LMK_OBS) { h->err = "set_windows: a landmark has more than 64 observations"; return SADVIO_E_INVALID_ARG; }
-            const TilePackIn in{F.n_lmk, F.n_kf, F.lmk_obs_ptr, pkf.data(), F.kf_const, run_max.data(), BUILD_WAVES * 64, MAX_TILE_KF, MAX_TILE_FREE_KF, MAX_GEMM_FREE_KF};
-            tile_pack(in, order, cut);
-        }
-        {
-            int l = 0;   // position in the window's landmark sequence: the landmark itself, or its place in order (packed)
-            size_t next_cut = 0;
-            auto lm_at = [&](int i) { return packed ? order[i] : i; };
-            auto& mark = ls.mark; auto& add = ls.add; auto& kfs = ls.kfs; auto& slot_of = ls.slot_of;
-            mark.assign(F.n_kf, -1); slot_of.assign(F.n_kf, -1);
-            while (l < F.n_lmk || (int)h->tiles.size() == d.tile_begin) {
-                Tile t{};
-                t.w = w; t.lmk0 = d.lmk_base + (l < F.n_lmk ? lm_at(l) : l); t.kmax = 1; t.G = 8;
-                t.lmk_off = packed ? (int)tile_lmk.size() : -1;
-                t.dpf = d.dpf;  // Np, red_off, S_off, ld: layout_reduced
-                t.cam_base = d.cam_base; t.n_cam = F.n_cam;
-                t.first_of_window = ((int)h->tiles.size() == d.tile_begin) ? 1 : 0;
-                kfs.clear();
-                int nfree = 0, tile_run_max = 0;
-                const int l_begin = l;
-                while (l < F.n_lmk) {
-                    const int gl = lm_at(l);
-                    if (packed && l == cut[next_cut]) break;
-                    const int k = F.lmk_obs_ptr[gl + 1] - F.lmk_obs_ptr[gl];
-                    if (k > MAX_LMK_OBS) { h->err = "set_windows: a landmark has more than 64 observations"; return SADVIO_E_INVALID_ARG; }
-                    int G = t.G;
-                    while (G < k) G <<= 1;
-                    const int cap = tile_rounds * BUILD_WAVES * (64 / G);  // landmarks per tile (tile_rounds rounds per wave)
-                    if (!packed && l - l_begin + 1 > cap && l > l_begin) break;
-                    // key-frames this landmark would add
-                    add.clear();
-                    int add_free = 0;
-                    for (int o = F.lmk_obs_ptr[gl]; o < F.lmk_obs_ptr[gl + 1]; o++) {
-                        const int kf = pkf[o];
-                        if (mark[kf] != (int)h->tiles.size()) {
-                            mark[kf] = (int)h->tiles.size();
-                            add.push_back(kf);
-                            if (!(F.kf_const && F.kf_const[kf])) add_free++;
-                        }
-                    }
-                    const bool fits_hard = (int)(kfs.size() + add.size()) <= MAX_TILE_KF && nfree + add_free <= MAX_TILE_FREE_KF;
-                    // soft limit: keep tiles on the MFMA path (<= MAX_GEMM_FREE_KF free key-frames) whenever a cut achieves it
-                    const bool fits = fits_hard && (nfree + add_free <= MAX_GEMM_FREE_KF || l == l_begin);
-                    if (!packed && !fits && l > l_begin) {
-                        for (int kf : add) mark[kf] = -1;  // roll back
-                        break;
-                    }
-                    for (int kf : add) kfs.push_back(kf);
-                    nfree += add_free;
-                    t.G = G;
-                    t.kmax = std::max(t.kmax, k);
-                    tile_run_max = std::max(tile_run_max, run_max[gl]);
-                    if (packed) tile_lmk.push_back(d.lmk_base + gl);
-                    l++;
-                    if (!packed && !fits_hard) break;  // a single landmark exceeding the capacity: global-atomics tile
-                }
-                if (packed) next_cut++;
-                t.n_lmk = l - l_begin;
-                t.lmk1 = t.lmk0 + t.n_lmk;   // (a packed tile: the count only; its landmarks are tile_lmk's)
-                std::sort(kfs.begin(), kfs.end());
-                t.lds_mode = ((int)kfs.size() <= MAX_TILE_KF && nfree <= MAX_TILE_FREE_KF) ? ((nfree <= MAX_GEMM_FREE_KF && tile_run_max <= (has_asrc ? 4 : 2) && t.G == 8) ? 2 : 1) : 0;
-                if (t.lds_mode == 2 && tile_run_max > 2) h->gemm_run4 = true;   // needs the RARE variant of k_build (pseudo-observations: it is taken)
-                if (t.lds_mode == 2) h->max_gemm_free = std::max(h->max_gemm_free, nfree);
-                if ((int)kfs.size() > 64) { h->err = "set_windows: a landmark is observed from more than 64 key-frames"; return SADVIO_E_INVALID_ARG; }
-                t.kf_off = (int)tile_kf.size(); t.n_kf = (int)kfs.size(); t.n_free = t.lds_mode ? nfree : 0;
-                int rank = 0;
-                for (size_t i = 0; i < kfs.size(); i++) {
-                    const int kf = kfs[i];
-                    slot_of[kf] = (int)i;
-                    tile_kf.push_back(d.kf_base + kf);
-                    const bool is_const = F.kf_const && F.kf_const[kf];
-                    if (is_const) tile_row.push_back(-1);
-                    else if (t.lds_mode) tile_row.push_back(6 * rank++);
-                    else tile_row.push_back(6 * kf_fidx[d.kf_base + kf]);  // global mode: 6 * free index of the window
-                }
-                for (int li = l_begin; li < l; li++)
-                    for (int o = F.lmk_obs_ptr[lm_at(li)]; o < F.lmk_obs_ptr[lm_at(li) + 1]; o++)
-                        obs_slot[d.obs_base + o] = (unsigned char)slot_of[pkf[o]];
-                h->max_tile_kf = std::max(h->max_tile_kf, t.n_kf);
-                h->max_tile_free = std::max(h->max_tile_free, t.n_free);
-                h->tiles.push_back(t);
-                if (F.n_lmk == 0) break;
-            }
-        }
-        d.tile_end = (int)h->tiles.size();
-        for (int ti = d.tile_begin; ti < d.tile_end; ti++) { h->tiles[ti].win_tile0 = d.tile_begin; h->tiles[ti].win_ntiles = d.tile_end - d.tile_begin; }
-    }
-    lap("concat+tiles");
-    // chunk tables of the throughput kernels: a tile's consecutive landmarks in chunks of <= LM_CHUNK landmarks and <= 64
-    // observations; obs_lslot = index of the observation's landmark inside its chunk
-    auto& chunk_ob = ls.chunk_ob; auto& chunk_lm = ls.chunk_lm;   // chunk starts + one sentinel (landmarks and observations are globally consecutive)
-    auto& obs_lslot = ls.obs_lslot;
-    chunk_ob.clear(); chunk_lm.clear();
-    obs_lslot.assign(std::max(obs_b, 1), 0);
-    // the tables cost host time (a second, sorted copy of the observation constants): only built where the throughput path can run
-    bool want_lm = lmk_b >= 65536;
-    if (h->env.lm >= 0) want_lm = h->env.lm != 0;
-    h->lm_ok = want_lm && !h->tiles.empty();
-    h->lm_landmarks = 0;
-    h->lm_sub_obs = 0;
-    for (auto& t : h->tiles) {
-        if (!want_lm) { t.chunk0 = t.chunk1 = 0; continue; }
-        t.chunk0 = (int)chunk_lm.size();
-        if (t.lds_mode != 2) h->lm_ok = false;
-        int l = t.lmk0;
-        while (l < t.lmk1) {
-            chunk_lm.push_back(l); chunk_ob.push_back(lmk_ob[l]);
-            int nl = 0, no = 0;
-            while (l < t.lmk1 && nl < LM_CHUNK && no + (lmk_oe[l] - lmk_ob[l]) <= 64) {
-                for (int o = lmk_ob[l]; o < lmk_oe[l]; o++) obs_lslot[o] = (unsigned char)nl;
-                no += lmk_oe[l] - lmk_ob[l]; nl++; l++;
-            }
-            if (nl == 0) { h->lm_ok = false; l++; }   // a landmark with more than 64 observations (never on the MFMA path)
-        }
-        t.chunk1 = (int)chunk_lm.size();
-        h->lm_landmarks += t.lmk1 - t.lmk0;
-    }
-    chunk_lm.push_back(lmk_b); chunk_ob.push_back(obs_b);
-    if (want_lm) {
-        // k_lm_pass stages the observation constants of LM_PASS_THREADS consecutive landmarks of a tile in LDS: the largest such block
-        for (const auto& t : h->tiles)
-            for (int l0 = t.lmk0; l0 < t.lmk1; l0 += LM_PASS_THREADS) {
-                const int l1 = std::min(l0 + LM_PASS_THREADS, t.lmk1);
-                h->lm_sub_obs = std::max(h->lm_sub_obs, lmk_oe[l1 - 1] - lmk_ob[l0]);
-            }
-        h->lm_sub_obs = (h->lm_sub_obs + 3) & ~3;
-        h->lm_max_cam = 1;
-        for (const auto& t : h->tiles) h->lm_max_cam = std::max(h->lm_max_cam, t.n_cam);
-        HIP_TRY(h->d_lm_hg.alloc(2 * (size_t)LM_HG * std::max(lmk_b, 1)));
-        h->lm_ksub = 1;
-        for (const auto& t : h->tiles) h->lm_ksub = std::max(h->lm_ksub, (t.lmk1 - t.lmk0 + LM_PASS_THREADS - 1) / LM_PASS_THREADS);
-        const size_t n_rec = std::max<size_t>(h->tiles.size(), 1) * h->lm_ksub;
-        HIP_TRY(h->d_lm_dt.alloc(2 * (size_t)LM_DT * n_rec));
-        HIP_TRY(h->d_lm_sacc.alloc(2 * 4 * n_rec));
-        HIP_TRY(hipMemsetAsync(h->d_lm_sacc.p, 0, sizeof(double) * 2 * 4 * n_rec, h->stream));   // slots of sub-blocks that do not exist stay zero
-        // k_build_obs sums a tile's key-frame record over EVERY sub-block slot, k_lm_pass writes one slot per work item: the slots
-        // nobody writes must be zero, and the buffer is grow-only (a re-layout with another tiling would leave stale records there)
-        HIP_TRY(hipMemsetAsync(h->d_lm_dt.p, 0, sizeof(double) * 2 * (size_t)LM_DT * n_rec, h->stream));
-    }
-    HIP_TRY(h->d_chunk_ob.alloc(chunk_ob.size())); HIP_TRY(h->d_chunk_lm.alloc(chunk_lm.size())); HIP_TRY(h->d_obs_lslot.alloc(obs_lslot.size()));
-    h->up.add(h->d_chunk_ob.p, chunk_ob.data(), chunk_ob.size() * sizeof(int));
-    h->up.add(h->d_chunk_lm.p, chunk_lm.data(), chunk_lm.size() * sizeof(int));
-    h->up.add(h->d_obs_lslot.p, obs_lslot.data(), obs_lslot.size());
-    {
-        // launch order of the throughput kernels: longest tiles first (LPT), so that the last workgroups to start are short ones
-        auto& perm = ls.perm;
-        perm.resize(h->tiles.size());
-        for (size_t i = 0; i < perm.size(); i++) perm[i] = (int)i;
-        if (want_lm && !h->env.no_lpt)
-            std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) {
-                return h->tiles[a].chunk1 - h->tiles[a].chunk0 > h->tiles[b].chunk1 - h->tiles[b].chunk0; });
-        if (h->env.debug && want_lm && !perm.empty())
-            fprintf(stderr, "[sadvio dbg] chunks per tile: largest %d, median %d, smallest %d\n", h->tiles[perm.front()].chunk1 - h->tiles[perm.front()].chunk0,
-                    h->tiles[perm[perm.size() / 2]].chunk1 - h->tiles[perm[perm.size() / 2]].chunk0, h->tiles[perm.back()].chunk1 - h->tiles[perm.back()].chunk0);
-        HIP_TRY(h->d_tile_perm.alloc(std::max<size_t>(perm.size(), 1)));
-        h->up.add(h->d_tile_perm.p, perm.data(), perm.size() * sizeof(int));
-        // work list of k_lm_pass: the sub-blocks (LM_PASS_THREADS landmarks) of every tile, in the same order
-        std::vector<int> sub;
-        if (h->env.lm_subs > 0) h->lm_sub_per_item = h->env.lm_subs;
-        if (want_lm)
-            for (int ti : perm) {
-                const Tile& t = h->tiles[ti];
-                for (int q = 0, l0 = t.lmk0; l0 < t.lmk1; l0 += LM_PASS_THREADS * h->lm_sub_per_item, q += h->lm_sub_per_item) { sub.push_back(ti); sub.push_back(q); }
-            }
-        h->lm_n_sub = (int)sub.size() / 2;
-        HIP_TRY(h->d_lm_sub.alloc(std::max<size_t>(sub.size(), 2)));
-        h->up.add(h->d_lm_sub.p, sub.data(), sub.size() * sizeof(int));
-    }
-    if (h->env.debug) {
-        int hist[32] = {0}, modes[3] = {0};
-        for (auto& t : h->tiles) { hist[std::min(t.n_free, 31)]++; modes[t.lds_mode]++; }
-        fprintf(stderr, "[sadvio dbg] %zu tiles, modes global/atomic/gemm = %d/%d/%d, max_tile_kf %d, n_free histogram:", h->tiles.size(), modes[0], modes[1], modes[2], h->max_tile_kf);
-        for (int i = 0; i < 32; i++) if (hist[i]) fprintf(stderr, " %d:%d", i, hist[i]);
-        fprintf(stderr, "\n");
-    }
-    HIP_TRY(h->d_win.alloc(n_windows)); HIP_TRY(h->d_tacc.alloc(2 * h->tiles.size()));
-    if (tile_kf.empty()) { tile_kf.push_back(0); tile_row.push_back(-1); }
-    if (tile_lmk.empty()) tile_lmk.push_back(0);
-    HIP_TRY(h->d_tile_kf.alloc(tile_kf.size())); HIP_TRY(h->d_tile_row.alloc(tile_row.size())); HIP_TRY(h->d_tile_lmk.alloc(tile_lmk.size()));
-    HIP_TRY(h->d_obs_slot.alloc(obs_slot.size())); HIP_TRY(h->d_ptab.alloc(2 * (size_t)POSE_TAB * kf_b));
-    HIP_TRY(h->d_kf_T0.alloc(kf_T0.size())); HIP_TRY(h->d_kf_fidx.alloc(kf_fidx.size()));
-    HIP_TRY(h->d_xp.alloc(2 * 6 * (size_t)kf_b)); HIP_TRY(h->d_xv.alloc(2 * 3 * (size_t)kf_b));
-    HIP_TRY(h->d_xba.alloc(2 * 3 * (size_t)kf_b)); HIP_TRY(h->d_xbg.alloc(2 * 3 * (size_t)kf_b));
-    HIP_TRY(h->d_kf_vel.alloc(kf_vel.size())); HIP_TRY(h->d_kf_ba.alloc(kf_ba.size())); HIP_TRY(h->d_kf_bg.alloc(kf_bg.size()));
-    HIP_TRY(h->d_cam_K.alloc(cam_K.size())); HIP_TRY(h->d_cam_T.alloc(cam_T.size())); HIP_TRY(h->d_cam_isig.alloc(cam_isig.size()));
-    HIP_TRY(h->d_lmk_p.alloc(lmk_p.size())); HIP_TRY(h->d_xl.alloc(2 * 3 * (size_t)std::max(lmk_b, 1)));
-    HIP_TRY(h->d_s_lmk.alloc(3 * (size_t)std::max(lmk_b, 1)));
-    HIP_TRY(h->d_lmk_ob.alloc(lmk_ob.size())); HIP_TRY(h->d_lmk_oe.alloc(lmk_oe.size()));
-    HIP_TRY(h->d_obs_kf.alloc(obs_kf.size())); HIP_TRY(h->d_obs_cam.alloc(obs_cam.size())); HIP_TRY(h->d_obs_meas.alloc(obs_meas.size()));
-#define UP(dst, src) h->up.add((dst).p, (src).data(), (src).size() * sizeof((src)[0]))
-    UP(h->d_kf_T0, kf_T0); UP(h->d_kf_fidx, kf_fidx); UP(h->d_kf_vel, kf_vel);
-    UP(h->d_kf_ba, kf_ba); UP(h->d_kf_bg, kf_bg); UP(h->d_cam_K, cam_K); UP(h->d_cam_T, cam_T); UP(h->d_cam_isig, cam_isig);
-    if (lmk_b) { UP(h->d_lmk_p, lmk_p); }
-    UP(h->d_lmk_ob, lmk_ob); UP(h->d_lmk_oe, lmk_oe); UP(h->d_obs_kf, obs_kf);
-    UP(h->d_obs_cam, obs_cam); UP(h->d_obs_meas, obs_meas); UP(h->d_tile_kf, tile_kf); UP(h->d_tile_row, tile_row); UP(h->d_tile_lmk, tile_lmk); UP(h->d_obs_slot, obs_slot);
-    // First-round packets (round 6): what a lane of k_build / k_backsub needs to address the inputs of its tile's FIRST landmark round,
-    // laid out by (tile, lane) so that the loads hang on blockIdx alone: | landmark | observation (-1: none) | observations of the
-    // landmark + valid flag | first observation of the landmark |, and per tile the first PRE_KF key-frames of its list with their free
-    // index. Without them the kernel's opening is a chain tile record -> CSR range / key-frame list -> observation / pose table
-    // (three dependent round trips of ~1 us each on a single window); with them two. Few-tile submissions only (the single-window /
-    // small-batch regime the latency kernels serve; 4 KB per tile).
-    h->pre_ok = !h->tiles.empty() && h->tiles.size() <= PRE_MAX_TILES && !h->env.no_pre;
-    if (h->pre_ok) {   // built on the device behind the upload (k_pre_packets, upload_priors): 1 MB of host stores + PCIe otherwise
-        HIP_TRY(h->d_pre_lane.alloc((size_t)4 * (BUILD_THREADS / 8) * h->tiles.size())); HIP_TRY(h->d_pre_kf.alloc((size_t)2 * PRE_KF * h->tiles.size()));
-        h->pre_dirty = true;
-    }
-#undef UP
-    h->h_lmk_const_user = lmk_const; h->user_lmk_const = h->has_lmk_const;
-    h->h_lmk_ob = lmk_ob; h->h_lmk_oe = lmk_oe; h->h_kf_fidx = kf_fidx; h->h_obs_kf = obs_kf;
-    h->rel.csr_win = -1;   // the per-key-frame landmark lists of marginalize_relative_batch describe the old layout
-    lap("alloc+queue");
-    int rc = layout_reduced(h);
-    if (rc != SADVIO_OK) return rc;
-    lap("layout_reduced");
-    rc = upload_priors(h);  // also uploads the window descriptors and synchronises (host vectors go out of scope)
-    if (rc != SADVIO_OK) return rc;
-    lap("flush");
-    h->uploaded = true;
-    for (auto& k : h->kclasses) { k.total_ms = 0; k.launches = 0; }
-    return SADVIO_OK;
-}
-
 int sadvio_ba_set_windows(sadvio_ba_handle* h, int32_t n_windows, const sadvio_flat_window* wins) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (n_windows <= 0 || !wins) { h->err = "set_windows: no windows"; return SADVIO_E_INVALID_ARG; }
     h->uploaded = false; h->solved = false;
     for (int w = 0; w < n_windows; w++) {
-        const sadvio_flat_window& F = wins[w];
-        // a pose-graph window (relative-pose factors only) has no cameras, landmarks or observations
-        if (F.n_kf <= 0 || F.n_cam < 0 || F.n_lmk < 0 || F.n_obs < 0 || !F.kf_T_f_w || (F.n_cam > 0 && (!F.cam_K || !F.cam_T_s_f)) ||
-            (F.n_obs > 0 && F.n_cam == 0) ||
-            (F.n_lmk > 0 && (!F.lmk_p || !F.lmk_obs_ptr)) || (F.n_obs > 0 && (!F.obs_kf || !F.obs_cam || !F.obs_meas))) {
-            h->err = "set_windows: missing array in window " + std::to_string(w);
-            return SADVIO_E_INVALID_ARG;
-        }
-        if (F.n_lmk > 0 && (F.lmk_obs_ptr[0] != 0 || F.lmk_obs_ptr[F.n_lmk] != F.n_obs)) {
-            h->err = "set_windows: lmk_obs_ptr is not a CSR over n_obs";
-            return SADVIO_E_INVALID_ARG;
-        }
-        for (int l = 0; l < F.n_lmk; l++)
-            if (F.lmk_obs_ptr[l + 1] < F.lmk_obs_ptr[l]) { h->err = "set_windows: CSR not monotone"; return SADVIO_E_INVALID_ARG; }
-        for (int o = 0; o < F.n_obs; o++)
-            if (F.obs_kf[o] < 0 || F.obs_kf[o] >= F.n_kf || F.obs_cam[o] < 0 || F.obs_cam[o] >= F.n_cam) {
-                h->err = "set_windows: observation index out of range";
-                return SADVIO_E_INVALID_ARG;
-            }
+        const int rc = check_flat_window(wins[w], w, h->err);
+        if (rc != SADVIO_OK) return rc;
     }
     // deep copies: later set_* calls rebuild the layout without the caller's buffers
     if ((int)h->src.size() != n_windows) h->src.assign(n_windows, SrcWin());   // same batch size: the copies below reuse their capacity
@@ -899,22 +128,12 @@ int sadvio_ba_set_windows(sadvio_ba_handle* h, int32_t n_windows, const sadvio_f
     h->lines_per_win.assign(n_windows, {});
     if (h->defer) {
         // the factor setters that follow validate against the windows' sizes and convert indices with their offsets in the batch:
-        // the same numbers build_layout derives at commit
-        h->wins.assign(n_windows, HostWin());
-        int kf_b = 0, lmk_b = 0, obs_b = 0;
-        for (int w = 0; w < n_windows; w++) {
-            const sadvio_flat_window& F = wins[w];
-            WinDev& d = h->wins[w].d;
-            memset(&d, 0, sizeof(d));
-            d.n_kf = F.n_kf; d.n_cam = F.n_cam; d.n_lmk = F.n_lmk; d.n_obs = F.n_obs;
-            d.kf_base = kf_b; d.lmk_base = lmk_b; d.obs_base = obs_b;
-            d.factor_type = F.factor_type; d.has_imu = F.has_imu; d.dpf = F.has_imu ? 15 : 6;
-            kf_b += F.n_kf; lmk_b += F.n_lmk; obs_b += F.n_obs;
-        }
+        // stub records with the numbers layout_build derives at commit (the cameras are not de-duplicated yet: no setter reads them)
+        layout_windows(n_windows, wins, h->plan);
         h->uploaded = true; h->pending = true;
         return SADVIO_OK;
     }
-    return build_layout(h);
+    return layout_build(h);
 }
 
 int sadvio_ba_begin_update(sadvio_ba_handle* h) {
@@ -929,19 +148,17 @@ int sadvio_ba_commit_update(sadvio_ba_handle* h) {
     h->defer = false;
     if (!h->pending) return SADVIO_OK;
     h->pending = false;
-    HIP_TRY(hipSetDevice(h->device));
-    h->uploaded = false;   // the deferred set_windows left stub window records: a failed build must not leave them usable
-    return build_layout(h);
+    return layout_build(h);   // (a failed build leaves the handle without a layout: the deferred set_windows left stub window records)
 }
 
 int sadvio_ba_set_lines(sadvio_ba_handle* h, int32_t w, const sadvio_line_set* L) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "set_lines before set_windows"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "set_lines: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "set_lines: window out of range"; return SADVIO_E_INVALID_ARG; }
     const int n = L ? L->n_line : 0;
     if (h->world > 1 && n > 0) { h->err = "set_lines: not supported on a window sharded over several GPUs"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     LineSetHost H;
     if (n > 0) {
         if (n < 0 || L->n_obs < 0 || !L->line_T_w_l || !L->line_model || !L->line_obs_ptr || (L->n_obs > 0 && (!L->obs_kf || !L->obs_cam || !L->obs_meas))) {
@@ -977,9 +194,9 @@ int sadvio_ba_set_lines(sadvio_ba_handle* h, int32_t w, const sadvio_line_set* L
 int sadvio_ba_get_line_deltas(sadvio_ba_handle* h, int32_t w, double* line_delta6) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->solved) { h->err = "get_line_deltas before solve"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size() || !line_delta6) { h->err = "get_line_deltas: bad argument"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size() || !line_delta6) { h->err = "get_line_deltas: bad argument"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     const int n = d.line_end - d.line_begin;
     if (n > 0) HIP_TRY(hipMemcpy(line_delta6, h->d_xline.p + (size_t)h->fin[w].s.cur * 6 * h->n_line_tot + 6 * (size_t)d.line_begin, sizeof(double) * 6 * n, hipMemcpyDeviceToHost));
     return SADVIO_OK;
@@ -988,14 +205,14 @@ int sadvio_ba_get_line_deltas(sadvio_ba_handle* h, int32_t w, double* line_delta
 int sadvio_ba_set_pose_priors(sadvio_ba_handle* h, int32_t w, int32_t n, const sadvio_pose_prior* pr) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "set_pose_priors before set_windows"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size() || n < 0 || (n > 0 && !pr)) { h->err = "set_pose_priors: bad argument"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size() || n < 0 || (n > 0 && !pr)) { h->err = "set_pose_priors: bad argument"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     auto& v = h->priors_per_win[w];
     v.clear();
     for (int i = 0; i < n; i++) {
-        if (pr[i].kf < 0 || pr[i].kf >= h->wins[w].d.n_kf) { h->err = "set_pose_priors: kf out of range"; return SADVIO_E_INVALID_ARG; }
+        if (pr[i].kf < 0 || pr[i].kf >= h->plan.wins[w].d.n_kf) { h->err = "set_pose_priors: kf out of range"; return SADVIO_E_INVALID_ARG; }
         PriorDev d{};
-        d.kf = h->wins[w].d.kf_base + pr[i].kf;
+        d.kf = h->plan.wins[w].d.kf_base + pr[i].kf;
         memcpy(d.T_prior, pr[i].T_prior, sizeof(d.T_prior));
         memcpy(d.inf, pr[i].inf_diag, sizeof(d.inf));
         v.push_back(d);
@@ -1074,8 +291,8 @@ static bool make_imu_dev(const sadvio_imu_factor& f, int kf_base, ImuDev& o) {
 int sadvio_ba_set_imu_factors(sadvio_ba_handle* h, int32_t w, int32_t n, const sadvio_imu_factor* fs) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "set_imu_factors before set_windows"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size() || n < 0 || (n > 0 && !fs)) { h->err = "set_imu_factors: bad argument"; return SADVIO_E_INVALID_ARG; }
-    const WinDev& d = h->wins[w].d;
+    if (w < 0 || w >= (int)h->plan.wins.size() || n < 0 || (n > 0 && !fs)) { h->err = "set_imu_factors: bad argument"; return SADVIO_E_INVALID_ARG; }
+    const WinDev& d = h->plan.wins[w].d;
     if (n > 0 && !d.has_imu) { h->err = "set_imu_factors: the window was uploaded with has_imu = 0"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     auto& v = h->imus_per_win[w];
@@ -1104,12 +321,12 @@ int sadvio_ba_set_dense_prior(sadvio_ba_handle* h, int32_t w, int32_t n_full, in
                               int32_t kf_keep, int32_t kf_col, int32_t n_keep, const int32_t* lmk_index, const int32_t* lmk_col) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "set_dense_prior before set_windows"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size() || (n_full < 0 && n_full != SADVIO_PRIOR_RESIDENT) || (n < 0 && n_full != SADVIO_PRIOR_RESIDENT) || n_keep < 0) { h->err = "set_dense_prior: bad argument"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size() || (n_full < 0 && n_full != SADVIO_PRIOR_RESIDENT) || (n < 0 && n_full != SADVIO_PRIOR_RESIDENT) || n_keep < 0) { h->err = "set_dense_prior: bad argument"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     // a window sharded over several GPUs carries a dense prior too (round 5): every rank holds the prior and its variables — the kept
     // frame is replicated anyway, the kept landmarks are in every rank's window (with their observations on rank 0 only:
     // sadvio_amd/sharding.py) — rank 0 adds J^T J / J^T r to the all-reduced system, every rank evaluates the cost with the same bits
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     DensePriorHost D;
     const bool resident = n_full == SADVIO_PRIOR_RESIDENT;
     if (resident) {
@@ -1147,7 +364,7 @@ int sadvio_ba_set_dense_prior(sadvio_ba_handle* h, int32_t w, int32_t n_full, in
     }
     h->dprior_per_win[w] = std::move(D);
     if (h->defer) { h->pending = true; return SADVIO_OK; }
-    if (!h->sparse_per_win[w].empty()) return build_layout(h);  // which sparse factors are eliminable may change
+    if (!h->sparse_per_win[w].empty()) return layout_build(h);  // which sparse factors are eliminable may change
     h->up.reset();
     int rc = layout_reduced(h);
     if (rc != SADVIO_OK) return rc;
@@ -1158,9 +375,9 @@ int sadvio_ba_set_dense_prior(sadvio_ba_handle* h, int32_t w, int32_t n_full, in
 int sadvio_ba_set_sparse_priors(sadvio_ba_handle* h, int32_t w, int32_t n, const sadvio_sparse_prior* f) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "set_sparse_priors before set_windows"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size() || n < 0 || (n > 0 && !f)) { h->err = "set_sparse_priors: bad argument"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size() || n < 0 || (n > 0 && !f)) { h->err = "set_sparse_priors: bad argument"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     for (int i = 0; i < n; i++) {
         const sadvio_sparse_prior& s = f[i];
         // A window sharded over several GPUs carries the SPARSIFIED VIO prior (what sparsifyVIO produces): IMUPriordx is a
@@ -1187,7 +404,7 @@ int sadvio_ba_set_sparse_priors(sadvio_ba_handle* h, int32_t w, int32_t n, const
     }
     h->sparse_per_win[w].assign(f, f + n);
     if (h->defer) { h->pending = true; return SADVIO_OK; }
-    return build_layout(h);  // eliminable pose-to-landmark factors become pseudo-observations: the tiles change
+    return layout_build(h);  // eliminable pose-to-landmark factors become pseudo-observations: the tiles change
 }
 
 }  // extern "C"
@@ -1201,7 +418,7 @@ int sadvio_ba_marginalize(sadvio_ba_handle* h, int32_t w, const sadvio_marg_requ
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "marginalize before set_windows"; return SADVIO_E_STATE; }
     if (h->defer) { h->err = "marginalize between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (!rq || w < 0 || w >= (int)h->wins.size()) { h->err = "marginalize: bad argument"; return SADVIO_E_INVALID_ARG; }
+    if (!rq || w < 0 || w >= (int)h->plan.wins.size()) { h->err = "marginalize: bad argument"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "marginalize: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
     return marginalize(h, w, rq, res, lmk_col_out, J_out, r0_out);
 }
@@ -1248,10 +465,10 @@ int sadvio_ba_marginalize_relative(sadvio_ba_handle* h, int32_t w, int32_t kf_a,
     if (!h || !inf36) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "marginalize_relative before set_windows"; return SADVIO_E_STATE; }
     if (h->defer) { h->err = "marginalize_relative between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "marginalize_relative: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "marginalize_relative: window out of range"; return SADVIO_E_INVALID_ARG; }
     if (eig_cut_mode != SADVIO_EIG_CUT_REFERENCE && eig_cut_mode != SADVIO_EIG_CUT_NOISE_FLOOR) { h->err = "marginalize_relative: bad eig_cut_mode"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "marginalize_relative: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     if (kf_a < 0 || kf_a >= d.n_kf || kf_b < 0 || kf_b >= d.n_kf || kf_a == kf_b) { h->err = "marginalize_relative: bad key-frame index"; return SADVIO_E_INVALID_ARG; }
     if (d.has_imu) { h->err = "marginalize_relative: frames with IMU states are not supported (the reference's own column layout for them is inconsistent, BundleAdjustmentCERESAnalytic.cpp:705-737)"; return SADVIO_E_INVALID_ARG; }
     return marginalize_relative(h, w, kf_a, kf_b, eig_cut_mode, inf36, Ak144);
@@ -1264,7 +481,7 @@ int sadvio_ba_sparsify(sadvio_ba_handle* h, int32_t w, int32_t vio, int32_t nf, 
     if (n_out) *n_out = 0;
     if (!h->uploaded) { h->err = "sparsify before set_windows"; return SADVIO_E_STATE; }
     if (h->defer) { h->err = "sparsify between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size() || !n_out || !out || n_keep < 0 || (n_keep > 0 && (!lmk_index || !lmk_col))) { h->err = "sparsify: bad argument"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size() || !n_out || !out || n_keep < 0 || (n_keep > 0 && (!lmk_index || !lmk_col))) { h->err = "sparsify: bad argument"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "sparsify: the window is sharded over several GPUs (linearisation values of a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
     return sparsify(h, w, vio, nf, n, J, kf_keep, kf_col, n_keep, lmk_index, lmk_col, n_out, out);
 }
@@ -1435,14 +652,14 @@ int sadvio_ba_solve(sadvio_ba_handle* h, const sadvio_solve_options* opts, sadvi
 int sadvio_ba_get_deltas(sadvio_ba_handle* h, int32_t w, double* pose, double* lmk, double* dv, double* dba, double* dbg) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->solved) { h->err = "get_deltas before solve"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "get_deltas: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "get_deltas: window out of range"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     const int cur = h->fin[w].s.cur;
     // One read-back per solve: both buffers of every delta array go to a pinned host buffer with asynchronous copies and ONE
     // synchronisation (a pageable hipMemcpy per array and window costs 30 - 80 us each); every get_deltas of this solve is then
     // a host memcpy. Layout: xp [2][6 n_kf] | xl [2][3 n_lmk] | xv | xba | xbg [2][3 n_kf] each.
-    const size_t nk = (size_t)h->n_kf_tot, nl = (size_t)h->n_lmk_tot;
+    const size_t nk = (size_t)h->plan.n_kf_tot, nl = (size_t)h->plan.n_lmk_tot;
     const size_t o_xp = 0, o_xl = o_xp + 12 * nk, o_xv = o_xl + 6 * nl, o_xba = o_xv + 6 * nk, o_xbg = o_xba + 6 * nk, total = o_xbg + 6 * nk;
     if (!h->deltas_cached) {
         if (h->h_deltas_cap < total) {
@@ -1452,7 +669,7 @@ int sadvio_ba_get_deltas(sadvio_ba_handle* h, int32_t w, double* pose, double* l
             h->h_deltas_cap = total + total / 2;
         }
         bool any_imu = false;
-        for (const auto& hw : h->wins) any_imu |= hw.d.has_imu != 0;
+        for (const auto& hw : h->plan.wins) any_imu |= hw.d.has_imu != 0;
         HIP_TRY(hipMemcpyAsync(h->h_deltas + o_xp, h->d_xp.p, sizeof(double) * 12 * nk, hipMemcpyDeviceToHost, h->stream));
         if (nl) HIP_TRY(hipMemcpyAsync(h->h_deltas + o_xl, h->d_xl.p, sizeof(double) * 6 * nl, hipMemcpyDeviceToHost, h->stream));
         if (any_imu) {
@@ -1477,7 +694,7 @@ int sadvio_ba_get_deltas(sadvio_ba_handle* h, int32_t w, double* pose, double* l
 int sadvio_ba_get_trace(sadvio_ba_handle* h, int32_t w, int32_t cap_rows, double* rows8, int32_t* n_rows) {
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->solved) { h->err = "get_trace before solve"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size() || cap_rows < 0 || (cap_rows > 0 && !rows8)) { h->err = "get_trace: bad argument"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size() || cap_rows < 0 || (cap_rows > 0 && !rows8)) { h->err = "get_trace: bad argument"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     const int stride = h->last_slots + 2;
     const int n = std::min(h->fin[w].s.iter + 1, stride);
@@ -1489,9 +706,9 @@ int sadvio_ba_get_trace(sadvio_ba_handle* h, int32_t w, int32_t cap_rows, double
 
 int sadvio_ba_get_ids(sadvio_ba_handle* h, int32_t w, int64_t* kf_id, int64_t* lmk_id) {
     if (!h) return SADVIO_E_INVALID_ARG;
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "get_ids: window out of range"; return SADVIO_E_INVALID_ARG; }
-    if (kf_id) memcpy(kf_id, h->wins[w].kf_id.data(), sizeof(int64_t) * h->wins[w].kf_id.size());
-    if (lmk_id) memcpy(lmk_id, h->wins[w].lmk_id.data(), sizeof(int64_t) * h->wins[w].lmk_id.size());
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "get_ids: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (kf_id) memcpy(kf_id, h->plan.wins[w].kf_id.data(), sizeof(int64_t) * h->plan.wins[w].kf_id.size());
+    if (lmk_id) memcpy(lmk_id, h->plan.wins[w].lmk_id.data(), sizeof(int64_t) * h->plan.wins[w].lmk_id.size());
     return SADVIO_OK;
 }
 
@@ -1500,9 +717,9 @@ int sadvio_ba_linearize(sadvio_ba_handle* h, int32_t w, const double* pose_delta
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "linearize before set_windows"; return SADVIO_E_STATE; }
     if (h->defer) { h->err = "linearize between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "linearize: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "linearize: window out of range"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     HIP_TRY(hipMemsetAsync(h->d_xp.p, 0, sizeof(double) * h->d_xp.n, h->stream));
     HIP_TRY(hipMemsetAsync(h->d_xl.p, 0, sizeof(double) * h->d_xl.n, h->stream));
     if (pose_delta6) HIP_TRY(hipMemcpyAsync(h->d_xp.p + 6 * (size_t)d.kf_base, pose_delta6, sizeof(double) * 6 * d.n_kf, hipMemcpyHostToDevice, h->stream));
@@ -1513,14 +730,14 @@ int sadvio_ba_linearize(sadvio_ba_handle* h, int32_t w, const double* pose_delta
     DevPtrs P = make_ptrs(h, o, 1);
     double* pr = h->d_probe.p; double* pj = pr + 2 * (size_t)d.n_obs; double* pl = pj + 12 * (size_t)d.n_obs;
     int blocks = (d.n_obs + 255) / 256;
-    if (h->factor_type == SADVIO_FACTOR_PIXEL) hipLaunchKernelGGL(k_linearize_probe<0>, dim3(blocks), dim3(256), 0, h->stream, P, w, pr, pj, pl);
+    if (h->plan.factor_type == SADVIO_FACTOR_PIXEL) hipLaunchKernelGGL(k_linearize_probe<0>, dim3(blocks), dim3(256), 0, h->stream, P, w, pr, pj, pl);
     else hipLaunchKernelGGL(k_linearize_probe<1>, dim3(blocks), dim3(256), 0, h->stream, P, w, pr, pj, pl);
     HIP_TRY(hipGetLastError());
     std::vector<double> hb(20 * (size_t)d.n_obs);
     HIP_TRY(hipMemcpyAsync(hb.data(), pr, sizeof(double) * 20 * (size_t)d.n_obs, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (int a = 0; a < d.n_obs; a++) {
-        const int src = h->obs_perm[d.obs_base + a];  // caller's index of the observation stored at position a
+        const int src = h->plan.obs_perm[d.obs_base + a];  // caller's index of the observation stored at position a
         if (src < 0) continue;                          // pseudo-observation
         if (r2) memcpy(r2 + 2 * (size_t)src, &hb[2 * (size_t)a], 16);
         if (Jp12) memcpy(Jp12 + 12 * (size_t)src, &hb[2 * (size_t)d.n_obs + 12 * (size_t)a], 96);
@@ -1791,9 +1008,9 @@ int sadvio_ba_landmark_chi2(sadvio_ba_handle* h, int32_t w, const double* pose_d
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "landmark_chi2 before set_windows"; return SADVIO_E_STATE; }
     if (h->defer) { h->err = "landmark_chi2 between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "landmark_chi2: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "landmark_chi2: window out of range"; return SADVIO_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     if (d.n_lmk == 0) return SADVIO_OK;
     const SrcWin& S = h->src[w];
     // image bounds per stored camera (identical cameras are stored once; they must agree on the image size)
@@ -1816,8 +1033,8 @@ int sadvio_ba_landmark_chi2(sadvio_ba_handle* h, int32_t w, const double* pose_d
     DevPtrs P = make_ptrs(h, o, 1);
     P.xp = d_sxp - 6 * (ptrdiff_t)d.kf_base; P.xl = d_sxl - 3 * (ptrdiff_t)d.lmk_base;  // the kernel indexes globally
     const int blocks = (d.n_lmk + 63) / 64;
-    const double isig = pixel_sigma > 0.0 ? 1.0 / pixel_sigma : (h->factor_type == SADVIO_FACTOR_PIXEL ? 0.0 : 1.0);  // 0: cam_isig
-    if (h->factor_type == SADVIO_FACTOR_PIXEL) hipLaunchKernelGGL(k_lmk_chi2<0>, dim3(blocks), dim3(64), 0, h->stream, P, w, d_wh, isig, d_out);
+    const double isig = pixel_sigma > 0.0 ? 1.0 / pixel_sigma : (h->plan.factor_type == SADVIO_FACTOR_PIXEL ? 0.0 : 1.0);  // 0: cam_isig
+    if (h->plan.factor_type == SADVIO_FACTOR_PIXEL) hipLaunchKernelGGL(k_lmk_chi2<0>, dim3(blocks), dim3(64), 0, h->stream, P, w, d_wh, isig, d_out);
     else hipLaunchKernelGGL(k_lmk_chi2<1>, dim3(blocks), dim3(64), 0, h->stream, P, w, d_wh, isig, d_out);
     HIP_TRY(hipGetLastError());
     std::vector<double> hb(2 * (size_t)d.n_lmk);
@@ -1839,9 +1056,9 @@ int sadvio_ba_landmark_chi2_models(sadvio_ba_handle* h, int32_t w, const double*
     if (!h) return SADVIO_E_INVALID_ARG;
     if (!h->uploaded) { h->err = "landmark_chi2_models before set_windows"; return SADVIO_E_STATE; }
     if (h->defer) { h->err = "landmark_chi2_models between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "landmark_chi2_models: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "landmark_chi2_models: window out of range"; return SADVIO_E_INVALID_ARG; }
     if (!models) { h->err = "landmark_chi2_models: null model table"; return SADVIO_E_INVALID_ARG; }
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     const SrcWin& S = h->src[w];
     // model and image bounds per stored camera (identical cameras are stored once; they must agree on both)
     std::vector<double> wh(2 * (size_t)d.n_cam, -1.0);
@@ -1873,7 +1090,7 @@ int sadvio_ba_landmark_chi2_models(sadvio_ba_handle* h, int32_t w, const double*
     memcpy(up.data() + n_wh, md.data(), sizeof(double) * n_md);
     if (obs_uv)                          // the measured pixels in the stored observation order (obs_perm: stored position -> caller's index)
         for (int a = 0; a < d.n_obs; a++) {
-            const int src = h->obs_perm[d.obs_base + a];
+            const int src = h->plan.obs_perm[d.obs_base + a];
             if (src >= 0) { up[n_wh + n_md + 2 * (size_t)a] = obs_uv[2 * (size_t)src]; up[n_wh + n_md + 2 * (size_t)a + 1] = obs_uv[2 * (size_t)src + 1]; }
         }
     if (pose_delta6) memcpy(up.data() + n_wh + n_md + n_uv, pose_delta6, sizeof(double) * n_xp);
@@ -1885,9 +1102,9 @@ int sadvio_ba_landmark_chi2_models(sadvio_ba_handle* h, int32_t w, const double*
     const double* k_wh = d_wh - 2 * (ptrdiff_t)d.cam_base;                               // ... the camera tables too
     const CamModelDev* k_md = (const CamModelDev*)d_md - (ptrdiff_t)d.cam_base;
     const int blocks = (d.n_lmk + 63) / 64;
-    const double isig = pixel_sigma > 0.0 ? 1.0 / pixel_sigma : (h->factor_type == SADVIO_FACTOR_PIXEL ? 0.0 : 1.0);  // 0: cam_isig
+    const double isig = pixel_sigma > 0.0 ? 1.0 / pixel_sigma : (h->plan.factor_type == SADVIO_FACTOR_PIXEL ? 0.0 : 1.0);  // 0: cam_isig
     const double* k_uv = obs_uv ? d_uv : nullptr;
-    if (h->factor_type == SADVIO_FACTOR_PIXEL) hipLaunchKernelGGL(k_lmk_chi2_models<0>, dim3(blocks), dim3(64), 0, h->stream, P, w, k_wh, k_md, k_uv, isig, d_ob + n_ob, d_ob);
+    if (h->plan.factor_type == SADVIO_FACTOR_PIXEL) hipLaunchKernelGGL(k_lmk_chi2_models<0>, dim3(blocks), dim3(64), 0, h->stream, P, w, k_wh, k_md, k_uv, isig, d_ob + n_ob, d_ob);
     else hipLaunchKernelGGL(k_lmk_chi2_models<1>, dim3(blocks), dim3(64), 0, h->stream, P, w, k_wh, k_md, k_uv, isig, d_ob + n_ob, d_ob);
     HIP_TRY(hipGetLastError());
     std::vector<double> hb(n_ob + n_out);   // obs | out
@@ -1900,7 +1117,7 @@ int sadvio_ba_landmark_chi2_models(sadvio_ba_handle* h, int32_t w, const double*
     }
     if (obs_chi2)
         for (int a = 0; a < d.n_obs; a++) {
-            const int src = h->obs_perm[d.obs_base + a];
+            const int src = h->plan.obs_perm[d.obs_base + a];
             if (src >= 0) obs_chi2[src] = hb[(size_t)a];
         }
     return SADVIO_OK;

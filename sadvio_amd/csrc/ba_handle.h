@@ -17,7 +17,7 @@
 
 #include "../../include/sadvio_ba.h"
 #include "kernels.h"
-#include "tile_pack.h"
+#include "layout_plan.h"
 #include "dense_chol.h"
 #include "marg_kernels.h"
 #include "lm_kernels.h"
@@ -66,12 +66,6 @@ struct KernelClass {
     long long launches = 0;
 };
 
-struct HostWin {
-    WinDev d;
-    std::vector<int64_t> kf_id, lmk_id;
-    int hb_lmk = 0;  // max distance (in free key-frame index) between two key-frames observing one landmark
-};
-
 }  // namespace
 
 // RCCL (all-reduce of the reduced system over xGMI), loaded on first use: single-GPU solves never touch it.
@@ -87,25 +81,6 @@ struct RcclLib {
     int (*comm_count)(void*, int*) = nullptr;
     int (*comm_user_rank)(void*, int*) = nullptr;
     int (*comm_cu_device)(void*, int*) = nullptr;
-};
-
-// Deep copy of a caller's window (set_windows) + the observation arrays actually tiled: pose-to-landmark NFR factors
-// whose landmark can be eliminated are appended to the landmark's observation list as two pseudo-observations
-// (rows 0-1 and row 2 of the 3-row factor), so that they ride the ordinary Schur elimination.
-struct SrcWin {
-    sadvio_flat_window v{};   // view into the vectors below
-    std::vector<int64_t> kf_id, lmk_id;
-    std::vector<double> kf_T, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_sigma, lmk_p, obs_meas;
-    std::vector<uint8_t> kf_const, lmk_const;
-    std::vector<int32_t> lmk_obs_ptr, obs_kf, obs_cam;
-    // augmented observation list (what build_layout tiles) and its map to the caller's observation index (-1 = pseudo)
-    std::vector<int32_t> a_ptr, a_kf, a_cam, a_src;
-    std::vector<double> a_meas;
-    // cameras with identical (K, T_s_f, sigma) are stored once: SaDVIO has one ImageSensor object per (frame, camera),
-    // i.e. 2 x N_kf table entries that are all copies of the rig's two cameras
-    std::vector<double> u_cam_K, u_cam_T, u_cam_sigma;
-    std::vector<int32_t> u_obs_cam;
-    std::vector<int> cam_map;   // caller's camera index -> stored camera index
 };
 
 // Host -> device uploads of one layout build are packed into ONE pinned staging buffer, copied with one
@@ -127,6 +102,7 @@ struct UploadBatch {
     char* pinned = nullptr; size_t pinned_cap = 0, used = 0;   // sources are packed straight into pinned memory
     char* dev = nullptr; size_t dev_cap = 0;
     bool failed = false;
+    bool trace = false;   // SADVIO_DEBUG & 8192: flush prints the size and FNV-1a hash of every item's payload (scripts/layout_same_uploads.py)
     // flush() does not wait: the staged copy + scatter are stream work like the kernels that read their output. The pinned buffer is
     // only touched again (next add / grow) after the event recorded behind the copy has fired — by then it normally has
     hipEvent_t ev = nullptr;
@@ -159,6 +135,12 @@ struct UploadBatch {
         const size_t total = data_bytes + items.size() * sizeof(UploadItem);
         reserve(total);
         if (failed) { failed = false; items.clear(); used = 0; return hipErrorOutOfMemory; }
+        if (trace)
+            for (const UploadItem& u : items) {
+                unsigned long long f = 0xcbf29ce484222325ULL;
+                for (unsigned long long i = 0; i < u.bytes; i++) f = (f ^ (unsigned char)pinned[u.off + i]) * 0x100000001b3ULL;
+                fprintf(stderr, "[sadvio dbg] upload %llu bytes fnv1a %016llx\n", u.bytes, f);
+            }
         hipError_t e = hipSuccess;
         // every error return drops the queue: callers that do not reset() afterwards (marginalize, sparsify) must not re-send it
         auto drop = [&](hipError_t err) { items.clear(); used = 0; return err; };
@@ -179,14 +161,6 @@ struct UploadBatch {
         return e;
     }
     ~UploadBatch() { wait(); if (ev) (void)hipEventDestroy(ev); if (pinned) (void)hipHostFree(pinned); if (dev) (void)hipFree(dev); }
-};
-
-struct DensePriorHost {
-    int n_full = 0, n = 0, kf_keep = -1, kf_col = 0;
-    bool resident = false;      // J, r0 = the handle's prior (PriorState), copied device to device
-    unsigned long long serial = 0;   // ... as it was when set_dense_prior named it
-    std::vector<double> J, r0;
-    std::vector<int> lmk_index, lmk_col;
 };
 
 // The handle's marginalisation prior: what the reference keeps in `_marginalization_last` inside the optimizer between
@@ -248,30 +222,13 @@ struct CovBatchScratch {
 };
 
 // Work buffers of sadvio_ba_marginalize_relative_batch (rel_driver.h), grown on demand, and the per-key-frame landmark lists of one
-// window: built by the first batch call on a layout, dropped with the layout (build_layout).
+// window: built by the first batch call on a layout, dropped with the layout (layout_build).
 struct RelScratch {
     DevBuf<int> pairs, kf_ptr, kf_lmk, n_shared, status;   // pairs: [2][n_pair] kf_a | kf_b
     DevBuf<double> inf, Ak, Tab;
     std::vector<int> h_pairs, h_ptr, h_lmk, h_last;
     int csr_win = -1;      // window the lists on the device describe (-1: none)
     int n_kf_lmk = 0;
-};
-
-struct LineSetHost {   // deep copy of a sadvio_line_set
-    std::vector<int64_t> id;
-    std::vector<double> T, model, meas;
-    std::vector<unsigned char> is_const;
-    std::vector<int> ptr, obs_kf, obs_cam;
-    int n() const { return (int)id.size(); }
-};
-
-// Host-side work arrays of build_layout, kept between calls: a sliding-window back end calls set_windows once per key-frame,
-// and ~2 MB of fresh std::vectors per call are ~500 page faults (more than the layout arithmetic itself).
-struct LayoutScratch {
-    std::vector<double> kf_T0, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_isig, lmk_p, obs_meas;
-    std::vector<int> kf_fidx, lmk_ob, lmk_oe, obs_kf, obs_cam, tile_kf, tile_row, tile_lmk, pack_order, pack_cut, pkf, pcam, run_max, idx, mark, add, kfs, slot_of, chunk_ob, chunk_lm, perm;
-    std::vector<unsigned char> lmk_const, obs_slot, obs_lslot;
-    std::vector<char> held;
 };
 
 // The diagnostic switches of DESIGN.md 4 (environment), read ONCE when the handle is created: none is needed in production, and none is
@@ -301,22 +258,15 @@ struct EnvCfg {
 struct sadvio_ba_handle {
     EnvCfg env;
     sadvio_ba_config cfg{};
-    LayoutScratch ls;
+    LayoutPlan plan;   // the current layout as host tables (layout_plan.h); layout_driver.h puts it on the device
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
     // host mirrors
-    std::vector<HostWin> wins;
-    std::vector<Tile> tiles;
     std::vector<PriorDev> priors;
-    std::vector<int> obs_perm;  // device observation position -> caller's observation index (within window)
     std::vector<std::vector<PriorDev>> priors_per_win;
     std::vector<std::vector<ImuDev>> imus_per_win;
     std::vector<ImuDev> imus;
-    int n_kf_tot = 0, n_cam_tot = 0, n_lmk_tot = 0, n_obs_tot = 0, np_tot = 0;
-    long long s_tot = 0;
-    int factor_type = 0;
-    int max_n_kf = 0, max_npose = 0, max_np = 0, n_big = 0;
     DevBuf<int> d_big_info;
     DevBuf<double> d_big_M;     // inverse diagonal blocks of the wide-panel dense solver, 96 x 96 per 96 columns (+ the factors' tiles)
     DevBuf<double> d_big_Lx;    // its out-of-place panels
@@ -332,7 +282,6 @@ struct sadvio_ba_handle {
     sadvio_allreduce_fn coll_fn = nullptr;
     void* coll_ctx = nullptr;
     RcclLib rccl;
-    long long red_total = 0;  // doubles in [S | gred | gfull | hdiag | rank_b], the buffer of the per-step all-reduce
     DevBuf<double> d_rank_b, d_rank_s;
     // dense marginalisation priors (host copies, one per window) and the layout they induce
     std::vector<DensePriorHost> dprior_per_win;
@@ -344,8 +293,6 @@ struct sadvio_ba_handle {
     double cov_huber_a = 0.0;   // huber_a of the last solve: sadvio_ba_covariance corrects the visual factors as that solve did
     bool cov_use_lm = false;    // ... and whether the throughput kernels ran it (covariance is then refused)
     std::vector<SrcWin> src;                       // caller windows (deep copies)
-    std::vector<std::vector<char>> sp_elim;        // per window, per sparse factor: handled as pseudo-observations
-    std::vector<int> n_obs_user;                   // caller's observation count per window
     std::vector<std::vector<sadvio_sparse_prior>> sparse_per_win;
     std::vector<LineSetHost> lines_per_win;        // linexd landmarks
     DevBuf<LineDev> d_lines;
@@ -357,10 +304,6 @@ struct sadvio_ba_handle {
     int n_sp_list = 0;   // sparse prior factors evaluated by sparse_factor_eval (all windows)
     size_t n_sparse_tot = 0;
     DevBuf<double> d_sp_scratch;
-    std::vector<unsigned char> h_lmk_const_user;  // as given by the caller
-    std::vector<int> h_lmk_ob, h_lmk_oe, h_kf_fidx, h_obs_kf;
-    bool user_lmk_const = false;
-    int n_kept = 0;
     DevBuf<int> d_lmk_red, d_kept_obs, d_dp_ints;
     DevBuf<double> d_dp_data;
     int last_slots = 0;
@@ -374,24 +317,17 @@ struct sadvio_ba_handle {
     DevBuf<unsigned char> d_lmk_const;
     DevBuf<int> d_lmk_ob, d_lmk_oe, d_obs_kf, d_obs_cam, d_tile_kf, d_tile_row, d_tile_lmk;
     DevBuf<int> d_pre_lane, d_pre_kf;     // first-round packets of the latency kernels (kernels.h: DevPtrs::pre_lane), few-tile submissions only
-    bool pre_ok = false, pre_dirty = false;
+    bool pre_dirty = false;
     DevBuf<int> d_rank_col; DevBuf<double> d_rank_x;       // refine_rank_by_eigenvalue (guarded calls only): pivot column per step, the solved vectors
     DevBuf<unsigned char> d_obs_slot, d_obs_lslot;
     DevBuf<int> d_chunk_ob, d_chunk_lm, d_tile_perm;   // chunk tables of the throughput kernels (lm_kernels.h)
     DevBuf<int> d_jac_ints;               // pivoting / rank of the Cholesky-preconditioned Jacobi
     DevBuf<double> d_jac_dbl;             // its remaining diagonal + threshold
-    DevBuf<double> d_lm_hg, d_lm_dt, d_lm_sacc;
+    DevBuf<double> d_lm_hg, d_lm_dt, d_lm_sacc;   // throughput path: per-landmark H_ll | g_l, per-tile key-frame sums and cost sums (each per delta buffer)
     DevBuf<int> d_lm_sub;                 // work list of k_lm_pass (tile, sub-block), see DevPtrs
-    int lm_n_sub = 0, lm_ksub = 1, lm_sub_per_item = 8;   // sub-blocks per work item of k_lm_pass (8 = the whole tile: MAX tile = 512 landmarks)   // throughput path: elimination records, per-landmark H_ll | g_l and per-tile key-frame sums (both per delta buffer)
-    int lm_max_cam = 1;
     int hidden_eig_count = 0;             // sparsify: priors of full rank by their pivots whose inverse showed an eigenvalue that may lie below the cut (SADVIO_DEBUG prints it)
     int marg_stats[4] = {0, 0, 0, 0};     // Cholesky-form marginalisations: calls | took the unpivoted route | tried it and fell back | calls whose rank the eigenvalue refinement lowered
-    int lm_sub_obs = 0;                   // most observations of LM_PASS_THREADS consecutive landmarks of a tile (LDS staging of k_lm_pass)
-    bool gemm_run4 = false;               // a tile on the MFMA path holds runs of 3 - 4 observations on one key-frame (k_build<.., RARE = true> only)
-    bool lm_ok = false;                   // every tile is on the MFMA path and chunked: k_build_obs / k_lm_pass may run
-    long long lm_landmarks = 0;
     DevBuf<double> d_ptab;
-    int max_tile_kf = 1, max_tile_free = 0, max_gemm_free = 0;
     DevBuf<double> d_obs_meas;
     DevBuf<PriorDev> d_priors;
     DevBuf<double> d_prior_lin;   // [2][n_prior][PRIOR_LIN], see DevPtrs::prior_lin
@@ -413,7 +349,6 @@ struct sadvio_ba_handle {
     hipGraphExec_t graph_exec = nullptr;
     std::vector<unsigned char> graph_key;
     DevBuf<double> d_probe;
-    bool has_lmk_const = false;
     // profiling
     std::vector<KernelClass> kclasses;
     hipStream_t side = nullptr;            // IMU factor evaluation runs here, concurrently with k_build / k_backsub

@@ -184,5 +184,12 @@ constexpr int PRIOR_LIN = 28;        // doubles of a pose prior's linearisation 
 constexpr int PRE_KF = 8;            // key-frames of a tile's list carried by its first-round packet (covers the first 256 / POSE_TAB = 6 tables)
 constexpr int PRE_MAX_TILES = 1024;  // submissions with more tiles run without the packets (batches: the throughput regime)
 constexpr int MAX_LDS_NP = 174;     // packed lower triangle incl. rhs row + panel strip: ~150 KB
+constexpr int LM_CHUNK = 12;            // landmarks per MFMA chunk of the throughput kernels (12 x 5 observations fill 60 of 64 lanes)
+constexpr int LM_PASS_THREADS = 64;     // k_lm_pass: one wave per tile and sub-block of 64 landmarks (measured: 64 > 128 > 256 > 192 threads, 211 / 202 / 188 / 163 k it/s)
+
+// Size of the tile-packed image of a reduced system that is solved in LDS (chol16.h), for the host's layout and the kernels alike
+constexpr int c16_blocks(int n_rows) { return (n_rows + 15) >> 4; }
+// doubles of the image of an N-column system (+ the right-hand-side row)
+constexpr int c16_size(int N) { return (c16_blocks(N + 1) * (c16_blocks(N + 1) + 1) / 2) << 8; }
 
 }  // namespace sadvio

@@ -25,6 +25,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_types.h"
+
 namespace sadvio {
 
 typedef double c16_d4 __attribute__((ext_vector_type(4)));
@@ -37,9 +39,7 @@ constexpr int C16_WORK = 2 * C16_PUB + 64 + C16_WT;   // doubles of the exchange
 __host__ __device__ constexpr int c16_tile(int I, int J) { return ((I * (I + 1)) >> 1) + J; }
 // element (i, j), i >= j, of the tile-packed lower triangle (diagonal tiles: the lower half; see c16_symmetrize)
 __host__ __device__ constexpr int c16_index(int i, int j) { return (c16_tile(i >> 4, j >> 4) << 8) + ((j & 15) << 4) + (i & 15); }
-__host__ __device__ constexpr int c16_blocks(int n_rows) { return (n_rows + 15) >> 4; }
-// doubles of the image of an N-column system (+ the right-hand-side row)
-__host__ __device__ constexpr int c16_size(int N) { return (c16_blocks(N + 1) * (c16_blocks(N + 1) + 1) / 2) << 8; }
+// c16_blocks, c16_size: ba_types.h (the host's layout sizes the image with them)
 
 __device__ __forceinline__ double c16_readlane(double v, int lane) {
     int lo = __double2loint(v), hi = __double2hiint(v);

@@ -13,7 +13,7 @@
 // xl[1 - cur] exactly as k_backsub does on the latency path; k_decide (shared) is the only writer of cur and flips it when, and only
 // when, it accepts the candidate; the closing k_decide launch copies the state to FinalRec, which the host keeps in fin[w].s.
 // xp / xl (and xv, xba, xbg) at fin[w].s.cur are therefore the accepted state of window w on either path — the buffer get_deltas
-// reads. (ii) The kernels here read the window's arrays, the observation arrays and the Tile / tile_lmk lists only; build_layout
+// reads. (ii) The kernels here read the window's arrays, the observation arrays and the Tile / tile_lmk lists only; layout_build
 // fills those for both paths (the throughput path adds chunk tables beside them, it replaces nothing).
 // Nothing of the solve is touched. Part of the library's single translation unit (ba_capi.hip); not a public header.
 #pragma once
@@ -44,8 +44,8 @@ int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* ite
     for (int it = 0; it < n_item; it++) {
         const int w = items[it].w;
         const sadvio_cov_request* rq = &items[it].rq;
-        if (w < 0 || w >= (int)h->wins.size()) { h->err = "covariance_batch: window out of range"; return SADVIO_E_INVALID_ARG; }
-        const WinDev& d = h->wins[w].d;
+        if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "covariance_batch: window out of range"; return SADVIO_E_INVALID_ARG; }
+        const WinDev& d = h->plan.wins[w].d;
         if (d.line_end > d.line_begin) { h->err = "covariance_batch: the window carries line landmarks"; return SADVIO_E_INVALID_ARG; }
         if (rq->n_kf < 0 || rq->n_pair < 0 || rq->n_lmk < -1 || (rq->n_kf > 0 && !rq->kf) || (rq->n_pair > 0 && (!rq->pair_a || !rq->pair_b)) ||
             (rq->n_lmk > 0 && !rq->lmk)) { h->err = "covariance_batch: request out of range"; return SADVIO_E_INVALID_ARG; }
@@ -62,11 +62,11 @@ int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* ite
 
 // 2. The route of every item; one unit per window that does not take the dense route
 void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, std::vector<CovbUnit>& units, std::vector<int>& unit_of) {
-    std::vector<int> of_win(h->wins.size(), -1);
+    std::vector<int> of_win(h->plan.wins.size(), -1);
     unit_of.assign((size_t)n_item, -1);
     for (int it = 0; it < n_item; it++) {
         sadvio_cov_batch_item& I = items[it];
-        const WinDev& d = h->wins[I.w].d;
+        const WinDev& d = h->plan.wins[I.w].d;
         I.status = SADVIO_OK; I.n_lmk_singular = 0;
         I.route = d.Np == 0 ? SADVIO_COV_ROUTE_NONE : (d.Np <= COVB_CAP && h->env.cov_batch_lds != 0 ? SADVIO_COV_ROUTE_LDS : SADVIO_COV_ROUTE_DENSE);
         if (I.route == SADVIO_COV_ROUTE_DENSE) continue;
@@ -119,7 +119,7 @@ int covb_groups(sadvio_ba_handle* h, std::vector<CovbUnit>& units, std::vector<C
         max_d = std::max(max_d, g.doubles); max_i = std::max(max_i, g.ints); max_r = std::max(max_r, g.r_doubles);
     }
     HIP_TRY(B.pool.alloc(max_d)); HIP_TRY(B.ipool.alloc(max_i)); HIP_TRY(B.rpool.alloc(max_r));
-    HIP_TRY(B.ptab.alloc((size_t)h->n_kf_tot * POSE_TAB));
+    HIP_TRY(B.ptab.alloc((size_t)h->plan.n_kf_tot * POSE_TAB));
     HIP_TRY(B.units.alloc(sizeof(CovUnit) * units.size()));
     HIP_TRY(B.pin(sizeof(CovUnit) * units.size() + sizeof(double) * r_tot));
     return SADVIO_OK;
@@ -142,7 +142,7 @@ int covb_assemble(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const
     bool any_kept = false, any_np = false;
     for (int u = g.u0; u < g.u1; u++) {
         const CovbUnit& U = units[u];
-        const WinDev& d = h->wins[U.w].d;
+        const WinDev& d = h->plan.wins[U.w].d;
         const size_t nl = U.nl, no = U.no, nn = U.nn;
         CovUnit& T = tab[u - g.u0];
         memset(&T, 0, sizeof(T));
@@ -171,7 +171,7 @@ int covb_assemble(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const
     d_units = (const CovUnit*)B.units.p + g.u0;
     HIP_TRY(hipMemcpyAsync((void*)d_units, tab, sizeof(CovUnit) * nu, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(B.pool.p, 0, sizeof(double) * s_tot, h->stream));
-    const bool pix = h->factor_type == SADVIO_FACTOR_PIXEL;
+    const bool pix = h->plan.factor_type == SADVIO_FACTOR_PIXEL;
     ScopedTimer t(h, "covb_assemble");
     hipLaunchKernelGGL(k_covb_tables, dim3(mx_tab, nu), dim3(256), 0, h->stream, P, d_units, B.ptab.p);
     if (mx_tiles > 0) hipLaunchKernelGGL(pix ? k_covb_assemble<0> : k_covb_assemble<1>, dim3(mx_tiles, nu), dim3(COV_THREADS), 0, h->stream, P, d_units);
@@ -206,7 +206,7 @@ int covb_landmarks(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, cons
     int blocks[2] = {0, 0};   // G = 16 | 64
     for (int u = g.u0; u < g.u1; u++) {
         const CovbUnit& U = units[u];
-        const WinDev& d = h->wins[U.w].d;
+        const WinDev& d = h->plan.wins[U.w].d;
         if (!U.R.want_lmk || d.n_lmk == 0) continue;
         const int per = COV_THREADS / U.R.G;
         int& b = blocks[U.R.G == 16 ? 0 : 1];
@@ -235,11 +235,11 @@ int covb_read_back(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items
         const double* lo = sig + U.nn;
         const int* st = (const int*)(lo + U.r_lout);
         if (st[2 * ((U.nl + 1) / 2)] != 0) { I.status = SADVIO_E_NOT_USABLE; continue; }
-        const WinDev& d = h->wins[I.w].d;
+        const WinDev& d = h->plan.wins[I.w].d;
         const sadvio_cov_request* rq = &I.rq;
         const int n = U.R.Np, dpf = d.dpf;
         auto block = [&](int ka, int kb, double* out) {
-            const int fa = h->h_kf_fidx[d.kf_base + ka], fb = h->h_kf_fidx[d.kf_base + kb];
+            const int fa = h->plan.kf_fidx[d.kf_base + ka], fb = h->plan.kf_fidx[d.kf_base + kb];
             for (int i = 0; i < dpf; i++)
                 for (int j = 0; j < dpf; j++) out[i * dpf + j] = (fa >= 0 && fb >= 0 && n > 0) ? sig[(size_t)(fa * dpf + i) * n + fb * dpf + j] : 0.0;
         };

@@ -29,9 +29,9 @@ int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const do
     if (h->world > 1) { h->err = "covariance: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
     if (h->defer) { h->err = "covariance between begin_update and commit_update"; return SADVIO_E_STATE; }
     if (!h->solved) { h->err = "covariance before solve"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "covariance: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "covariance: window out of range"; return SADVIO_E_INVALID_ARG; }
     if (!rq) { h->err = "covariance: null request"; return SADVIO_E_INVALID_ARG; }
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     if (d.line_end > d.line_begin) { h->err = "covariance: the window carries line landmarks"; return SADVIO_E_INVALID_ARG; }
     if (h->cov_use_lm) { h->err = "covariance: the batch was solved by the throughput kernels"; return SADVIO_E_INVALID_ARG; }
     if (rq->n_kf < 0 || rq->n_pair < 0 || rq->n_lmk < -1 || (rq->n_kf > 0 && !rq->kf) || (rq->n_pair > 0 && (!rq->pair_a || !rq->pair_b)) ||
@@ -48,10 +48,10 @@ int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const do
 }
 
 CovRoutes cov_routes(const sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov) {
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     CovRoutes R;
     R.cur = h->fin[w].s.cur;
-    R.pix = h->factor_type == SADVIO_FACTOR_PIXEL;
+    R.pix = h->plan.factor_type == SADVIO_FACTOR_PIXEL;
     R.Np = d.Np;
     R.kept = d.kept_end > d.kept_begin;
     R.dense = d.dp_n_full > 0;
@@ -73,10 +73,10 @@ CovDev cov_dev(sadvio_ba_handle* h, int w, const CovRoutes& R) {
 
 // 2. Allocate; linearise at x*; S = H_pp - sum_l H_pl H_ll^-1 H_lp, full symmetric, in V.S
 int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     CovScratch& V = h->cv;
     const size_t nl = (size_t)std::max(d.n_lmk, 1), no = (size_t)std::max(d.n_obs, 1), nn = (size_t)std::max(R.Np, 1) * std::max(R.Np, 1);
-    HIP_TRY(V.ptab.alloc((size_t)h->n_kf_tot * POSE_TAB));
+    HIP_TRY(V.ptab.alloc((size_t)h->plan.n_kf_tot * POSE_TAB));
     HIP_TRY(V.hll.alloc(6 * nl)); HIP_TRY(V.hinv.alloc(6 * nl)); HIP_TRY(V.status.alloc(nl)); HIP_TRY(V.ent_n.alloc(nl)); HIP_TRY(V.lout.alloc(9 * nl));
     HIP_TRY(V.ent_col.alloc(no)); HIP_TRY(V.ent_w.alloc(COV_ENT_W * no)); HIP_TRY(V.ent_hpp.alloc(COV_ENT_HPP * no));
     HIP_TRY(V.S.alloc(nn)); HIP_TRY(V.Sig.alloc(nn));
@@ -127,7 +127,7 @@ int cov_invert(sadvio_ba_handle* h, const CovRoutes& R, bool& usable) {
 
 // 4. Sigma_ll of every landmark of the window
 int cov_landmarks(sadvio_ba_handle* h, int w, const CovRoutes& R) {
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     if (!R.want_lmk || d.n_lmk == 0) return SADVIO_OK;
     SolveOpts so{};
     const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
@@ -142,7 +142,7 @@ int cov_landmarks(sadvio_ba_handle* h, int w, const CovRoutes& R) {
 // 5. One wait; the caller's blocks are picked from Sigma_pp and the landmark table on the host
 int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const CovRoutes& R, double* kf_cov, double* pair_cov, double* lmk_cov,
                   int32_t* n_lmk_singular) {
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     CovScratch& V = h->cv;
     const int n = R.Np, dpf = d.dpf;
     std::vector<double>& sig = V.h_sig; std::vector<double>& lo = V.h_lout;
@@ -161,7 +161,7 @@ int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, cons
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->cfg.profile_kernels) collect_timers(h);
     auto block = [&](int ka, int kb, double* out) {
-        const int fa = h->h_kf_fidx[d.kf_base + ka], fb = h->h_kf_fidx[d.kf_base + kb];
+        const int fa = h->plan.kf_fidx[d.kf_base + ka], fb = h->plan.kf_fidx[d.kf_base + kb];
         for (int i = 0; i < dpf; i++)
             for (int j = 0; j < dpf; j++) out[i * dpf + j] = (fa >= 0 && fb >= 0 && n > 0) ? sig[(size_t)(fa * dpf + i) * n + fb * dpf + j] : 0.0;
     };

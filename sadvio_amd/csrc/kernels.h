@@ -599,6 +599,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
     else decision_inputs(T.w, T.win_tile0, T.win_ntiles);
     bool first_valid;
     int gl_first, pre_ob, pre_oe, pre_o;     // pre_o: the lane's own observation of the first round, -1 = none
+    static_assert(MAX_LMK_OBS <= 0xff, "a first-round packet carries the landmark's observation count in 8 bits");
     if (P.pre_lane) {
         first_valid = (pl.z >> 16) & 1; gl_first = pl.x; pre_ob = pl.y; pre_oe = pl.y + (pl.z & 0xff);
         pre_o = (pl.w + (tid & 7) < (pl.z & 0xff)) ? pl.y + pl.w + (tid & 7) : -1;
@@ -2058,6 +2059,7 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, 
     // which delta buffer holds x (both are fetched, the record selects)
     bool first_valid;
     int gl_first, pre_ob, pre_oe, pre_o;
+    static_assert(MAX_LMK_OBS <= 0xff, "a first-round packet carries the landmark's observation count in 8 bits");
     if (P.pre_lane) {
         first_valid = (pl.z >> 16) & 1; gl_first = pl.x; pre_ob = pl.y; pre_oe = pl.y + (pl.z & 0xff);
         pre_o = (pl.w + (tid & 7) < (pl.z & 0xff)) ? pl.y + pl.w + (tid & 7) : -1;

@@ -26,13 +26,12 @@
 
 namespace sadvio {
 
-constexpr int LM_CHUNK = 12;            // landmarks per MFMA chunk (12 x 5 observations fill 60 of 64 lanes)
+// LM_CHUNK, LM_PASS_THREADS: ba_types.h (the host's layout cuts the chunks)
 constexpr int LM_KS = 3 * LM_CHUNK + 2; // strip row stride (doubles): 3 columns per landmark + 2 (bank spread); 32 x 38 doubles = 9.5 KB per wave
 constexpr int LM_HG = 9;                // per landmark and delta buffer: H_ll (00 01 02 11 12 22) | g_l (3) at that buffer's point
 constexpr int LM_DT_RANK = 28;          // per tile, delta buffer and free key-frame of the tile: sum Jp^T Jp (21, lower, row-major) | sum Jp^T r (6) | -
 constexpr int LM_DT_COST = MAX_GEMM_FREE_KF * LM_DT_RANK;   // then: sum r^2 (blocks in the program) | of the constant blocks | max |g_l| | -
 constexpr int LM_DT = LM_DT_COST + 4;
-constexpr int LM_PASS_THREADS = 64;     // k_lm_pass: one wave per tile and sub-block of 64 landmarks (measured: 64 > 128 > 256 > 192 threads, 211 / 202 / 188 / 163 k it/s)
 
 // LM damping of a landmark's 3 x 3 block and the inverse of its Cholesky factor (the arithmetic of group_eliminate, one lane):
 // Li = L^-1 (packed lower, sym3_chol_inverse), M = H_ll + D = L L^T

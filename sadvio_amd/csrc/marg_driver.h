@@ -392,7 +392,7 @@ MargRoutes marg_routes(const sadvio_ba_handle* h, const sadvio_marg_request* rq,
 // 1. Validate the request, lay out the columns, list the blocks. Host work only (and hipSetDevice): nothing is allocated or queued
 // before the request is known to be good.
 int marg_layout(sadvio_ba_handle* h, int w, const sadvio_marg_request* rq, MargLayout& L, sadvio_marg_result* res, int32_t* lmk_col_out) {
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     if (rq->kf_marg < 0 || rq->kf_marg >= d.n_kf || rq->kf_keep >= d.n_kf || rq->n_marg < 0 || rq->n_keep < 0 || rq->n_prior < 0 ||
         rq->n_prior > 4 || (rq->n_marg > 0 && !rq->lmk_marg) || (rq->n_keep > 0 && !rq->lmk_keep) || (rq->n_prior > 0 && !rq->priors) ||
         (rq->eig_cut_mode != SADVIO_EIG_CUT_REFERENCE && rq->eig_cut_mode != SADVIO_EIG_CUT_NOISE_FLOOR) ||
@@ -435,8 +435,8 @@ int marg_layout(sadvio_ba_handle* h, int w, const sadvio_marg_request* rq, MargL
         const int32_t* list = pass == 0 ? rq->lmk_keep : rq->lmk_marg;
         for (int k = 0; k < cnt; k++) {
             const int gl = d.lmk_base + list[k];
-            for (int o = h->h_lmk_ob[gl]; o < h->h_lmk_oe[gl]; o++)
-                if (h->h_obs_kf[o] == d.kf_base + rq->kf_marg && h->obs_perm[o] >= 0) { it2.push_back(o); it2.push_back(lcol[list[k]]); itl.push_back(gl); }  // pseudo-observations excluded
+            for (int o = h->plan.lmk_ob[gl]; o < h->plan.lmk_oe[gl]; o++)
+                if (h->plan.obs_kf[o] == d.kf_base + rq->kf_marg && h->plan.obs_perm[o] >= 0) { it2.push_back(o); it2.push_back(lcol[list[k]]); itl.push_back(gl); }  // pseudo-observations excluded
         }
     }
     L.n_items = (int)itl.size();
@@ -520,7 +520,7 @@ int marg_assemble(sadvio_ba_handle* h, const sadvio_marg_request* rq, const Marg
     if (small) { HIP_TRY(M.small.alloc(1)); h->up.add(M.small.p, &L.S, sizeof(L.S)); }
     HIP_TRY(h->up.flush(h->stream));
     if (L.n_items > 0) {
-        auto ko = h->factor_type == SADVIO_FACTOR_PIXEL ? k_marg_obs<0> : k_marg_obs<1>;
+        auto ko = h->plan.factor_type == SADVIO_FACTOR_PIXEL ? k_marg_obs<0> : k_marg_obs<1>;
         hipLaunchKernelGGL(ko, dim3((L.n_items + 127) / 128), dim3(128), 0, h->stream, P, M.ditems.p, L.n_items, M.A.p, M.b.p, N);
     }
     if (small) hipLaunchKernelGGL(k_marg_small, dim3(1), dim3(64), 0, h->stream, P, M.small.p, M.A.p, M.b.p, N);
@@ -803,7 +803,7 @@ bool nfr_sqrt_info(const double* S, int rows, bool invert_first, double* W) {
 
 // sadvio_ba_marginalize_relative behind its argument checks
 int marginalize_relative(sadvio_ba_handle* h, int w, int kf_a, int kf_b, int eig_cut_mode, double* inf36, double* Ak144) {
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     HIP_TRY(hipSetDevice(h->device));
     // preMarginalizeRelative (marginalization.cpp:532-588): a landmark of frame a is entered once per feature it has in frame b
     const int ga = d.kf_base + kf_a, gb = d.kf_base + kf_b;
@@ -812,9 +812,9 @@ int marginalize_relative(sadvio_ba_handle* h, int w, int kf_a, int kf_b, int eig
     for (int l = 0; l < d.n_lmk; l++) {
         const int gl = d.lmk_base + l;
         int ca = 0, cb = 0;
-        for (int o = h->h_lmk_ob[gl]; o < h->h_lmk_oe[gl]; o++) {
-            if (h->obs_perm[o] < 0) continue;      // pseudo-observation of a sparse prior factor
-            ca += h->h_obs_kf[o] == ga; cb += h->h_obs_kf[o] == gb;
+        for (int o = h->plan.lmk_ob[gl]; o < h->plan.lmk_oe[gl]; o++) {
+            if (h->plan.obs_perm[o] < 0) continue;      // pseudo-observation of a sparse prior factor
+            ca += h->plan.obs_kf[o] == ga; cb += h->plan.obs_kf[o] == gb;
         }
         if (ca > 0 && cb > 0) { items.push_back(gl); items.push_back(cb); m += 3 * cb; }
     }
@@ -826,7 +826,7 @@ int marginalize_relative(sadvio_ba_handle* h, int w, int kf_a, int kf_b, int eig
     HIP_TRY(hipMemsetAsync(dAk.p, 0, 144 * sizeof(double), h->stream)); HIP_TRY(hipMemsetAsync(dmax.p, 0, 8, h->stream));
     SolveOpts o{};
     DevPtrs P = make_ptrs(h, o, 1);
-    auto kl = h->factor_type == SADVIO_FACTOR_PIXEL ? k_relmarg_lmk<0> : k_relmarg_lmk<1>;
+    auto kl = h->plan.factor_type == SADVIO_FACTOR_PIXEL ? k_relmarg_lmk<0> : k_relmarg_lmk<1>;
     hipLaunchKernelGGL(kl, dim3((n_items + 63) / 64), dim3(64), 0, h->stream, P, ditems.p, n_items, ga, gb, dscr.p, dAk.p, dmax.p);
     hipLaunchKernelGGL(k_relmarg_apply, dim3((n_items + 63) / 64), dim3(64), 0, h->stream, dscr.p, n_items, m, dmax.p, dAk.p, eig_cut_mode == SADVIO_EIG_CUT_NOISE_FLOOR ? 1 : 0);
     hipLaunchKernelGGL(k_relmarg_jac, dim3(1), dim3(64), 0, h->stream, P, ga, gb, dJ.p);
@@ -892,7 +892,7 @@ int sparsify(sadvio_ba_handle* h, int w, int vio, int nf, int n, const double* J
         nf = PR.n_full; n = PR.n;
     }
     if (n <= 0 || nf <= 0) { h->err = "sparsify: empty prior"; return SADVIO_E_REFUSED; }
-    const HostWin& HW = h->wins[w];
+    const HostWin& HW = h->plan.wins[w];
     const WinDev& d = HW.d;
     const SrcWin& SW = h->src[w];
     if (vio && (kf_keep < 0 || kf_keep >= d.n_kf || kf_col < 0 || kf_col + 15 > n)) { h->err = "sparsify: kept key-frame out of range"; return SADVIO_E_INVALID_ARG; }

@@ -16,10 +16,10 @@ namespace {
 int rel_check(sadvio_ba_handle* h, int w, int n_pair, const int32_t* kf_a, const int32_t* kf_b, int eig_cut_mode, const double* inf36, const int32_t* status) {
     if (!h->uploaded) { h->err = "marginalize_relative_batch before set_windows"; return SADVIO_E_STATE; }
     if (h->defer) { h->err = "marginalize_relative_batch between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->wins.size()) { h->err = "marginalize_relative_batch: window out of range"; return SADVIO_E_INVALID_ARG; }
+    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "marginalize_relative_batch: window out of range"; return SADVIO_E_INVALID_ARG; }
     if (eig_cut_mode != SADVIO_EIG_CUT_REFERENCE && eig_cut_mode != SADVIO_EIG_CUT_NOISE_FLOOR) { h->err = "marginalize_relative_batch: bad eig_cut_mode"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "marginalize_relative_batch: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     if (d.has_imu) { h->err = "marginalize_relative_batch: frames with IMU states are not supported (the reference's own column layout for them is inconsistent, BundleAdjustmentCERESAnalytic.cpp:705-737)"; return SADVIO_E_INVALID_ARG; }
     if (n_pair < 0) { h->err = "marginalize_relative_batch: negative pair count"; return SADVIO_E_INVALID_ARG; }
     if (n_pair == 0) return SADVIO_OK;
@@ -33,16 +33,16 @@ int rel_check(sadvio_ba_handle* h, int w, int n_pair, const int32_t* kf_a, const
 // layout; the pairs; the output rows. O(n_obs) the first time, O(n_pair) afterwards; no allocation once the buffers have grown.
 int rel_index(sadvio_ba_handle* h, int w, int n_pair, const int32_t* kf_a, const int32_t* kf_b) {
     RelScratch& S = h->rel;
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     if (S.csr_win != w) {
         std::vector<int>& ptr = S.h_ptr; std::vector<int>& lst = S.h_lmk; std::vector<int>& last = S.h_last;
         ptr.assign((size_t)d.n_kf + 1, 0); last.assign((size_t)d.n_kf, -1);
         auto visit = [&](bool fill) {
             for (int l = 0; l < d.n_lmk; l++) {
                 const int gl = d.lmk_base + l;
-                for (int o = h->h_lmk_ob[gl]; o < h->h_lmk_oe[gl]; o++) {
-                    if (h->obs_perm[o] < 0) continue;
-                    const int k = h->h_obs_kf[o] - d.kf_base;
+                for (int o = h->plan.lmk_ob[gl]; o < h->plan.lmk_oe[gl]; o++) {
+                    if (h->plan.obs_perm[o] < 0) continue;
+                    const int k = h->plan.obs_kf[o] - d.kf_base;
                     if (k < 0 || k >= d.n_kf || last[k] == gl) continue;
                     last[k] = gl;
                     if (fill) lst[ptr[k]++] = gl; else ptr[k + 1]++;
@@ -74,17 +74,17 @@ int rel_index(sadvio_ba_handle* h, int w, int n_pair, const int32_t* kf_a, const
 // 3. One launch for all pairs
 int rel_launch(sadvio_ba_handle* h, int w, int n_pair, int eig_cut_mode) {
     RelScratch& S = h->rel;
-    const WinDev& d = h->wins[w].d;
+    const WinDev& d = h->plan.wins[w].d;
     SolveOpts o{};
     const DevPtrs P = make_ptrs(h, o, 1);
     RelDev R{};
     R.kf_a = S.pairs.p; R.kf_b = S.pairs.p + n_pair; R.n_pair = n_pair;
-    R.kf_base = d.kf_base; R.n_lmk_tot = h->n_lmk_tot; R.n_obs_tot = h->n_obs_tot; R.n_cam_tot = h->n_cam_tot;
+    R.kf_base = d.kf_base; R.n_lmk_tot = h->plan.n_lmk_tot; R.n_obs_tot = h->plan.n_obs_tot; R.n_cam_tot = h->plan.n_cam_tot;
     R.kf_ptr = S.kf_ptr.p; R.kf_lmk = S.kf_lmk.p; R.n_kf_lmk = S.n_kf_lmk;
     R.noise_floor = eig_cut_mode == SADVIO_EIG_CUT_NOISE_FLOOR ? 1 : 0;
     R.inf = S.inf.p; R.Ak = S.Ak.p; R.Tab = S.Tab.p; R.n_shared = S.n_shared.p; R.status = S.status.p;
     ScopedTimer t(h, "k_rel_batch");
-    hipLaunchKernelGGL(h->factor_type == SADVIO_FACTOR_PIXEL ? k_rel_batch<0> : k_rel_batch<1>, dim3((unsigned)n_pair), dim3(REL_THREADS), 0, h->stream, P, R);
+    hipLaunchKernelGGL(h->plan.factor_type == SADVIO_FACTOR_PIXEL ? k_rel_batch<0> : k_rel_batch<1>, dim3((unsigned)n_pair), dim3(REL_THREADS), 0, h->stream, P, R);
     HIP_TRY(hipGetLastError());
     return SADVIO_OK;
 }

@@ -17,39 +17,39 @@ DevPtrs make_ptrs(sadvio_ba_handle* h, const SolveOpts& o, int state_stride) {
     P.win = h->d_win.p; P.tiles = h->d_tiles.p;
     P.kf_T0 = h->d_kf_T0.p; P.kf_fidx = h->d_kf_fidx.p;
     P.xp = h->d_xp.p; P.xv = h->d_xv.p; P.xba = h->d_xba.p; P.xbg = h->d_xbg.p;
-    P.xp_stride = 6LL * h->n_kf_tot; P.xv_stride = 3LL * h->n_kf_tot; P.xl_stride = 3LL * h->n_lmk_tot;
+    P.xp_stride = 6LL * h->plan.n_kf_tot; P.xv_stride = 3LL * h->plan.n_kf_tot; P.xl_stride = 3LL * h->plan.n_lmk_tot;
     P.kf_vel = h->d_kf_vel.p; P.kf_ba = h->d_kf_ba.p; P.kf_bg = h->d_kf_bg.p;
     P.cam_K = h->d_cam_K.p; P.cam_T = h->d_cam_T.p; P.cam_isig = h->d_cam_isig.p;
     P.lmk_p = h->d_lmk_p.p; P.xl = h->d_xl.p; P.s_lmk = h->d_s_lmk.p;
-    P.lmk_const = h->has_lmk_const ? h->d_lmk_const.p : nullptr;
+    P.lmk_const = h->plan.has_lmk_const ? h->d_lmk_const.p : nullptr;
     P.lmk_ob = h->d_lmk_ob.p; P.lmk_oe = h->d_lmk_oe.p;
     P.obs_kf = h->d_obs_kf.p; P.obs_cam = h->d_obs_cam.p; P.obs_meas = h->d_obs_meas.p;
     P.obs_slot = h->d_obs_slot.p; P.tile_kf = h->d_tile_kf.p; P.tile_lmk = h->d_tile_lmk.p; P.tile_row = h->d_tile_row.p;
-    P.pre_lane = h->pre_ok ? (const int4*)h->d_pre_lane.p : nullptr; P.pre_kf = h->pre_ok ? (const int2*)h->d_pre_kf.p : nullptr;
-    P.ptab = h->d_ptab.p; P.ptab_stride = (long long)POSE_TAB * h->n_kf_tot;
+    P.pre_lane = h->plan.pre_ok ? (const int4*)h->d_pre_lane.p : nullptr; P.pre_kf = h->plan.pre_ok ? (const int2*)h->d_pre_kf.p : nullptr;
+    P.ptab = h->d_ptab.p; P.ptab_stride = (long long)POSE_TAB * h->plan.n_kf_tot;
     P.priors = h->d_priors.p; P.prior_lin = h->d_prior_lin.p; P.prior_lin_stride = (long long)h->priors.size() * PRIOR_LIN; P.n_prior_tot = (int)h->priors.size();
     P.imus = h->d_imus.p; P.imu_scratch = h->d_imu_scratch.p; P.imu_scratch_stride = (long long)h->imus.size() * IMU_ROW;
     P.S = h->d_S.p; P.gred = h->d_gred.p; P.gfull = h->d_gfull.p; P.hdiag = h->d_hdiag.p;
     P.delta = h->d_delta.p; P.s_pose = h->d_s_pose.p;
     P.dbg_ts = h->d_dbg.p;
     P.trace = h->d_trace.p; P.t_start = h->d_tstart.p;
-    P.states = h->d_states.p; P.acc = h->d_acc.p; P.tacc = h->d_tacc.p; P.n_tiles = (int)h->tiles.size();
+    P.states = h->d_states.p; P.acc = h->d_acc.p; P.tacc = h->d_tacc.p; P.n_tiles = (int)h->plan.tiles.size();
     P.state_stride = state_stride;
     P.final_out = h->h_final ? h->h_final : h->d_final.p;   // the final records go straight to pinned host memory (device-visible): no copy after the last kernel
     P.big_info = h->d_big_info.p;
     P.world = h->world; P.rank = h->rank; P.rank_b = h->d_rank_b.p; P.rank_s = h->d_rank_s.p;
-    P.lmk_red = h->d_lmk_red.p; P.kept_obs = h->d_kept_obs.p; P.n_kept = h->n_kept;
+    P.lmk_red = h->d_lmk_red.p; P.kept_obs = h->d_kept_obs.p; P.n_kept = h->plan.n_kept;
     P.dp_data = h->d_dp_data.p; P.dp_ints = h->d_dp_ints.p;
     P.sparse = h->d_sparse.p; P.sp_scratch = h->d_sp_scratch.p; P.sp_list = h->d_sp_list.p;
     P.sp_scratch_stride = (long long)std::max<size_t>(h->n_sparse_tot, 1) * SPARSE_J; P.n_imu_tot = (int)h->imus.size(); P.n_sp_list = h->n_sp_list;
     P.chunk_ob = h->d_chunk_ob.p; P.chunk_lm = h->d_chunk_lm.p; P.tile_perm = h->d_tile_perm.p; P.obs_lslot = h->d_obs_lslot.p;
-    P.lm_hg = h->d_lm_hg.p; P.lm_hg_stride = (long long)LM_HG * std::max(h->n_lmk_tot, 1);
-    P.lm_dt = h->d_lm_dt.p; P.lm_dt_stride = (long long)LM_DT * std::max<long long>((long long)h->tiles.size(), 1) * h->lm_ksub;
-    P.lm_sub = h->d_lm_sub.p; P.lm_ksub = h->lm_ksub; P.lm_sub_per_item = h->lm_sub_per_item; P.lm_sacc = h->lm_ok ? h->d_lm_sacc.p : nullptr;
+    P.lm_hg = h->d_lm_hg.p; P.lm_hg_stride = (long long)LM_HG * std::max(h->plan.n_lmk_tot, 1);
+    P.lm_dt = h->d_lm_dt.p; P.lm_dt_stride = (long long)LM_DT * std::max<long long>((long long)h->plan.tiles.size(), 1) * h->plan.lm_ksub;
+    P.lm_sub = h->d_lm_sub.p; P.lm_ksub = h->plan.lm_ksub; P.lm_sub_per_item = h->plan.lm_sub_per_item; P.lm_sacc = h->plan.lm_ok ? h->d_lm_sacc.p : nullptr;
     P.lines = h->d_lines.p; P.lobs = h->d_lobs.p; P.xline = h->d_xline.p; P.line_scratch = h->d_line_scratch.p;
     P.xline_stride = 6LL * h->n_line_tot;
     P.n_xp = (long long)h->d_xp.n; P.n_xv = (long long)h->d_xv.n; P.n_xl = (long long)h->d_xl.n;
-    P.n_win = (int)h->wins.size();
+    P.n_win = (int)h->plan.wins.size();
     P.debug = h->env.debug;
     P.o = o;
     return P;
@@ -89,7 +89,7 @@ struct BigPlan {
     BigRoute route;
     int bw;                       // rows below a block column of S that can be non-zero (block half-bandwidth + 1) * dpf
     int C;                        // band window of the band routes
-    // Copies of the window's WinDev fields of the same names (plan_solve): the routes read these, never h->wins, so that what they
+    // Copies of the window's WinDev fields of the same names (plan_solve): the routes read these, never h->plan.wins, so that what they
     // launch with is keyed. A route that needs another WinDev field gets it here, not from the handle.
     int Np, ld, dpf, red_off;
     long long S_off;
@@ -267,7 +267,7 @@ void solve_big(sadvio_ba_handle* h, const SolvePlan& pl, const BigPlan& p, int w
 // Decide one solve: state and workspace allocations, launch parameters, kernel variants, the route of every out-of-LDS window.
 int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::vector<BigPlan>& big) {
     memset(&plan, 0, sizeof(plan));
-    const int n_win = (int)h->wins.size();
+    const int n_win = (int)h->plan.wins.size();
     // Slot s (s = 0 .. slots-1) is one step attempt; with max_num_iterations = 0 Ceres still evaluates
     // iteration 0, so at least one slot is always run and the final decision is taken by k_final.
     const int slots = plan.slots = std::max(1, o.max_num_iterations);
@@ -287,48 +287,48 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     }
     DevPtrs& P = plan.P;
     P = make_ptrs(h, o, stride);
-    const int n_tiles = (int)h->tiles.size();
+    const int n_tiles = (int)h->plan.tiles.size();
     // with many tiles, re-summing all partials in every k_build workgroup costs more than one tiny launch per slot
     // The decision of a slot is re-derived by every k_build workgroup from its OWN window's tile partials (read by all 256 threads
     // with every load in flight: the cost does not depend on how many windows the batch has), as long as a window has at most
     // 4 * BUILD_THREADS tiles (the canonical summation order of wave_sum_backsub_partials); a separate k_decide launch per slot
     // only for larger windows (configs 4 / 5) and for the throughput kernels, which read the decided state.
     int max_win_tiles = 0;
-    for (int w = 0; w < n_win; w++) max_win_tiles = std::max(max_win_tiles, h->wins[w].d.tile_end - h->wins[w].d.tile_begin);
+    for (int w = 0; w < n_win; w++) max_win_tiles = std::max(max_win_tiles, h->plan.wins[w].d.tile_end - h->plan.wins[w].d.tile_begin);
     plan.max_win_tiles = max_win_tiles;
     P.decide_kernel = max_win_tiles > 4 * BUILD_THREADS ? 1 : 0;
     // a sharded window keeps the item loop of k_solve: every rank must leave it with the same bits (plain adds, one factor at a time)
     P.imu_direct = (!h->coll_fn && P.world == 1 && !h->env.imu_items) ? 1 : 0;
-    const int mtk = plan.mtk = h->max_tile_kf;
-    const size_t nt = 6 * (size_t)h->max_tile_free;
-    int Rp = 16 * ((6 * h->max_gemm_free + 15) / 16);                          // padded rows of the Y / E strips
+    const int mtk = plan.mtk = h->plan.max_tile_kf;
+    const size_t nt = 6 * (size_t)h->plan.max_tile_free;
+    int Rp = 16 * ((6 * h->plan.max_gemm_free + 15) / 16);                          // padded rows of the Y / E strips
     int strip_doubles = std::max(STAGE_VALS * 64, 2 * Rp * (32 + 2));          // per wave: Y | E strips, later the wave's copy of the tile
     size_t lds_build = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)BUILD_WAVES * strip_doubles + nt * (nt + 1) / 2 + 3 * nt +
                                                                    0) + 16;
-    if (lds_build > 160 * 1024 && h->max_gemm_free > 0) {
+    if (lds_build > 160 * 1024 && h->plan.max_gemm_free > 0) {
         // a window mixing short tracks with very long ones: the MFMA strips + the large atomic tile do not fit
         // together; run every tile on the ds_add_f64 path instead. This is the only write to the layout a solve makes
-        for (auto& t : h->tiles) if (t.lds_mode == 2) t.lds_mode = 1;
-        HIP_TRY(hipMemcpyAsync(h->d_tiles.p, h->tiles.data(), h->tiles.size() * sizeof(Tile), hipMemcpyHostToDevice, h->stream));
-        h->max_gemm_free = 0;
+        for (auto& t : h->plan.tiles) if (t.lds_mode == 2) t.lds_mode = 1;
+        HIP_TRY(hipMemcpyAsync(h->d_tiles.p, h->plan.tiles.data(), h->plan.tiles.size() * sizeof(Tile), hipMemcpyHostToDevice, h->stream));
+        h->plan.max_gemm_free = 0;
         Rp = 0; strip_doubles = STAGE_VALS * 64;
         lds_build = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)BUILD_WAVES * strip_doubles + nt * (nt + 1) / 2 + 3 * nt +
                                                                0) + 16;
     }
-    if (h->env.debug) fprintf(stderr, "[sadvio dbg] lds_build %zu B, Rp %d, strip_doubles %d, max_tile_kf %d, max_tile_free %d, tiles %d\n", lds_build, Rp, strip_doubles, mtk, h->max_tile_free, n_tiles);
+    if (h->env.debug) fprintf(stderr, "[sadvio dbg] lds_build %zu B, Rp %d, strip_doubles %d, max_tile_kf %d, max_tile_free %d, tiles %d\n", lds_build, Rp, strip_doubles, mtk, h->plan.max_tile_free, n_tiles);
     plan.Rp = Rp; plan.strip_doubles = strip_doubles; plan.lds_build = lds_build;
     plan.lds_back = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)mtk * 18) + 16;
     // k_solve<0>: tile-packed image + y / gf / hd / xs + the chol16 exchange areas
-    const size_t npq = (size_t)h->max_np;
+    const size_t npq = (size_t)h->plan.max_np;
     plan.lds_solve = sizeof(double) * ((size_t)c16_size((int)npq) + 4 * npq + 1 + C16_WORK + 16 * (size_t)c16_blocks((int)npq + 1) + SOLVE_KFC * SOLVE_KFC_STRIDE) + 64;
     // robust loss or prior-kept landmarks in the batch: the kernels carrying those (rare) paths
     bool any_pseudo = false;
-    for (const auto& v : h->sp_elim) for (char e : v) any_pseudo |= e != 0;
+    for (const auto& v : h->plan.sp_elim) for (char e : v) any_pseudo |= e != 0;
     // (kept landmarks: by their reduced columns, not by their observations — on a sharded window the ranks other than 0 hold them without any)
     bool any_kept_lmk = false;
-    for (int w = 0; w < n_win; w++) any_kept_lmk |= h->wins[w].d.n_red > 0;
-    const bool rare = plan.rare = o.huber_a > 0.0 || h->n_kept > 0 || any_kept_lmk || any_pseudo || h->gemm_run4;
-    const bool pix = plan.pix = h->factor_type == SADVIO_FACTOR_PIXEL;
+    for (int w = 0; w < n_win; w++) any_kept_lmk |= h->plan.wins[w].d.n_red > 0;
+    const bool rare = plan.rare = o.huber_a > 0.0 || h->plan.n_kept > 0 || any_kept_lmk || any_pseudo || h->plan.gemm_run4;
+    const bool pix = plan.pix = h->plan.factor_type == SADVIO_FACTOR_PIXEL;
     // IMU factor pairs and listed sparse-prior factors ride k_build (linearisation) and k_backsub (candidate cost) as extra workgroups
     // when the submission is a window or two: the inlined linearisation leaves those variants of k_build one workgroup per CU, which
     // a batch of VIO windows would pay for; there the evaluation runs as kernels of its own on the same stream (k_pf_eval)
@@ -340,17 +340,17 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     plan.k_backsub = backsub_variant(pix, rare, with_imu);
     plan.k_build_kept = pix ? k_build_kept<0> : k_build_kept<1>;
     // large plain batches: the throughput kernels of lm_kernels.h (SADVIO_LM=1 / 0 forces / forbids them, for tests and A/B runs)
-    bool use_lm = h->lm_ok && !rare && !h->coll_fn && h->world == 1 && h->lm_landmarks >= 65536;
-    if (h->env.lm >= 0) use_lm = h->lm_ok && !rare && !h->coll_fn && h->world == 1 && h->env.lm != 0;
+    bool use_lm = h->plan.lm_ok && !rare && !h->coll_fn && h->world == 1 && h->plan.lm_landmarks >= 65536;
+    if (h->env.lm >= 0) use_lm = h->plan.lm_ok && !rare && !h->coll_fn && h->world == 1 && h->env.lm != 0;
     plan.use_lm = use_lm;
     plan.k_build_obs = pix ? k_build_obs<0> : k_build_obs<1>;
     plan.k_lm_pass = pix ? k_lm_pass<0, false> : k_lm_pass<1, false>;
     plan.k_lm_pass0 = pix ? k_lm_pass<0, true> : k_lm_pass<1, true>;
-    plan.lm_n_sub = h->lm_n_sub; plan.lm_sub_obs = h->lm_sub_obs;
-    const size_t lds_views = pix ? sizeof(double) * (size_t)mtk * h->lm_max_cam * LM_VT : 0;   // view tables of the pixel factor
+    plan.lm_n_sub = h->plan.lm_n_sub; plan.lm_sub_obs = h->plan.lm_sub_obs;
+    const size_t lds_views = pix ? sizeof(double) * (size_t)mtk * h->plan.lm_max_cam * LM_VT : 0;   // view tables of the pixel factor
     plan.lds_bobs = tile_tables_bytes(mtk) + sizeof(double) * ((size_t)BUILD_WAVES * Rp * LM_KS + nt * (nt + 1) / 2 + nt + 1 + LM_DT) + lds_views + 16;
     // k_lm_pass: tables at x (+ at the candidate, + the pose steps), the tile's key-frame sums, the staged observation constants
-    plan.lds_pass0 = tile_tables_bytes(mtk) + sizeof(double) * LM_DT_COST + (size_t)h->lm_sub_obs * ((pix ? 2 : 3) * sizeof(double) + sizeof(int)) + lds_views + 16;
+    plan.lds_pass0 = tile_tables_bytes(mtk) + sizeof(double) * LM_DT_COST + (size_t)h->plan.lm_sub_obs * ((pix ? 2 : 3) * sizeof(double) + sizeof(int)) + lds_views + 16;
     plan.lds_pass = plan.lds_pass0 + sizeof(double) * (size_t)mtk * (POSE_TAB + 6) + lds_views;
     if (!use_lm) P.lm_sacc = nullptr;   // k_decide sums the tiles' k_backsub partials
     if (use_lm) {
@@ -363,7 +363,7 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     HIP_TRY(hipFuncSetAttribute((const void*)plan.k_backsub, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_back));
     bool extras = false;  // any pose-only factor family beyond PosePriordx in the batch?
     for (int w = 0; w < n_win; w++) {
-        const WinDev& d = h->wins[w].d;
+        const WinDev& d = h->plan.wins[w].d;
         if (d.imu_end > d.imu_begin || d.sp_end > d.sp_begin || d.dp_n_full > 0 || d.dpf == 15 || d.lobs_end > d.lobs_begin || d.line_end > d.line_begin) extras = true;   // dpf 15: padded pivots live in the EXTRAS kernel
     }
     plan.extras = extras;
@@ -371,10 +371,10 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     plan.k_solve_front = extras ? k_solve<1, true> : k_solve<1, false>;
     plan.k_solve_back = extras ? k_solve<2, true> : k_solve<2, false>;
     HIP_TRY(hipFuncSetAttribute((const void*)plan.k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_solve));
-    plan.n_kf_tot = h->n_kf_tot; plan.n_big = h->n_big;
+    plan.n_kf_tot = h->plan.n_kf_tot; plan.n_big = h->plan.n_big;
     plan.reset_blocks = (int)std::min<long long>(1024, std::max<long long>(1, (P.n_xl + P.n_xp + 255) / 256));
     // (extra blocks of k_reset) the pose tables / prior records at x = 0
-    plan.table_blocks = (std::max(h->n_kf_tot, (int)h->priors.size()) + 63) / 64;
+    plan.table_blocks = (std::max(h->plan.n_kf_tot, (int)h->priors.size()) + 63) / 64;
     // IMU factor pairs and the listed sparse-prior factors ride the tile kernels as extra workgroups (kernels.h: pose_factor_eval).
     // Line observations are still evaluated on a side stream: the linearisation next to k_build, the candidate cost next to
     // k_backsub (fork / join with events; parallel branches of the captured graph)
@@ -386,24 +386,24 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     big.clear(); big.resize(n_win);
     if (n_win) memset(big.data(), 0, sizeof(BigPlan) * (size_t)n_win);
     for (int w = 0; w < n_win; w++) {
-        const WinDev& d = h->wins[w].d;
+        const WinDev& d = h->plan.wins[w].d;
         if (!d.ld) continue;
         BigPlan& p = big[w];
         p.Np = d.Np; p.ld = d.ld; p.dpf = d.dpf; p.red_off = d.red_off; p.S_off = d.S_off;
-        int hb = h->wins[w].hb_lmk;
+        int hb = h->plan.wins[w].hb_lmk;
         for (const ImuDev& f : h->imus_per_win[w]) {
-            const int fi = h->h_kf_fidx[f.kf_i], fj = h->h_kf_fidx[f.kf_j];
+            const int fi = h->plan.kf_fidx[f.kf_i], fj = h->plan.kf_fidx[f.kf_j];
             if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
         }
         if (w < (int)h->sparse_per_win.size())
             for (const sadvio_sparse_prior& sp : h->sparse_per_win[w])
                 if (sp.type == SADVIO_SPARSE_RELATIVE_POSE) {     // a relative-pose factor couples its two key-frames
-                    const int fi = h->h_kf_fidx[d.kf_base + sp.kf], fj = h->h_kf_fidx[d.kf_base + sp.kf_b];
+                    const int fi = h->plan.kf_fidx[d.kf_base + sp.kf], fj = h->plan.kf_fidx[d.kf_base + sp.kf_b];
                     if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
                 }
         p.bw = (d.n_red > 0 || d.dp_n_full > 0 || d.line_end > d.line_begin) ? d.Np : std::min(d.Np, (hb + 1) * d.dpf);
     }
-    if (h->coll_fn && h->world > 1 && h->n_big) {
+    if (h->coll_fn && h->world > 1 && h->plan.n_big) {
         // every rank must factor the all-reduced S with the same (largest) bandwidth: gather the local ones
         std::vector<double> slots((size_t)n_win * h->world * 4, 0.0);
         for (int w = 0; w < n_win; w++) slots[((size_t)w * h->world + h->rank) * 4] = (double)big[w].bw;
@@ -438,15 +438,15 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     }
     if (h->coll_fn) {
         // the window spans devices: what the per-slot all-reduce of the reduced system sends
-        plan.coll_buf = h->d_S.p; plan.coll_count = h->red_total;
+        plan.coll_buf = h->d_S.p; plan.coll_count = h->plan.red_total;
         if (n_win == 1 && big[0].ld && big[0].bw < big[0].Np && big[0].S_off == 0) {
             // one banded window spanning the devices: only the band of S travels (dense_chol.h: k_band_pack)
-            const long long nbd = (long long)big[0].Np * big[0].bw, tail = h->red_total - (long long)big[0].Np * big[0].ld;
+            const long long nbd = (long long)big[0].Np * big[0].bw, tail = h->plan.red_total - (long long)big[0].Np * big[0].ld;
             HIP_TRY(h->d_coll_band.alloc((size_t)(nbd + tail)));
             plan.coll_band = true; plan.coll_buf = h->d_coll_band.p; plan.coll_count = nbd + tail;
         }
     }
-    for (int w = 0; w < n_win; w++) { plan.dp_max_nf = std::max(plan.dp_max_nf, h->wins[w].d.dp_n_full); plan.dp_max_n = std::max(plan.dp_max_n, h->wins[w].d.dp_n); }
+    for (int w = 0; w < n_win; w++) { plan.dp_max_nf = std::max(plan.dp_max_nf, h->plan.wins[w].d.dp_n_full); plan.dp_max_n = std::max(plan.dp_max_n, h->plan.wins[w].d.dp_n); }
     return SADVIO_OK;
 }
 

@@ -1,6 +1,10 @@
 #!/usr/bin/env python
-"""Host-time breakdown of sadvio_ba_set_windows (SADVIO_DEBUG=8192 laps of build_layout) on the config-2 window and the config-3 shaped
-VIO window: python scripts/set_windows_laps.py"""
+"""Host-time breakdown of sadvio_ba_set_windows (SADVIO_DEBUG=8192 laps of layout_build and of the planning steps it calls, layout_driver.h / layout_plan.h; with that switch every flush also hashes its payload, so read the laps, not the medians) on the config-2 window and the config-3 shaped
+VIO window: python scripts/set_windows_laps.py
+Against lap tables from before the planner / driver split: "layout_reduced" is now the host planning of the reduced systems alone and is
+printed before "alloc+queue"; their allocations, memsets, the dense priors' flush and the prepare launches are the new lap "reduced
+device" (they were part of "layout_reduced"); "chunks" (chunk tables and work lists of the throughput kernels) was part of "alloc+queue";
+"  half-bandwidth", which timed nothing, is gone."""
 import os, sys, time
 os.environ["SADVIO_DEBUG"] = "8192"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
