@@ -19,9 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 def one(window):
     import step_helpers as sh
     from oracle import oracle
-    from sadvio_amd import capi
     case = next(c for c in sh.CASES if c.window == window)
-    ref = sh.mp_first_step(sh.case_window(case), capi.gn_options(1), oracle_lib=oracle)
+    ref = sh.mp_first_step(sh.case_window(case), sh.case_options(case), oracle_lib=oracle)
     return window, ref
 
 

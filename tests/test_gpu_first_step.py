@@ -1,4 +1,4 @@
-"""The first LM step of every reduced-solve route against the 50-digit step (tests/step_helpers.py).
+"""The first LM step of every reduced-solve route and of every tile-kernel variant against the 50-digit step (tests/step_helpers.py).
 
 One solve of ONE iteration per case: k_solve<0, false> (VO, N_p = 6 .. 174 at every size where chol16.h's c16_solve branches),
 k_solve<0, true> (VIO and kept landmarks), and the five out-of-LDS routes of solve_driver.h at their boundary sizes. The step must lie
@@ -6,6 +6,14 @@ within TOL_FACTOR x max(E_REF, FLOOR) of the 50-digit one, where E_REF is the fl
 (tests/test_step_reference_cpu.py keeps that table honest and proves that this bar sees a single unrefined reciprocal square root, a
 dropped rank-4 product and a missing damping term); the trace row of the step must carry the 50-digit model cost change and cost to
 1e-11. The whole-solve tests hold the same code to 1e-6 only.
+
+The tile kernels carry most of the arithmetic of a step, and the cases above reach k_solve through one tile path only (packed
+single-round MFMA tiles of k_build, then k_backsub). step_helpers.TILE_CASES hold their other variants to the same bar on small
+windows: the contiguous cut, no first-round packets, two and three landmark rounds per tile, constant key-frames and landmarks,
+k_build<RARE> / k_backsub<RARE> under Huber, 16 / 32 / 64 lanes per landmark and a 6-free-key-frame tile (lds_mode 1), the IMU pairs
+outside the tile workgroups, and the throughput kernels k_lm_pass0 / k_build_obs / k_lm_pass (SADVIO_LM=1) at every chunk cut, at one
+and five free key-frames, with two sub-blocks per tile and at window index 2 of a batch. Each of them asserts from kernel_times()
+which kernels ran; tests/test_tile_plan_cpu.py asserts on the host that the planner gave each window the tiles it is meant to have.
 
 Every case prints its measured multiples (`FIRST_STEP ...`, run with -s) before it asserts; DESIGN.md section 2 records them."""
 import numpy as np
@@ -16,28 +24,40 @@ from sadvio_amd import capi
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("SADVIO_BAND_C", "SADVIO_NO_BCR")
+SWITCHES = sh.SWITCHES
 _device = {}      # case name -> deltas of the device's step (the route-against-route test reuses them)
 
 
-def run_case(backend_cls, monkeypatch, case, front=()):
-    """(summary, deltas, trace) of one iteration on the case's window, stored behind the windows `front` of one batch. The
-    switches are set before the handle is created: it reads them once, in create."""
+def run_case(backend_cls, monkeypatch, case, front=None):
+    """(summary, deltas, trace, kernel_times) of one iteration on the case's window, stored behind the windows `front` of one batch
+    (default: the case's decoys). The switches are set before the handle is created: it reads them once, in create. A case that
+    names its kernels runs on a profiling handle, and kernel_times() says which kernels ran."""
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in case.env.items():
         monkeypatch.setenv(k, v)
-    w = sh.case_window(case)
-    i = len(front)
-    be = backend_cls(device=0)
+    ws = sh.case_windows(case) if front is None else list(front) + [sh.case_window(case)]
+    i = len(ws) - 1
+    be = backend_cls(device=0, profile_kernels=bool(case.kernels))
     try:
-        be.set_windows(list(front) + [w])
-        s = be.solve(capi.gn_options(1))[i]
+        be.set_windows(ws)
+        s = be.solve(sh.case_options(case))[i]
         d = be.get_deltas(i)
         tr = be.get_trace(i)
+        kt = be.kernel_times() if case.kernels else {}
     finally:
         be.close()
-    return s, d, tr
+    return s, d, tr, kt
+
+
+def check_kernels(case, kt):
+    """The kernels the case is about are the ones that ran."""
+    n = {k: v["launches"] for k, v in kt.items()}
+    if case.kernels == "throughput":
+        assert (n.get("k_lm_pass0"), n.get("k_build_obs"), n.get("k_lm_pass")) == (1, 1, 1) and "k_build" not in n, n
+    elif case.kernels in ("latency", "pf"):
+        assert n.get("k_build") == 1 and n.get("k_backsub") == 1 and "k_lm_pass" not in n and "k_build_obs" not in n, n
+        assert ("k_pf_lin" in n and "k_pf_cost" in n) == (case.kernels == "pf"), n
 
 
 def check_case(case, oracle_lib, s, d, tr, n_win=1, tag=""):
@@ -67,16 +87,17 @@ def check_case(case, oracle_lib, s, d, tr, n_win=1, tag=""):
 
 @pytest.mark.parametrize("case", sh.CASES, ids=[c.name for c in sh.CASES])
 def test_first_step_against_50_digits(backend_cls, oracle_lib, monkeypatch, case):
-    s, d, tr = run_case(backend_cls, monkeypatch, case)
+    s, d, tr, kt = run_case(backend_cls, monkeypatch, case)
     _device[case.name] = d
-    check_case(case, oracle_lib, s, d, tr)
+    check_kernels(case, kt)
+    check_case(case, oracle_lib, s, d, tr, n_win=len(case.front) + 1)
 
 
 def test_first_step_at_window_index_2_of_a_batch(backend_cls, oracle_lib, monkeypatch):
     """k_solve runs one workgroup per window: the N_p = 114 window behind two decoys, at the same bar."""
     import batch_helpers as bh
     case = sh.CASE[sh.BATCH_CASE]
-    s, d, tr = run_case(backend_cls, monkeypatch, case, front=(bh.decoy(sh.PIXEL, "a"), bh.decoy(sh.PIXEL, "b")))
+    s, d, tr, _ = run_case(backend_cls, monkeypatch, case, front=(bh.decoy(sh.PIXEL, "a"), bh.decoy(sh.PIXEL, "b")))
     check_case(case, oracle_lib, s, d, tr, n_win=3, tag="@2")
 
 

@@ -4,6 +4,12 @@
   - a float64 host model of the blocked in-LDS Cholesky solve with a planted defect lands ABOVE the bar of the GPU test in every
     in-LDS case: the bar is tight enough to see an unrefined reciprocal-square-root seed on one pivot, a dropped rank-4 product on one
     tile and a column whose damping is missing; the same model without a defect passes the bar;
+  - a float64 host model of the TILE kernels (the un-reduced system summed observation by observation from the twin's Jacobian
+    rows) stays within both bars on every window of the tile-kernel cases, and lands above the bar with one observation scaled by
+    1 + 2^-24, one landmark pivot's unrefined reciprocal square root, one Jp dp term missing from a back-substitution or one
+    landmark's E M^-1 g_l missing from the reduced gradient;
+  - the E_REF2 table (the second step, tests/test_gpu_second_step.py) brackets the oracle's measured error against the twin's 50-digit
+    LM loop, and the oracle accepts both steps;
   - expected_route restates BigPlan::choose at its edges."""
 import numpy as np
 import pytest
@@ -64,7 +70,7 @@ def test_e_ref_table_brackets_the_measured_values(oracle_lib, case):
     of the step agrees with the 50-digit model cost change and cost to the bar it is held to in test_twin.py."""
     w = case_w = sh.case_window(case)
     assert sh.reduced_np(w) == case.np_
-    f64 = sh.oracle_step(oracle_lib, case_w, capi.gn_options(1))
+    f64 = sh.oracle_step(oracle_lib, case_w, sh.case_options(case))
     ref = sh.reference(case, oracle_lib)
     e = sh.step_error(f64, ref, w)
     print(f"E_REF {case.window!r}: ({e[0]:.2e}, {e[1]:.2e}),")
@@ -98,6 +104,52 @@ def test_planted_defects_land_above_the_bar(oracle_lib, case):
         e = sh.step_error(sh.host_model_step(w, H, g, opts, defect=d), ref, w)
         print(f"{case.name}: {name}: pose {e[0] / bar_p:.3g} x bar, landmark {e[1] / bar_l:.3g} x bar")
         if not e[0] > bar_p:
+            missed.append((name, e, (bar_p, bar_l)))
+    assert not missed, missed
+
+
+@pytest.mark.parametrize("window", sh.SECOND_WINDOWS)
+def test_e_ref2_table_brackets_the_measured_values(oracle_lib, window):
+    """E_REF2[window] >= the C oracle's float64 error on the second step and on trace row 2 against the twin's 50-digit LM loop, and
+    not more than 4 x above it; the oracle accepts both steps."""
+    case = sh.window_case(window)
+    w = sh.case_window(case)
+    r1 = oracle_lib.solve(w, sh.case_options(case, 1))
+    r2 = oracle_lib.solve(w, sh.case_options(case, 2))
+    assert (r1["summary"].num_successful_steps, r2["summary"].num_successful_steps) == (1, 2), "the oracle rejects a step"
+    ref = sh.second_reference(window)
+    assert ref["pose"].shape == (w.n_kf, 6) and ref["lmk"].shape == (w.n_lmk, 3) and ref["row"][5] == 1.0
+    e = sh.step_error(sh.second_step(r1, r2), ref, w) + (sh.row_error(r2["log"][2], ref["row"]),)
+    print(f"E_REF2 {window!r}: ({e[0]:.2e}, {e[1]:.2e}, {e[2]:.2e}),")
+    for part, m, t in zip(("pose", "landmark", "trace row 2"), e, sh.E_REF2[window]):
+        assert m <= t <= 4.0 * m, (part, m, t)
+    # the second step is a step of its own size, not the rounding of the first: the metric divides by max |second step|
+    assert np.abs(sh.pose_part(ref, w)).max() > 1e-6 and np.abs(ref["lmk"]).max() > 1e-6
+
+
+TILE_WINDOWS = [c for c in WINDOWS if c in sh.TILE_CASES and not c.route.endswith("extras")]
+DEFECT_WINDOWS = ("w70", "lm_obs8", "g16", "w70_huber")
+
+
+@pytest.mark.parametrize("case", TILE_WINDOWS, ids=[c.window for c in TILE_WINDOWS])
+def test_tile_host_model_and_its_planted_defects(oracle_lib, case):
+    """The clean host model of the tile kernels stays within both bars of the GPU test on every new window; on DEFECT_WINDOWS each
+    planted defect pushes the pose or the landmark part above its bar (a condition: a window that lets one through is replaced,
+    the bar is not moved)."""
+    w = sh.case_window(case)
+    opts = sh.case_options(case)
+    ref = sh.reference(case, oracle_lib)
+    bar_p, bar_l = sh.bars(case)
+    clean = sh.step_error(sh.tile_host_model_step(w, opts), ref, w)
+    print(f"{case.window}: clean host model: pose {clean[0] / bar_p:.3g} x bar, landmark {clean[1] / bar_l:.3g} x bar")
+    assert clean[0] <= bar_p and clean[1] <= bar_l, ("the host model itself", clean, (bar_p, bar_l))
+    if case.window not in DEFECT_WINDOWS:
+        return
+    missed = []
+    for name in sh.TILE_DEFECTS:
+        e = sh.step_error(sh.tile_host_model_step(w, opts, defect=name), ref, w)
+        print(f"{case.window}: {name}: pose {e[0] / bar_p:.3g} x bar, landmark {e[1] / bar_l:.3g} x bar")
+        if not (e[0] > bar_p or e[1] > bar_l):
             missed.append((name, e, (bar_p, bar_l)))
     assert not missed, missed
 
