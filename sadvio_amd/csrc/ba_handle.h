@@ -239,7 +239,7 @@ struct EnvCfg {
     int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
     int cov_batch_lds = 1, cov_batch_scratch_mb = 1024;   // sadvio_ba_covariance_batch: the in-LDS inverse (0: every item down the dense route, A/B) | scratch budget of one group
     double jacobi_tol = 1e-14;
-    bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false;
+    bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {
         auto on = [](const char* k) { return getenv(k) != nullptr; };
         auto num = [](const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; };
@@ -251,6 +251,7 @@ struct EnvCfg {
         no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
         no_bcr = on("SADVIO_NO_BCR");
         contig_tiles = on("SADVIO_CONTIG_TILES");   // A/B: single-round tiles as runs of consecutive landmarks (no packing, tile_pack.h)
+        c16_old_tail = on("SADVIO_C16_OLD_TAIL");   // A/B: k_solve's in-LDS solve with both barriers of its last block column (chol16.h)
         imu_items = on("SADVIO_IMU_ITEMS");   // A/B: the IMU pairs' entries through k_solve's item loop (the pre-0.5 path) on one device too
     }
 };

@@ -14,14 +14,23 @@
 //                        (v_readlane), its Cholesky factor is computed uniformly (v_rsq_f64 + 2 Newton steps per column:
 //                        65 cycles, the dependency floor), every lane gets the 4 entries of its row with three
 //                        v_permlane{16,32}_swap pairs and forward-substitutes them (y = a L_ss^-T), D -= y y^T is ONE MFMA.
-//                        The step's y (= 4 columns of L_kk) and the 10 numbers of the 4 x 4 factor are published in LDS.
-//   all waves            "replay" the same 4 steps on the panel tiles below (A_Ik -> L_Ik = A_Ik L_kk^-T, one MFMA per step)
-//                        and on an identity tile (-> L_kk^-T, kept in the dead diagonal tile for the back-substitution);
-//   bulk waves           trailing update C_IJ -= L_Ik L_Jk^T, 4 MFMAs per tile, while the pivot wave updates and factors
-//                        the next diagonal tile (look-ahead).
-// Two workgroup barriers per block column (8 for N = 114 instead of 38 with 6-column blocks). The right-hand side is row N
-// of the matrix (forward substitution for free); columns >= N of the last tile are dummy pivots (inverse 0: no effect).
-// Back-substitution: thread c owns y_c; per block, x_J = L_JJ^-T v_J by 16 lanes, y_c -= L_Jc^T x_J by everyone.
+//                        The step's y (= 4 columns of L_kk) is published in LDS (the back-substitution reads the rhs row's).
+//                        The same steps run on an identity tile: after the block W = L_kk^-T, which goes into the dead
+//                        diagonal tile (X layout) and, transposed and padded, into `wt`.
+//   phase A, all waves   panel tiles below the block: L_Ik = A_Ik L_kk^-T, four MFMAs per tile with `wt` as the operand. The
+//                        pivot wave takes tile (k + 1, k) and updates the next diagonal tile with it.
+//   phase B              the pivot wave factors the next diagonal tile (look-ahead) while the bulk waves run the trailing
+//                        update C_IJ -= L_Ik L_Jk^T, 4 MFMAs per tile, and turn the panel of the PREVIOUS block column, dead
+//                        as L by then, into H_IJ = L_IJ L_JJ^-1 (stored transposed). In the phase B of the last block column
+//                        but one, the wave that ran the only trailing tile left converts that column's panel as well, after
+//                        its own reads of it: the last block column then has nothing but the panel of the right-hand side's
+//                        tile row (N a multiple of 16; the pivot wave's, which also converts it) and runs without a barrier.
+// Two workgroup barriers per block column but the last. The right-hand side is row N of the matrix (forward substitution for
+// free); columns >= N of the last tile are dummy pivots (inverse 0: no effect).
+// Back-substitution on the H tiles: x_J = z_J - sum_{I > J} H_IJ^T x_I with z = the right-hand-side row of H, no triangular
+// solve per block. Thread c owns z_c; per block I from the last one down: its 16 owners put x_I into LDS, one workgroup barrier,
+// every thread c < 16 I subtracts H_I,J(c)^T x_I. (A chain through the four blocks of a wave without the barrier, barriers
+// between waves only, gives the same bits and was measured 0.55 us SLOWER at N = 114: docs/KERNEL_HISTORY.md "The tail of chol16".)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -304,8 +313,12 @@ __device__ __forceinline__ void c16_to_h(double* A, int I, int J, int ln) {
 // doubles. Returns false if the solution is not finite (a non-positive pivot). ts (may be null): phase timestamps.
 // SOLVE = false stops after the factorisation: the panel tiles hold L_IJ, the diagonal tiles L_JJ^-T, the tiles of row N the
 // forward-substituted right-hand side (L^-1 rhs)^T in their first rows — what the wide-panel dense solver takes (dense_chol.h).
+// old_tail (uniform; SADVIO_C16_OLD_TAIL, A/B): the last block column keeps both of its barriers and converts the panel of the
+// column before it, as every other block column does. Same bits either way. ts[1 + 2 kb], ts[2 + 2 kb]: end of the phases of
+// block column kb < 8 (a skipped phase repeats the stamp before it), ts[18] .. ts[19]: the back-substitution from the barrier in
+// front of it to its last step, ts[20]: the end.
 template <int GATHER = 1, bool SOLVE = true>
-__device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* pub, double* yv, long long* ts, long long* dbg = nullptr) {
+__device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* pub, double* yv, long long* ts, long long* dbg = nullptr, bool old_tail = false) {
     const int tid = threadIdx.x, ln = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = blockDim.x >> 6;
     const int nb = c16_blocks(N + 1);     // tile rows incl. the right-hand-side row
@@ -319,7 +332,8 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
     c16_d4 D = {0.0, 0.0, 0.0, 0.0};      // pivot wave: the next diagonal tile
     if (wv == 0) c16_publish_w(A, wt, ln, c16_pivot_block<GATHER>(c16_load(A, ln), N < 16 ? N : 16, pub, gbuf, ln, lc));
     __syncthreads();
-    if (ts && tid == 0) ts[0] = clock64();
+    long long tlast = 0;                  // the last stamp written (repeated for a skipped phase)
+    if (ts && tid == 0) ts[0] = tlast = clock64();
     for (int kb = 0; kb < nbc; kb++) {
         const int m = nb - kb - 1;        // tile rows below the diagonal tile
         // ---- phase A: L_Ik = A_Ik L_kk^-T, one product per panel tile. The pivot wave takes the tile it needs next,
@@ -345,8 +359,15 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
                 c16_store(tp, ln, c16_panel(c16_load(tp, ln), wt, ln));
             }
         }
+        if (!old_tail && kb == nbc - 1) {
+            // the last block column: its panel is at most the right-hand side's tile (m = 1), the pivot wave's above, which no
+            // other wave touches before the barrier in front of the back-substitution; phase B has nothing (the panel of block
+            // column kb - 1 became H one phase early, below)
+            if (ts && tid == 0 && kb < 8) { ts[1 + 2 * kb] = tlast; ts[2 + 2 * kb] = tlast; }
+            break;
+        }
         __syncthreads();
-        if (ts && tid == 0 && kb < 8) ts[1 + 2 * kb] = clock64();
+        if (ts && tid == 0 && kb < 8) ts[1 + 2 * kb] = tlast = clock64();
         // ---- phase B: factorisation of the next diagonal tile (look-ahead) | trailing update of everything else, and the
         //      panel of the PREVIOUS block column (no longer needed as L) turned into H = L L_JJ^-1 ----
         if (wv == 0) {
@@ -383,18 +404,26 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
                 }
                 if (SOLVE && kb >= 1)
                     for (int Ic = kb + (nbw - 1 - bw); Ic < nb; Ic += nbw) c16_to_h(A, Ic, kb - 1, ln);   // last waves first: they got fewer tiles above
+                // The last block column but one: the only trailing tile left to the bulk waves is (nbc, nbc - 1), the first
+                // bulk wave's (none when the right-hand side shares the last diagonal tile), and the pivot wave read (kb + 1, kb)
+                // in phase A. That wave turns THIS column's panel into H after its own reads of it (c16_to_h reads and writes
+                // the addresses the same lane read as LI / LJ): nothing is left for the last block column's phase B
+                if (SOLVE && !old_tail && kb == nbc - 2 && bw == 0)
+                    for (int Ic = kb + 1; Ic < nb; Ic++) c16_to_h(A, Ic, kb, ln);
             }
         }
         __syncthreads();
-        if (ts && tid == 0 && kb < 8) ts[2 + 2 * kb] = clock64();
+        if (ts && tid == 0 && kb < 8) ts[2 + 2 * kb] = tlast = clock64();
     }
     if (!SOLVE) { __syncthreads(); return true; }
-    // the last block column's panel (at most the tile row of the right-hand side when N is a multiple of 16)
-    for (int Ic = nbc + wv; Ic < nb; Ic += nwv) c16_to_h(A, Ic, nbc - 1, ln);
+    // the last block column's panel (at most the tile row of the right-hand side when N is a multiple of 16): the pivot wave's,
+    // as its phase A was
+    if (wv == 0 && nbc < nb) c16_to_h(A, nbc, nbc - 1, ln);
     // ---- back-substitution. z_c = H[N][c] = (L_JJ^-T y_J)[c]; x_I = z_I once the blocks above are in; then every thread
-    //      c < 16 I subtracts H_I,J(c)^T x_I (16 consecutive doubles of tile (I, c / 16)). One barrier per block. ----
+    //      c < 16 I subtracts H_I,J(c)^T x_I (16 consecutive doubles of tile (I, c / 16)): I descending, i ascending ----
     const int IB = N >> 4, r = N & 15;
     __syncthreads();
+    if (ts && tid == 0) ts[18] = clock64();
     double z = 0.0;
     if (tid < N) {
         const int J = tid >> 4, cl = tid & 15;
@@ -425,11 +454,17 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
         if (I == 0) break;
         __syncthreads();
         if (tid < 16 * I) {
-            const double* xi = yv + 16 * I;
+            // all of x_I on the way before the first FMA: left to itself the compiler loads it four values at a time between
+            // the FMAs that use them and exposes the LDS latency five times per block instead of once
+            double xv[16];
 #pragma unroll
-            for (int i = 0; i < 16; i++) z = __builtin_fma(-hcol[i], xi[i], z);
+            for (int i = 0; i < 16; i++) xv[i] = yv[16 * I + i];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < 16; i++) z = __builtin_fma(-hcol[i], xv[i], z);
         }
     }
+    if (ts && tid == 0) ts[19] = clock64();
     if (bad) s_bad = 1;
     __syncthreads();
     if (ts && tid == 0) ts[20] = clock64();

@@ -297,6 +297,7 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     for (int w = 0; w < n_win; w++) max_win_tiles = std::max(max_win_tiles, h->plan.wins[w].d.tile_end - h->plan.wins[w].d.tile_begin);
     plan.max_win_tiles = max_win_tiles;
     P.decide_kernel = max_win_tiles > 4 * BUILD_THREADS ? 1 : 0;
+    P.c16_old_tail = h->env.c16_old_tail ? 1 : 0;
     // a sharded window keeps the item loop of k_solve: every rank must leave it with the same bits (plain adds, one factor at a time)
     P.imu_direct = (!h->coll_fn && P.world == 1 && !h->env.imu_items) ? 1 : 0;
     const int mtk = plan.mtk = h->plan.max_tile_kf;
@@ -563,7 +564,7 @@ void print_debug_stamps(sadvio_ba_handle* h, int n_tiles) {
                 (ts[114] - ts[106]) * 0.01, (ts[115] - ts[114]) * 0.01, (ts[116] - ts[114]) * 0.01, (ts[117] - ts[114]) * 0.01, (ts[120] - ts[106]) * 0.01, (ts[121] - ts[120]) * 0.01);
         fprintf(stderr, "\n[sadvio dbg] chol16 cycles since its first barrier (panel | trailing + next pivot, per block column):");
         for (int i = 65; i < 81; i++) fprintf(stderr, " %lld", ts[i] - ts[64]);
-        fprintf(stderr, " | end %lld", ts[84] - ts[64]);
+        fprintf(stderr, " | back-substitution %lld .. %lld | end %lld", ts[82] - ts[64], ts[83] - ts[64], ts[84] - ts[64]);
         fprintf(stderr, "\n[sadvio dbg] k_chol_panel / k_band_solve (fwd window 2: carry fresh chol store | fwd end | bwd window 2: load below steps | bwd end):");
         for (int i = 45; i < 55; i++) fprintf(stderr, " %d:%.2f", i - 44, (ts[i] - ts[44]) * 0.01);
         fprintf(stderr, "\n");

@@ -1,6 +1,7 @@
 // chol16_probe.hip — standalone check + timing of the in-LDS tile Cholesky solve (sadvio_amd/csrc/chol16.h), the same
 // code k_solve<0> runs: random SPD systems of every size class against a host double-precision Cholesky, phase
-// timestamps, hipEvent time per launch.
+// timestamps, hipEvent time per launch. Every size runs the product (variant 1), the product with old_tail (variant 2: the
+// last block column with both of its barriers) and GATHER = 0 (variant 3).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o scripts/probe/_build/chol16_probe scripts/probe/chol16_probe.hip
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -13,7 +14,7 @@
 using namespace sadvio;
 
 template <int GATHER>
-__global__ __launch_bounds__(512) void k_probe(const double* img, int N, double* xout, long long* ts, int* ok, int reps) {
+__global__ __launch_bounds__(512) void k_probe(const double* img, int N, double* xout, long long* ts, int* ok, int reps, int old_tail) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nb = c16_blocks(N + 1);
     const int sz = c16_size(N);
@@ -28,7 +29,7 @@ __global__ __launch_bounds__(512) void k_probe(const double* img, int N, double*
         c16_symmetrize(A, nb);
         __syncthreads();
         if (threadIdx.x == 0 && rep == reps - 1) ts[30] = clock64();
-        good = c16_solve<GATHER>(A, N, xs, pub, yv, rep == reps - 1 ? ts : nullptr, (rep == reps - 1 && reps == 2) ? ts + 32 : nullptr) && good;
+        good = c16_solve<GATHER>(A, N, xs, pub, yv, rep == reps - 1 ? ts : nullptr, (rep == reps - 1 && reps == 2) ? ts + 32 : nullptr, old_tail != 0) && good;
         __syncthreads();
         if (threadIdx.x == 0 && rep == reps - 1) ts[31] = clock64();
     }
@@ -82,10 +83,11 @@ int main() {
         CK(hipMemcpy(dimg, img.data(), sz * 8, hipMemcpyHostToDevice));
         CK(hipMemset(dts, 0, 128 * 8));
         const size_t lds = (size_t)(sz + C16_WORK + 16 * nb + 16 * nb + 16) * 8;
-      for (int var = 0; var < 2; var++) {
-        auto kern = var ? k_probe<0> : k_probe<1>;   // 1: the product (pivot entries gathered through LDS), 2: GATHER = 0 (v_readlane + v_permlane swaps)
+      for (int var = 0; var < 3; var++) {
+        auto kern = var == 2 ? k_probe<0> : k_probe<1>;   // 1: the product (pivot entries gathered through LDS), 2: the same with old_tail, 3: GATHER = 0 (v_readlane + v_permlane swaps)
+        const int old_tail = var == 1;
         CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds, 0, dimg, N, dx, dts, dok, 3);
+        hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds, 0, dimg, N, dx, dts, dok, 3, old_tail);
         CK(hipDeviceSynchronize());
         std::vector<double> xg(N); long long ts[128]; int ok = 0;
         CK(hipMemcpy(xg.data(), dx, N * 8, hipMemcpyDeviceToHost));
@@ -97,13 +99,14 @@ int main() {
         double res = 0;
         for (int i = 0; i < N; i++) { double t = -b[i]; for (int j = 0; j < N; j++) t += S[(size_t)i * N + j] * xg[j]; res = fmax(res, fabs(t)); }
         long long ts2[128];
-        if (N == 114 || N == 165 || N == 120 || N == 174) {   // second launch with the in-step stamps (they cost ~55 cycles each: not in the timed run)
-            hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds, 0, dimg, N, dx, dts, dok, 2);
+        const bool stamps = N == 114 || N == 165 || N == 120 || N == 174 || N == 112 || N == 113 || N == 128;
+        if (stamps) {   // second launch with the in-step stamps (they cost ~55 cycles each: not in the timed run)
+            hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds, 0, dimg, N, dx, dts, dok, 2, old_tail);
             CK(hipDeviceSynchronize());
             CK(hipMemcpy(ts2, dts, 128 * 8, hipMemcpyDeviceToHost));
         }
         printf("N=%3d variant=%d ok=%d max|x - x_host| %.2e (|x| %.2e) residual %.2e  solve %lld cyc = %.2f us", N, var + 1, ok, err, mx, res, ts[31] - ts[30], (ts[31] - ts[30]) / 2400.0);
-        if (N == 114 || N == 165 || N == 120 || N == 174) {
+        if (stamps) {
             printf("\n      block phases (cycles: replay | look-ahead+trailing):");
             const int nbc = c16_blocks(N);
             for (int kb = 0; kb < nbc && kb < 8; kb++) printf(" %lld|%lld", ts[1 + 2 * kb] - (kb ? ts[2 * kb] : ts[0]), ts[2 + 2 * kb] - ts[1 + 2 * kb]);
@@ -112,13 +115,16 @@ int main() {
                 for (int st = 0; st < 4; st++) { printf(" |"); for (int q = 1; q <= 6; q++) printf(" %lld", ts2[32 + 8 * st + q] - ts2[32 + 8 * st + q - 1]); }
             }
             printf("\n     ");
-            printf("  first block %lld, back-substitution %lld", ts[0] - ts[30], ts[20] - ts[2 * (nbc < 8 ? nbc : 8)]);
+            // since c16_solve's first barrier, as SADVIO_DEBUG=4096 prints them: the end of block column min(nbc, 8)'s phases | the
+            // barrier in front of the back-substitution | its last step | the end (the tail is everything after the last pivot)
+            printf("  first block %lld, stamps: last column %lld | back-substitution %lld .. %lld | end %lld (loop %lld)", ts[0] - ts[30],
+                   ts[2 * (nbc < 8 ? nbc : 8)] - ts[0], ts[18] - ts[0], ts[19] - ts[0], ts[20] - ts[0], ts[19] - ts[18]);
         }
         printf("\n");
         if (N == 114) {   // launch-to-launch time incl. the LDS fill, 200 launches
             hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
             CK(hipEventRecord(e0));
-            for (int i = 0; i < 200; i++) hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds, 0, dimg, N, dx, dts, dok, 1);
+            for (int i = 0; i < 200; i++) hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds, 0, dimg, N, dx, dts, dok, 1, old_tail);
             CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
             float ms = 0; CK(hipEventElapsedTime(&ms, e0, e1));
             printf("      N=114: %.2f us per launch (fill + symmetrize + solve + write-back, 200 back-to-back launches)\n", 1e3 * ms / 200);
