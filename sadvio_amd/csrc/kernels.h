@@ -422,10 +422,11 @@ __device__ __forceinline__ void lane_linearize(const DevPtrs& P, const double* p
 
 // Per-landmark elimination, every lane of the group redundantly: H_ll, g_l (group sums), LM damping, the inverse Cholesky
 // factor Li of the damped block (sym3_chol_inverse: packed lower 6-vector; named Mi below). Returns whether the landmark has a
-// parameter block in the program.
+// parameter block in the program. s_pre: the landmark's three Jacobi scales (DevPtrs::s_lmk) where the caller fetched them with
+// the round's other inputs (k_build), or null: they are loaded here, behind the group sums. Unused with write_scale.
 __device__ __forceinline__ bool group_eliminate(const DevPtrs& P, const ObsLin& L, int G, int gl, bool lmk_valid,
                                                 bool lfree, int nobs, double radius, bool write_scale, bool leader,
-                                                double* Mi, double* g) {
+                                                double* Mi, double* g, const double* s_pre) {
     double H[6];
     H[0] = L.Jl[0] * L.Jl[0] + L.Jl[3] * L.Jl[3];
     H[1] = L.Jl[0] * L.Jl[1] + L.Jl[3] * L.Jl[4];
@@ -454,6 +455,8 @@ __device__ __forceinline__ bool group_eliminate(const DevPtrs& P, const ObsLin& 
         if (leader) {
             P.s_lmk[3 * (long long)gl] = s[0]; P.s_lmk[3 * (long long)gl + 1] = s[1]; P.s_lmk[3 * (long long)gl + 2] = s[2];
         }
+    } else if (s_pre) {
+        s[0] = s_pre[0]; s[1] = s_pre[1]; s[2] = s_pre[2];
     } else {
         s[0] = P.s_lmk[3 * (long long)gl]; s[1] = P.s_lmk[3 * (long long)gl + 1]; s[2] = P.s_lmk[3 * (long long)gl + 2];
     }
@@ -618,6 +621,12 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         pre_x0[i] = P.xl[3 * (long long)gl_first + i];
         pre_x1[i] = P.xl[P.xl_stride + 3 * (long long)gl_first + i];
     }
+    // the landmark's Jacobi scales of iteration 0 (slot 0 computes and writes them in group_eliminate)
+    double pre_s[3] = {1.0, 1.0, 1.0};
+    if (slot != 0) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) pre_s[i] = P.s_lmk[3 * (long long)gl_first + i];
+    }
     double pre_t0 = 0.0, pre_t1 = 0.0;
     if (P.pre_lane) {
         if (pk.x >= 0) {
@@ -698,6 +707,11 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         // goes the usual way, the landmark rows / columns are added by k_build_kept
         const int lcode = first ? pre_lcode : (P.lmk_const ? P.lmk_const[gl] : 0);
         const bool lfree = lcode == 0;
+        double sc[3] = {pre_s[0], pre_s[1], pre_s[2]};
+        if (!first && slot != 0) {                    // later rounds: with the round's other inputs, not behind the group sums
+#pragma unroll
+            for (int i = 0; i < 3; i++) sc[i] = P.s_lmk[3 * (long long)gl + i];
+        }
         ObsLin L;
         L.valid = q < nobs;
         L.row = -1; L.slot = 0; L.counted = false;
@@ -726,7 +740,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         }
     SADVIO_TS(3, 35);
         double Mi[6], g[3];
-        const bool active = group_eliminate(P, L, G, gl, lmk_valid, lfree, nobs, st.radius, slot == 0, q == 0, Mi, g);
+        const bool active = group_eliminate(P, L, G, gl, lmk_valid, lfree, nobs, st.radius, slot == 0, q == 0, Mi, g, sc);
         if (active && q == 0) gmax_part = fmax(gmax_part, fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2]))));
     SADVIO_TS(3, 36);
         // N = Jl Li^T (2x3: Jl M^-1 Jl^T = N N^T), gamma = Li g_l, reduced residual r~ = r - Jl M^-1 g_l = r - N gamma
@@ -1416,6 +1430,19 @@ __device__ __noinline__ void pose_table_store(const double* T0, double d0, doubl
 #pragma unroll
     for (int i = 0; i < POSE_TAB; i++) dst[i] = tab[i];
 }
+// The same between two places in LDS (k_solve<0>'s parked key-frames): ds_read / ds_write, no flat access. The call ABI waits for
+// every outstanding memory operation of the wave at entry and at return; with nothing but LDS traffic in flight around the call
+// neither wait meets a round trip to HBM. The caller's workgroup copies the tables to DevPtrs::ptab afterwards.
+typedef __attribute__((address_space(3))) double lds_double;
+__device__ __noinline__ void pose_table_lds(const lds_double* T0, double d0, double d1, double d2, double d3, double d4, double d5, lds_double* dst) {
+    double T0r[12], tab[POSE_TAB];
+#pragma unroll
+    for (int i = 0; i < 12; i++) T0r[i] = T0[i];
+    const double d6[6] = {d0, d1, d2, d3, d4, d5};
+    pose_table_entry(T0r, d6, tab);
+#pragma unroll
+    for (int i = 0; i < POSE_TAB; i++) dst[i] = tab[i];
+}
 __device__ __noinline__ double prior_lin_record_call(const double* T0, double d0, double d1, double d2, double d3, double d4, double d5, const PriorDev* pr,
                                                      double* rec) {
     double T0r[12];
@@ -1842,7 +1869,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
     bool bad = false;
     for (int i = tid; i < Np; i += blockDim.x) {
         double d = -xs[i];
-        dl[i] = d;
+        if (MODE != 0) dl[i] = d;               // MODE 0: stored from y behind the closing barrier, see there
         y[i] = d;
         sn += d * d;
         if (!isfinite(d)) bad = true;
@@ -1851,29 +1878,71 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
     __syncthreads();
     SADVIO_TS(3, 5);
     double* xpc = P.xp + (long long)(1 - cur) * P.xp_stride;
-    for (int k = tid; k < W.n_kf; k += blockDim.x) {
+    // MODE 0, the key-frames parked in LDS by the front half (one lane each, all in the first wave): every input is read from LDS
+    // with LDS instructions, the table goes into the tile image (dead once c16_solve has returned) and the candidate's HBM stores
+    // are issued behind the table work and never waited for: from the barrier above to the closing reductions this wave has no
+    // store of its own in flight when it waits for memory. The tables and the step reach HBM from the other waves, behind the
+    // closing barrier. (A window whose image is smaller than its tables - few free key-frames among many - stores them from the call.)
+    const int n_park = MODE == 0 ? min(W.n_kf, SOLVE_KFC) : 0;
+    const bool tab_lds = MODE == 0 && n_park * POSE_TAB <= img_n;
+    if (MODE == 0 && tid < n_park) {
+        const int k = tid, g = W.kf_base + k;
+        const lds_double* kc = (const lds_double*)(kfc + k * SOLVE_KFC_STRIDE);
+        const lds_double* yl = (const lds_double*)y;
+        const int fi = (int)kc[0];
+        const bool dpf15 = W.dpf == 15;
+        double d6[6], vbb[9], dy[15];
+#pragma unroll
+        for (int i = 0; i < 6; i++) d6[i] = kc[1 + i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) dy[i] = fi < 0 ? 0.0 : yl[fi * W.dpf + i];
+        if (dpf15) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) { vbb[i] = kc[19 + i]; dy[6 + i] = fi < 0 ? 0.0 : yl[fi * 15 + 6 + i]; }
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            d6[i] += dy[i];
+            if (fi >= 0) cn = fma(d6[i], d6[i], cn);    // (spelled out: a sum of bare products may be contracted from either end)
+        }
+        // pose table of the candidate buffer (k_backsub reads it now, k_build reads it if the step is accepted)
+        if (tab_lds) pose_table_lds(kc + 7, d6[0], d6[1], d6[2], d6[3], d6[4], d6[5], (lds_double*)A + k * POSE_TAB);
+        else pose_table_store(kfc + k * SOLVE_KFC_STRIDE + 7, d6[0], d6[1], d6[2], d6[3], d6[4], d6[5], P.ptab + (long long)(1 - cur) * P.ptab_stride + (long long)g * POSE_TAB);
+#pragma unroll
+        for (int i = 0; i < 6; i++) xpc[6 * (long long)g + i] = d6[i];
+        if (dpf15) {
+            double* xs3[3] = {P.xv + (long long)(1 - cur) * P.xv_stride, P.xba + (long long)(1 - cur) * P.xv_stride, P.xbg + (long long)(1 - cur) * P.xv_stride};
+#pragma unroll
+            for (int q = 0; q < 3; q++)
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    const double v = vbb[3 * q + i] + dy[6 + 3 * q + i];
+                    xs3[q][3 * (long long)g + i] = v;
+                    if (fi >= 0) cn = fma(v, v, cn);
+                }
+        }
+    }
+    // the key-frames behind them, and every key-frame of an out-of-LDS window: inputs from HBM
+    for (int k = (MODE == 0 ? SOLVE_KFC : 0) + tid; k < W.n_kf; k += blockDim.x) {
         int g = W.kf_base + k;
-        const bool pre = MODE == 0 && k < SOLVE_KFC;  // parked in LDS by the front half
-        const double* kc = kfc + (pre ? k : 0) * SOLVE_KFC_STRIDE;
-        int fi = pre ? (int)kc[0] : P.kf_fidx[g];
+        int fi = P.kf_fidx[g];
         double d6[6];
-        const double* T0r = pre ? kc + 7 : P.kf_T0 + 12 * (long long)g;   // LDS (parked by the front half) or HBM: a flat pointer either way
+        const double* T0r = P.kf_T0 + 12 * (long long)g;
         double vbb[9];                          // v, ba, bg at x: fetched before the table is computed
         if (W.dpf == 15) {
             const double* xs3[3] = {P.xv + (long long)cur * P.xv_stride, P.xba + (long long)cur * P.xv_stride, P.xbg + (long long)cur * P.xv_stride};
 #pragma unroll
             for (int q = 0; q < 3; q++)
 #pragma unroll
-                for (int i = 0; i < 3; i++) vbb[3 * q + i] = pre ? kc[19 + 3 * q + i] : xs3[q][3 * (long long)g + i];
+                for (int i = 0; i < 3; i++) vbb[3 * q + i] = xs3[q][3 * (long long)g + i];
         }
 #pragma unroll
         for (int i = 0; i < 6; i++) {
-            double v = (pre ? kc[1 + i] : xp[6 * (long long)g + i]) + (fi < 0 ? 0.0 : y[fi * W.dpf + i]);
+            double v = xp[6 * (long long)g + i] + (fi < 0 ? 0.0 : y[fi * W.dpf + i]);
             xpc[6 * (long long)g + i] = v;
             d6[i] = v;
             if (fi >= 0) cn += v * v;
         }
-        // pose table of the candidate buffer (k_backsub reads it now, k_build reads it if the step is accepted)
         pose_table_store(T0r, d6[0], d6[1], d6[2], d6[3], d6[4], d6[5], P.ptab + (long long)(1 - cur) * P.ptab_stride + (long long)g * POSE_TAB);
         if (W.dpf == 15) {
             double* xs3[3] = {P.xv + (long long)(1 - cur) * P.xv_stride, P.xba + (long long)(1 - cur) * P.xv_stride, P.xbg + (long long)(1 - cur) * P.xv_stride};
@@ -1999,6 +2068,15 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
     __syncthreads();
     if (ln == 0) { s_red[wv * 4] = sn; s_red[wv * 4 + 1] = cn; s_red[wv * 4 + 2] = mcc; s_red[wv * 4 + 3] = cc; }
     __syncthreads();
+    if (MODE == 0) {
+        // the parked key-frames' tables and the step, LDS -> HBM, coalesced, on the waves that do not sum the step scalars
+        const int t0 = nwv > 1 ? 64 : 0, nth = (int)blockDim.x - t0;
+        if (tab_lds) {
+            double* pt = P.ptab + (long long)(1 - cur) * P.ptab_stride + (long long)W.kf_base * POSE_TAB;
+            for (int i = tid - t0; i >= 0 && i < n_park * POSE_TAB; i += nth) pt[i] = A[i];
+        }
+        for (int i = tid - t0; i >= 0 && i < Np; i += nth) dl[i] = y[i];
+    }
     if (tid == 0) {
         double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
         for (int k = 0; k < nwv; k++) { a0 += s_red[k * 4]; a1 += s_red[k * 4 + 1]; a2 += s_red[k * 4 + 2]; a3 += s_red[k * 4 + 3]; }
@@ -2175,7 +2253,7 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, 
             for (int i = 0; i < 6; i++) L.Jl[i] = 0.0;
         }
         double Mi[6], g[3];
-        const bool active = group_eliminate(P, L, G, gl, lmk_valid, lfree, nobs, st.radius, false, false, Mi, g);
+        const bool active = group_eliminate(P, L, G, gl, lmk_valid, lfree, nobs, st.radius, false, false, Mi, g, nullptr);
 
         // predicted residual e = r + Jp dp of this lane's observation
         double e0 = L.r[0], e1 = L.r[1];
