@@ -34,7 +34,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "ba_types.h"
+
+// SADVIO_C16_PARENT_ORDER (compile time; tests/cpp/chol16_order_check.hip and A/B measurements): the back-substitution with the H
+// column of a step requested in front of that step's barrier, as it was before the column was requested one step ahead — the same
+// floating-point operations in the same order either way. Not a runtime switch: a binary that carries two back-substitution loops ran
+// every panel slower (docs/KERNEL_HISTORY.md, "The tail of chol16").
 
 namespace sadvio {
 
@@ -107,6 +114,30 @@ __device__ __forceinline__ void c16_symmetrize(double* A, int nb) {
         double* t = A + (c16_tile(I, I) << 8);
         t[c * 16 + q] = t[q * 16 + c];
     }
+}
+
+// The same for the diagonal tiles I0 <= I < I1 alone, on the nt threads t = 0 .. nt - 1 (a caller that lets the pivot wave mirror
+// tile (0, 0) by itself and start on it while the other waves mirror the rest).
+__device__ __forceinline__ void c16_symmetrize_tiles(double* A, int I0, int I1, int t0, int nt) {
+    for (int e = t0; e < (I1 - I0) * 120; e += nt) {
+        const int I = e / 120;
+        int q = e - I * 120;
+        const int c = (int)((1.0f + __builtin_sqrtf((float)(1 + 8 * q))) * 0.5f);
+        q -= (c * (c - 1)) >> 1;
+        double* t = A + (c16_tile(I0 + I, I0 + I) << 8);
+        t[c * 16 + q] = t[q * 16 + c];
+    }
+}
+
+// One diagonal tile mirrored by one wave, in front of its own c16_load of that tile: lane (i, k) reads the elements (i, 4 s + k)
+// (the X layout: conflict-free) and stores those below the diagonal to their mirror places. No index arithmetic to speak of:
+// the e -> (row, column) decoding above is some 45 instructions per element, which here would stand in front of the first pivot.
+__device__ __forceinline__ void c16_symmetrize_wave(double* t, int ln) {
+    const int i = ln & 15, k = ln >> 4;
+    const c16_d4 v = c16_load(t, ln);
+#pragma unroll
+    for (int s = 0; s < 4; s++)
+        if (i > 4 * s + k) t[i * 16 + 4 * s + k] = v[s];
 }
 
 // ---- one 4-column step ------------------------------------------------------------------------------------------------
@@ -308,6 +339,34 @@ __device__ __forceinline__ void c16_to_h(double* A, int I, int J, int ln) {
     c16_store(t, ln, H + H2);
 }
 
+// ---- back-substitution, one block: the 16 owners of x_I publish it, one workgroup barrier, every thread c < 16 I subtracts
+// H_I,J(c)^T x_I. hc: the thread's 16 values of H_I,J(c) (requested a step ago); hn receives those of step I - 1 ----
+__device__ __forceinline__ void c16_back_hcol(const double* A, int I, int tid, double (&h)[16]) {
+    const double* ht = A + (c16_tile(I, tid >> 4) << 8) + (tid & 15);
+#pragma unroll
+    for (int i = 0; i < 16; i++) h[i] = ht[i * 16];
+}
+__device__ __forceinline__ bool c16_back_step(const double* A, double* yv, double* xs, int N, int I, int tid, const double (&hc)[16], double (&hn)[16], double& z, bool& bad) {
+    if ((tid >> 4) == I) {
+        yv[tid] = z;
+        if (tid < N) { xs[tid] = z; if (!(fabs(z) < 1e300)) bad = true; }
+    }
+    if (I == 0) return false;
+    __syncthreads();
+    if (tid < 16 * I) {
+        double xv[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) xv[i] = yv[16 * I + i];
+        // the owners of x_{I-1} (16 (I - 1) <= tid < 16 I) have no column at step I - 1: they read the diagonal tile
+        // (I - 1, I - 1), inside the image, and drop it — one instruction stream for the whole wave, no branch around the loads
+        c16_back_hcol(A, I - 1, tid, hn);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 16; i++) z = __builtin_fma(-hc[i], xv[i], z);
+    }
+    return true;
+}
+
 // Solve [S] x = rhs for the tile-packed image A (N columns, rhs = row N; diagonal tiles already symmetric). On return
 // xs[0 .. N) = S^-1 rhs. Every thread of the 512-thread workgroup must call it. pub: C16_WORK doubles; yv: 16 * nb
 // doubles. Returns false if the solution is not finite (a non-positive pivot). ts (may be null): phase timestamps.
@@ -317,8 +376,22 @@ __device__ __forceinline__ void c16_to_h(double* A, int I, int J, int ln) {
 // column before it, as every other block column does. Same bits either way. ts[1 + 2 kb], ts[2 + 2 kb]: end of the phases of
 // block column kb < 8 (a skipped phase repeats the stamp before it), ts[18] .. ts[19]: the back-substitution from the barrier in
 // front of it to its last step, ts[20]: the end.
-template <int GATHER = 1, bool SOLVE = true>
-__device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* pub, double* yv, long long* ts, long long* dbg = nullptr, bool old_tail = false) {
+//
+// c16_solve_hooked: the same with a caller's hook, for work that wants to run in the shadow of the first block column instead of in
+// front of the first pivot block (k_solve's end-of-solve test):
+//   hook.under_first_panel()   every thread calls it behind the first workgroup barrier, in front of phase A of block column 0;
+//   hook.ended()               every thread calls it behind the barrier in front of the back-substitution and must get the same answer;
+//                              on true every thread returns true at once. (Asked behind the barrier that closes the first panel
+//                              instead, an exit inside the loop, every panel phase ran ~100 cycles longer and the gain was gone:
+//                              docs/KERNEL_HISTORY.md "k_solve's front half under the first pivot block".)
+// No barrier is added, none is skipped by one wave alone, the loop over the block columns is untouched. C16NoHook does nothing:
+// c16_solve is the code it was.
+struct C16NoHook {
+    __device__ __forceinline__ void under_first_panel() {}
+    __device__ __forceinline__ bool ended() { return false; }
+};
+template <int GATHER = 1, bool SOLVE = true, class HOOK>
+__device__ __forceinline__ bool c16_solve_hooked(double* A, int N, double* xs, double* pub, double* yv, long long* ts, long long* dbg, bool old_tail, HOOK& hook) {
     const int tid = threadIdx.x, ln = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = blockDim.x >> 6;
     const int nb = c16_blocks(N + 1);     // tile rows incl. the right-hand-side row
@@ -334,6 +407,8 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
     __syncthreads();
     long long tlast = 0;                  // the last stamp written (repeated for a skipped phase)
     if (ts && tid == 0) ts[0] = tlast = clock64();
+    static_assert(SOLVE || std::is_same<HOOK, C16NoHook>::value, "a hook needs SOLVE = true: the barrier that closes SOLVE = false does not ask it");
+    hook.under_first_panel();
     for (int kb = 0; kb < nbc; kb++) {
         const int m = nb - kb - 1;        // tile rows below the diagonal tile
         // ---- phase A: L_Ik = A_Ik L_kk^-T, one product per panel tile. The pivot wave takes the tile it needs next,
@@ -423,6 +498,7 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
     //      c < 16 I subtracts H_I,J(c)^T x_I (16 consecutive doubles of tile (I, c / 16)): I descending, i ascending ----
     const int IB = N >> 4, r = N & 15;
     __syncthreads();
+    if (hook.ended()) return true;
     if (ts && tid == 0) ts[18] = clock64();
     double z = 0.0;
     if (tid < N) {
@@ -440,6 +516,7 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
         z = tid < N ? xi : 0.0;
     }
     bool bad = false;
+#ifdef SADVIO_C16_PARENT_ORDER
     for (int I = nbc - 1; I >= 0; I--) {
         double hcol[16];
         if (tid < 16 * I) {                // issued before the barrier: independent of x_I
@@ -464,11 +541,27 @@ __device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* 
             for (int i = 0; i < 16; i++) z = __builtin_fma(-hcol[i], xv[i], z);
         }
     }
+#else
+    // The H column of a step is requested ONE STEP AHEAD, behind the reads of x of the step before it: LDS reads retire in order, so
+    // the FMAs wait for x_I alone, the column of step I - 1 lands under them, and the owners' store of x_{I-1} follows the last FMA
+    // with no wait in front of it. Two register buffers, the loop body twice.
+    double h0[16], h1[16];
+    if (nbc >= 1 && tid < 16 * (nbc - 1)) c16_back_hcol(A, nbc - 1, tid, h0);
+    for (int I = nbc - 1; I >= 0; I -= 2) {
+        if (!c16_back_step(A, yv, xs, N, I, tid, h0, h1, z, bad)) break;
+        if (!c16_back_step(A, yv, xs, N, I - 1, tid, h1, h0, z, bad)) break;
+    }
+#endif
     if (ts && tid == 0) ts[19] = clock64();
     if (bad) s_bad = 1;
     __syncthreads();
     if (ts && tid == 0) ts[20] = clock64();
     return s_bad == 0;
+}
+template <int GATHER = 1, bool SOLVE = true>
+__device__ __forceinline__ bool c16_solve(double* A, int N, double* xs, double* pub, double* yv, long long* ts, long long* dbg = nullptr, bool old_tail = false) {
+    C16NoHook none;
+    return c16_solve_hooked<GATHER, SOLVE>(A, N, xs, pub, yv, ts, dbg, old_tail, none);
 }
 
 }  // namespace sadvio

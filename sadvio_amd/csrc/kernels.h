@@ -1453,6 +1453,51 @@ __device__ __noinline__ double prior_lin_record_call(const double* T0, double d0
     return prior_lin_record(T0r, q.T_prior, q.inf, d6, rec);
 }
 
+// k_solve<0, .>: the finalisation test of the in-LDS solve as the hook of c16_solve_hooked (chol16.h). It only ends the solve, so it
+// runs behind c16_solve's first barrier, under the first panel, on the last thread: a wave without a panel tile up to 8 tile rows
+// (N_p <= 127). Every wave reads the verdict behind the barrier in front of the back-substitution and leaves there: an ended solve
+// has written its state record and the `acc` fields, as before, and nothing else; it costs one factorisation more, once per solve
+// that ends here (gradient tolerance, solver time, zero iterations).
+struct SolveEndHook {
+    const DevPtrs& P;
+    const LmState& st;
+    LmState* stp;
+    IterAcc* acc;
+    const double* s_red;   // [wave][3]: gradient maximum | cost | fixed cost, complete at the barrier in front of under_first_panel
+    int* s_done;           // zero since before that barrier
+    bool is_ended;
+    __device__ __forceinline__ void under_first_panel() {
+        if (threadIdx.x != blockDim.x - 1) return;
+        constexpr int MAXW = SOLVE_THREADS / 64;
+        double r[MAXW * 3];            // all requested before the first use: one LDS round trip, not one per wave
+#pragma unroll
+        for (int k = 0; k < MAXW * 3; k++) r[k] = s_red[k];
+        __builtin_amdgcn_sched_barrier(0);
+        double g = 0, cs = 0, fs = 0;   // (k_solve runs with SOLVE_THREADS threads: MAXW waves, added in the order the loop over nwv had)
+#pragma unroll
+        for (int k = 0; k < MAXW; k++) { g = fmax(g, r[k * 3]); cs += r[k * 3 + 1]; fs += r[k * 3 + 2]; }
+        acc->gmax_bits = (unsigned long long)__double_as_longlong(g);
+        acc->lin_cost = cs;
+        acc->fixed_cost = fs;
+        acc->cand_cost = 0.0; acc->mcc = 0.0; acc->step_norm2 = 0.0; acc->cand_norm2 = 0.0;
+        // FinalizeIterationAndCheckIfMinimizerCanContinue of the previous iteration (of iteration zero at slot 0), in Ceres'
+        // order: solver time, then the gradient tolerance (the iteration limit was applied by lm_decide)
+        const bool time_up = P.o.max_time_ticks > 0.0 && P.t_start && (double)(wall_clock64() - *P.t_start) >= P.o.max_time_ticks;
+        acc->time_up = time_up ? 1 : 0;
+        // (max_num_iterations = 0: Ceres evaluates the initial cost, tests the gradient tolerance and stops with NO_CONVERGENCE)
+        const bool no_iterations = st.iter == 0 && P.o.max_num_iterations <= 0;
+        if (time_up || g <= P.o.gradient_tolerance || no_iterations) {
+            LmState e = st;
+            e.done = 1; e.termination = (time_up || g > P.o.gradient_tolerance) ? 0 : 3;
+            e.x_cost = 0.5 * cs;
+            if (e.iter == 0) e.initial_cost = e.x_cost;
+            *stp = e;
+            *s_done = 1;
+        }
+    }
+    __device__ __forceinline__ bool ended() { is_ended = *s_done != 0; return is_ended; }
+};
+
 template <int MODE, bool EXTRAS>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1473,6 +1518,14 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
     LmState st = *stp;                          // uniform address: every thread keeps its own copy (no LDS round trip, no barrier)
     if (MODE == 1 && tid == 0) P.big_info[w] = 0;
     if (st.done) return;
+    // MODE 0: wave 0 starts the first pivot block as soon as tile (0, 0) is ready and the finalisation test runs under the first
+    // panel (SolveEndHook). SADVIO_SOLVE_PARENT_FRONT (compile time, A/B measurements) keeps the test in front of the factorisation.
+#ifdef SADVIO_SOLVE_PARENT_FRONT
+    constexpr bool SPLIT_FRONT = false;
+#else
+    constexpr bool SPLIT_FRONT = MODE == 0;
+#endif
+    SolveEndHook end_hook{P, st, stp, acc, s_red, &s_done, false};
     const int Np = W.Np;
     const long long ld = W.ld;
     double* Sg = P.S + W.S_off;
@@ -1805,6 +1858,27 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
     gm = wave_max(gm); cost_part = wave_sum(cost_part); fixed_part = wave_sum(fixed_part);
     if (ln == 0) { s_red[wv * 3] = gm; s_red[wv * 3 + 1] = cost_part; s_red[wv * 3 + 2] = fixed_part; }
     if (tid == 0) s_done = 0;
+    if (SPLIT_FRONT) {
+        // In-LDS windows: the first pivot block needs tile (0, 0) alone, and that tile is complete once wave 0 has run the pass
+        // above (its diagonal; the right-hand side's row when N_p < 16) and mirrored it: wave 0 goes straight on into c16_solve
+        // while the other waves mirror the other diagonal tiles. The finalisation test (end_hook) runs behind c16_solve's first
+        // barrier, under the first panel, and every wave leaves at the barrier in front of the back-substitution if it ended the solve.
+        if (Np > 0) {
+            if (wv == 0) {
+                c16_symmetrize_wave(A, ln);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the wave's own stores in front of its tile load (LDS completes in order)
+            } else {
+                c16_symmetrize_tiles(A, 1, nbt, tid - 64, (int)blockDim.x - 64);
+            }
+        } else {        // nothing to factor: the test between two barriers, as it was
+            __syncthreads();
+            end_hook.under_first_panel();
+            __syncthreads();
+            if (end_hook.ended()) return;
+        }
+        SADVIO_TS(3, 2);
+        SADVIO_TS(3, 3);
+    } else {
     __syncthreads();
     if (!BIG) c16_symmetrize(A, nbt);           // the assembly writes i >= j only; the diagonal tiles are used as full symmetric tiles
     if (tid == blockDim.x - 1) {   // the last thread has the least symmetrisation work above
@@ -1843,12 +1917,20 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
         __syncthreads();
     }
     SADVIO_TS(3, 3);
+    }  // !SPLIT_FRONT
     if (MODE == 1) return;  // the host enqueues potrf / potrs on S, gred next
     }  // MODE != 2
     long long* ts = SADVIO_TS_PTR((P.debug & 4096) && blockIdx.x == 0 && slot == 3);
     if (MODE == 0) {
         bool ok = true;  // Np == 0 (every key-frame constant, landmarkOptimization): nothing to factor
-        if (Np > 0) ok = c16_solve<1>(A, Np, xs, pub, yv, ts ? ts + 64 : nullptr, nullptr, P.c16_old_tail != 0);   // SADVIO_KERNEL_TS builds: per-block-column cycle stamps
+        if (Np > 0) {   // SADVIO_KERNEL_TS builds: per-block-column cycle stamps
+            if (SPLIT_FRONT) {
+                ok = c16_solve_hooked<1, true>(A, Np, xs, pub, yv, ts ? ts + 64 : nullptr, nullptr, P.c16_old_tail != 0, end_hook);
+                if (end_hook.is_ended) return;
+            } else {
+                ok = c16_solve<1>(A, Np, xs, pub, yv, ts ? ts + 64 : nullptr, nullptr, P.c16_old_tail != 0);
+            }
+        }
         if (!ok) {
             if (tid == 0) acc->chol_fail = 1;
             return;
