@@ -663,8 +663,20 @@ typedef struct sadvio_cov_request {
  * taken in a fixed order: no floating-point atomics).
  * Returns SADVIO_E_STATE before a solve or inside a begin_update bracket; SADVIO_E_INVALID_ARG for an index out of range, for a
  * window sharded over several GPUs, a window with line landmarks, or a batch the throughput kernels solved (the error text says
- * which), and for a reduced system of 2047 columns or more; SADVIO_E_NOT_USABLE when the factorisation of S meets a pivot that is
- * not safely positive (gauge not fixed: no constant key-frame and no prior) — the outputs are then untouched. */
+ * which), and for a reduced system of 2047 columns or more that is not bandable (below); SADVIO_E_NOT_USABLE when the factorisation
+ * of S meets a pivot that is not safely positive (gauge not fixed: no constant key-frame and no prior) — the outputs are then
+ * untouched.
+ * The band route. A window without a dense prior, landmarks kept in the reduced system or line landmarks has a block-banded S: no
+ * non-zero at |i - j| >= bw = (hb + 1) d, hb the largest distance in free key-frame index that a landmark, an IMU pair or a
+ * relative-pose factor of the sparsified prior couples (the rule of the solve's band routes). It is BANDABLE when N_p > 0, bw < N_p
+ * and bw + nb <= 128 (nb = 6, or 5 with has_imu: the band route's LDS image; d = 6: hb <= 19, d = 15: hb <= 7). For such a window
+ * the band of Sigma_pp follows from the band Cholesky factor by the Takahashi recursion (O(N_p bw^2) work, one workgroup, FP64, the
+ * same three pivot tests), pair blocks of key-frames further apart than hb by band substitution, and only the blocks asked for
+ * travel to the host. pair(a, b) and pair(b, a)^T are equal to the bit; a pair's bits do not depend on the other pairs asked for.
+ * Environment variable SADVIO_COV_BAND, read when the handle is created: unset, a bandable window takes the band route only where
+ * the call was refused before (N_p >= 2047), so no window served before changes a bit; 1, every bandable window takes it (tests,
+ * A/B timing); 0, never (the 2047-column refusal included). In sadvio_ba_get_kernel_times the route shows as the classes cov_band
+ * (forward sweep), cov_band_sel (backward sweep), cov_band_pairs and cov_band_gather in place of cov_invert. */
 int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_request *rq, double *kf_cov, double *pair_cov,
                          double *lmk_cov, int32_t *n_lmk_singular);
 
@@ -679,6 +691,9 @@ int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_reques
  *                           call in a fixed number of launches behind ONE wait. Another factorisation order than the single
  *                           call's: equal within rounding, not to the bit.
  *   SADVIO_COV_ROUTE_DENSE  N_p > 176: the route of sadvio_ba_covariance, item by item. Same bits as the single call.
+ *   SADVIO_COV_ROUTE_BAND   a window that sadvio_ba_covariance sends down its band route (see there and SADVIO_COV_BAND: by default
+ *                           a bandable window of 2047 columns or more), item by item through the single call's steps. Same bits as
+ *                           the single call.
  * The environment variable SADVIO_COV_BATCH_LDS=0 (read when the handle is created) sends every item with N_p > 0 down the DENSE
  * route. The LDS and NONE items are processed in groups of windows whose work arrays stay under 1 GiB
  * (SADVIO_COV_BATCH_SCRATCH_MB overrides the figure; a window larger than the budget is a group of its own); the grouping does not
@@ -689,13 +704,15 @@ int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_reques
  * other items are unaffected and the call returns SADVIO_OK.
  * Argument errors fail the whole call before anything is written, in any item, with the single call's codes: SADVIO_E_STATE before
  * a solve or inside a begin_update bracket; SADVIO_E_INVALID_ARG for n_item < 0, null `items` with n_item > 0, an index out of
- * range in any item, a handle sharded over several GPUs, a window with line landmarks, a reduced system of 2047 columns or more.
+ * range in any item, a handle sharded over several GPUs, a window with line landmarks, a reduced system of 2047 columns or more
+ * that is not bandable.
  * n_item = 0 returns SADVIO_OK and touches nothing.
  * No floating-point atomics: two calls return the same bits, and an item's bits depend neither on the other items of the call nor
  * on its position among them. The solve's deltas, summaries, trace and the handle's prior are left untouched. */
 #define SADVIO_COV_ROUTE_NONE  0
 #define SADVIO_COV_ROUTE_LDS   1
 #define SADVIO_COV_ROUTE_DENSE 2
+#define SADVIO_COV_ROUTE_BAND  3
 
 typedef struct sadvio_cov_batch_item {
     int32_t w;               /* in: window of the batch */

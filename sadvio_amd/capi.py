@@ -125,7 +125,7 @@ class CovBatchItemC(C.Structure):
                 ("kf_cov", _dp), ("pair_cov", _dp), ("lmk_cov", _dp)]
 
 
-COV_ROUTE_NONE, COV_ROUTE_LDS, COV_ROUTE_DENSE = 0, 1, 2   # SADVIO_COV_ROUTE_*
+COV_ROUTE_NONE, COV_ROUTE_LDS, COV_ROUTE_DENSE, COV_ROUTE_BAND = 0, 1, 2, 3   # SADVIO_COV_ROUTE_*
 PRIOR_RESIDENT = -1
 # SADVIO_EIG_CUT_*: the C ABI's default (a zero-initialised request) is the reference's absolute 1e-12; this harness and the
 # oracle's wrapper default to "noise_floor" because the parity tests compare n_full, which only that mode makes reproducible

@@ -197,6 +197,11 @@ struct CovScratch {
     DevBuf<double> ptab, hll, hinv, ent_w, ent_hpp, S, Sig, lout, V, Lx, G, Z;
     DevBuf<int> status, ent_n, ent_col, step_of;
     std::vector<double> h_sig, h_lout;
+    // the band route (cov_band_kernels.h): L's band and the inverse pivot blocks | the solved columns of the out-of-band pairs | the
+    // gathered blocks; the in-band pair table of k_cov_schur | the gather table | the pivot flag
+    DevBuf<double> Lb, Linv, X, gout;
+    DevBuf<int> pair_tab, gtab, xcol, bflag;
+    std::vector<int> h_pair_tab, h_gtab, h_xcol;
 };
 
 // Work buffers of sadvio_ba_covariance_batch (cov_batch_driver.h). The pools hold the work arrays (pool, ipool) and the results (rpool)
@@ -238,6 +243,7 @@ struct EnvCfg {
     int lm = -1, pf_wg = -1;            // -1: not set
     int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
     int cov_batch_lds = 1, cov_batch_scratch_mb = 1024;   // sadvio_ba_covariance_batch: the in-LDS inverse (0: every item down the dense route, A/B) | scratch budget of one group
+    int cov_band = -1;   // covariance, the band route (cov_band_kernels.h): -1 not set: only where the call was refused before (N_p >= 2047) | 1: every bandable window | 0: never
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {
@@ -246,6 +252,7 @@ struct EnvCfg {
         debug = num("SADVIO_DEBUG", 0); lm = num("SADVIO_LM", -1); pf_wg = num("SADVIO_PF_WG", -1);
         tile_rounds = num("SADVIO_TILE_ROUNDS", 0); lm_subs = num("SADVIO_LM_SUBS", 0); band_c = num("SADVIO_BAND_C", 0);
         cov_batch_lds = num("SADVIO_COV_BATCH_LDS", 1); cov_batch_scratch_mb = num("SADVIO_COV_BATCH_SCRATCH_MB", 1024);
+        cov_band = num("SADVIO_COV_BAND", -1);
         if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);
         marg_pivoted = on("SADVIO_MARG_PIVOTED"); marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
@@ -373,7 +380,7 @@ struct ScopedTimer {
     sadvio_ba_handle* h;
     int pool = -1;
     ScopedTimer(sadvio_ba_handle* h_, const char* name) : h(h_) {
-        if (!h->cfg.profile_kernels) return;
+        if (!h->cfg.profile_kernels || !name) return;   // (a null name: no timer)
         if (h->ev_next == h->ev_pool.size()) {
             hipEvent_t a, b;
             if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;

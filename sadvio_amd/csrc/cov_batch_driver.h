@@ -5,7 +5,8 @@
 // picks for them. Units whose N_p is at most COVB_CAP (route LDS) or zero (route NONE) are processed in groups whose work arrays
 // stay under the scratch budget; a group is one launch sequence on the handle's stream (cov_batch_kernels.h), its results go to
 // pinned host memory with one asynchronous copy, and the call waits once, after the last group. A unit above the cap (route DENSE)
-// goes item by item through cov_driver.h's steps as they are, with the wait that route has.
+// goes item by item through cov_driver.h's steps as they are, with the wait that route has; so does a unit on the band route (route
+// BAND, cov_driver.h: cov_band_route), whatever its N_p.
 //
 // After a solve by the throughput kernels (lm_kernels.h). sadvio_ba_covariance refuses such a batch; this call accepts it, on these
 // grounds. (i) Both solve paths keep two delta buffers per array and LmState::cur names the one holding the accepted state x: k_solve
@@ -55,7 +56,7 @@ int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* ite
             if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) { h->err = "covariance_batch: key-frame index of a pair out of range"; return SADVIO_E_INVALID_ARG; }
         for (int i = 0; i < rq->n_lmk; i++)
             if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) { h->err = "covariance_batch: landmark index out of range"; return SADVIO_E_INVALID_ARG; }
-        if (d.Np + 1 > PCH_MAXN) { h->err = "covariance_batch: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
+        if (d.Np + 1 > PCH_MAXN && !cov_band_route(h, w)) { h->err = "covariance_batch: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
     }
     return SADVIO_OK;
 }
@@ -69,7 +70,8 @@ void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, 
         const WinDev& d = h->plan.wins[I.w].d;
         I.status = SADVIO_OK; I.n_lmk_singular = 0;
         I.route = d.Np == 0 ? SADVIO_COV_ROUTE_NONE : (d.Np <= COVB_CAP && h->env.cov_batch_lds != 0 ? SADVIO_COV_ROUTE_LDS : SADVIO_COV_ROUTE_DENSE);
-        if (I.route == SADVIO_COV_ROUTE_DENSE) continue;
+        if (cov_band_route(h, I.w)) I.route = SADVIO_COV_ROUTE_BAND;   // (cov_driver.h: by default only a window the dense route refuses)
+        if (I.route == SADVIO_COV_ROUTE_DENSE || I.route == SADVIO_COV_ROUTE_BAND) continue;
         const CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
         if (of_win[I.w] < 0) {
             of_win[I.w] = (int)units.size();
@@ -98,7 +100,9 @@ int covb_dense_item(sadvio_ba_handle* h, sadvio_cov_batch_item& I) {
         return SADVIO_OK;
     }
     if (int rc = cov_landmarks(h, I.w, R)) return rc;
-    return cov_read_back(h, I.w, &I.rq, R, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
+    const int rc = cov_read_back(h, I.w, &I.rq, R, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
+    if (rc == SADVIO_E_NOT_USABLE && R.band) { I.status = SADVIO_E_NOT_USABLE; return SADVIO_OK; }   // the band route's pivot flag comes with the wait
+    return rc;
 }
 
 // 3. Groups of consecutive units under the scratch budget (a unit larger than the budget is a group of its own); the pools, the
@@ -266,7 +270,7 @@ int covb_run(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items) {
     std::vector<int> unit_of;
     covb_routes(h, n_item, items, units, unit_of);
     for (int it = 0; it < n_item; it++)
-        if (items[it].route == SADVIO_COV_ROUTE_DENSE)
+        if (items[it].route == SADVIO_COV_ROUTE_DENSE || items[it].route == SADVIO_COV_ROUTE_BAND)
             if (int rc = covb_dense_item(h, items[it])) return rc;
     if (units.empty()) return SADVIO_OK;
     std::vector<CovbGroup> groups;

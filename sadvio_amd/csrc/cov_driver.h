@@ -1,5 +1,9 @@
 // cov_driver.h — the host side of sadvio_ba_covariance as named steps
 //   cov_check -> cov_routes -> cov_assemble -> cov_invert -> cov_landmarks -> cov_read_back
+// Sigma_pp is formed densely (cov_invert) or, for a block-banded S, inside its band only (cov_invert_band, cov_band_kernels.h: the
+// BAND route; cov_band_route says when). On the band route k_cov_schur runs over the table of in-band key-frame pairs, no kernel
+// reads an entry of Sigma outside the band, pair blocks outside the band come from band substitution, and the host receives the
+// blocks asked for and nothing else.
 // The kernels are cov_kernels.h's; the factorisation of S and the triangular inverse are marg_driver.h's (factor_unpivoted,
 // prior_build_Z: the route sadvio_ba_sparsify takes to Sigma_k = Ak^-1), called as they are. Nothing of the solve is touched: the
 // delta buffers, the final records, the trace and the handle's prior are read only; the work buffers are the handle's CovScratch
@@ -7,6 +11,7 @@
 // Part of the library's single translation unit (ba_capi.hip, which includes it below marg_driver.h); not a public header.
 #pragma once
 #include "ba_handle.h"
+#include "cov_band_kernels.h"
 #include "cov_kernels.h"
 #include "marg_driver.h"
 
@@ -22,7 +27,26 @@ struct CovRoutes {
     bool want_lmk = false;  // landmark blocks asked for (k_cov_lmk)
     int G = 16;             // lanes per landmark of k_cov_lmk: 16 up to 8 free key-frames, else 64
     int n_lmk_out = 0;      // landmark blocks written
+    bool band = false;      // the band route; then hb / bw / nb: block half-bandwidth, (hb + 1) * dpf, block column of the sweeps
+    int hb = 0, bw = 0, nb = 0, dpf = 6;
 };
+
+// The band route's block column: 6 for dpf 6, 5 for dpf 15 (as k_band_solve)
+inline int cov_band_nb(int dpf) { return dpf == 6 ? 6 : 5; }
+
+// Does window w take the band route? Bandable: N_p > 0, bw < N_p (window_bandwidth: no dense prior, kept landmarks or lines) and the
+// kernel's LDS image fits (bw + nb <= COVBAND_MAXW). SADVIO_COV_BAND unset: only a window the dense route refuses (N_p >= 2047);
+// 1: every bandable window; 0: never.
+bool cov_band_route(const sadvio_ba_handle* h, int w, int* hb_out = nullptr, int* bw_out = nullptr) {
+    const WinDev& d = h->plan.wins[w].d;
+    if (h->env.cov_band == 0 || d.Np <= 0) return false;
+    int hb = 0;
+    const int bw = window_bandwidth(h, w, &hb), nb = cov_band_nb(d.dpf);
+    if (hb_out) *hb_out = hb;
+    if (bw_out) *bw_out = bw;
+    if (!(bw < d.Np && bw + nb <= COVBAND_MAXW && d.Np % nb == 0)) return false;
+    return h->env.cov_band > 0 || d.Np + 1 > PCH_MAXN;
+}
 
 // 1. State and arguments. Host work only.
 int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov) {
@@ -42,7 +66,7 @@ int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const do
         if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) { h->err = "covariance: key-frame index of a pair out of range"; return SADVIO_E_INVALID_ARG; }
     for (int i = 0; i < rq->n_lmk; i++)
         if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) { h->err = "covariance: landmark index out of range"; return SADVIO_E_INVALID_ARG; }
-    if (d.Np + 1 > PCH_MAXN) { h->err = "covariance: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
+    if (d.Np + 1 > PCH_MAXN && !cov_band_route(h, w)) { h->err = "covariance: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
     (void)lmk_cov;
     return SADVIO_OK;
 }
@@ -58,6 +82,8 @@ CovRoutes cov_routes(const sadvio_ba_handle* h, int w, const sadvio_cov_request*
     R.n_lmk_out = rq->n_lmk < 0 ? d.n_lmk : rq->n_lmk;
     R.want_lmk = lmk_cov != nullptr && R.n_lmk_out > 0;
     R.G = d.n_free_kf <= 8 ? 16 : 64;
+    R.band = cov_band_route(h, w, &R.hb, &R.bw);
+    R.nb = cov_band_nb(d.dpf); R.dpf = d.dpf;
     return R;
 }
 
@@ -68,6 +94,7 @@ CovDev cov_dev(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     C.ptab = V.ptab.p; C.hll = V.hll.p; C.hinv = V.hinv.p; C.status = V.status.p; C.ent_n = V.ent_n.p;
     C.ent_col = V.ent_col.p; C.ent_w = V.ent_w.p; C.ent_hpp = V.ent_hpp.p;
     C.S = V.S.p; C.Sig = V.Sig.p; C.lout = V.lout.p;
+    C.pair_tab = R.band ? V.pair_tab.p : nullptr;
     return C;
 }
 
@@ -84,6 +111,16 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     SolveOpts so{};
     so.huber_a = h->cov_huber_a;
     const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
+    int n_schur = d.n_free_kf * (d.n_free_kf + 1) / 2;
+    if (R.band && R.Np > 0) {   // the in-band pairs (a, b), a >= b, a - b <= hb: nothing else of S can be non-zero
+        std::vector<int>& tab = V.h_pair_tab;
+        tab.clear();
+        for (int a = 0; a < d.n_free_kf; a++)
+            for (int b = std::max(0, a - R.hb); b <= a; b++) { tab.push_back(a); tab.push_back(b); }
+        n_schur = (int)tab.size() / 2;
+        HIP_TRY(V.pair_tab.alloc(tab.size()));
+        HIP_TRY(hipMemcpyAsync(V.pair_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
+    }
     const CovDev C = cov_dev(h, w, R);
     ScopedTimer t(h, "cov_assemble");
     const int n_tab = std::max(d.n_kf, d.n_lmk);
@@ -91,9 +128,15 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     const int n_tiles = d.tile_end - d.tile_begin;
     if (n_tiles > 0) hipLaunchKernelGGL(R.pix ? k_cov_assemble<0> : k_cov_assemble<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C);
     if (R.Np == 0) return SADVIO_OK;
-    if (d.n_free_kf > 0) hipLaunchKernelGGL(k_cov_schur, dim3(d.n_free_kf * (d.n_free_kf + 1) / 2), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C);
+    if (d.n_free_kf > 0) {
+        ScopedTimer ts(h, R.band ? "k_cov_schur" : nullptr);   // (band route: a class of its own inside cov_assemble's span, for the profile)
+        hipLaunchKernelGGL(k_cov_schur, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C);
+    }
     if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
-    hipLaunchKernelGGL(k_cov_factors, dim3(1), dim3(64), 0, h->stream, P, C);
+    {
+        ScopedTimer tf(h, R.band ? "k_cov_factors" : nullptr);
+        hipLaunchKernelGGL(k_cov_factors, dim3(1), dim3(64), 0, h->stream, P, C);
+    }
     if (R.dense) hipLaunchKernelGGL(k_cov_dense, dim3((unsigned)(((long long)d.dp_n * d.dp_n + 255) / 256)), dim3(256), 0, h->stream, P, C);
     HIP_TRY(hipGetLastError());
     return SADVIO_OK;
@@ -101,9 +144,39 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
 
 // 3. Sigma_pp = S^-1: unpivoted Cholesky with every pivot tested, triangular inverse Z = G^-T, Sigma_pp = Z^T Z.
 // usable = false: a pivot is not safely positive (gauge not fixed).
+CovBand cov_band_dev(sadvio_ba_handle* h, const CovRoutes& R) {
+    CovScratch& V = h->cv;
+    CovBand B{};
+    B.n = R.Np; B.bw = R.bw; B.M = R.bw + R.nb; B.dpf = R.dpf;
+    B.tau = -pchol_tau(R.Np, SADVIO_EIG_CUT_REFERENCE);          // the reference's cut is an absolute pivot floor (a negative tau_rel)
+    B.safe_rel = 1024.0 * R.Np * 2.220446049250313e-16;          // run_wfac's
+    B.S = V.S.p; B.Sig = V.Sig.p; B.Lb = V.Lb.p; B.Linv = V.Linv.p; B.flag = V.bflag.p;
+    return B;
+}
+
+// 3 (band route). The band of Sigma_pp: band Cholesky with every pivot tested, then the Takahashi recursion. Two launches whatever
+// N_p; no host wait: a failed pivot sets V.bflag, which cov_read_back_band reads behind the call's one wait.
+int cov_invert_band(sadvio_ba_handle* h, const CovRoutes& R) {
+    CovScratch& V = h->cv;
+    const int M = R.bw + R.nb;
+    HIP_TRY(V.Lb.alloc((size_t)R.Np * M)); HIP_TRY(V.Linv.alloc((size_t)R.Np * R.nb)); HIP_TRY(V.bflag.alloc(2));
+    HIP_TRY(hipMemsetAsync(V.bflag.p, 0, sizeof(int) * 2, h->stream));
+    const CovBand B = cov_band_dev(h, R);
+    const size_t lds = covband_lds_bytes(M, R.nb);
+    auto kc = R.nb == 6 ? k_cov_band_chol<6> : k_cov_band_chol<5>;
+    auto ks = R.nb == 6 ? k_cov_band_sel<6> : k_cov_band_sel<5>;
+    HIP_TRY(hipFuncSetAttribute((const void*)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)covband_lds_bytes(COVBAND_MAXW, R.nb)));
+    HIP_TRY(hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)covband_lds_bytes(COVBAND_MAXW, R.nb)));
+    { ScopedTimer t(h, "cov_band"); hipLaunchKernelGGL(kc, dim3(1), dim3(COVBAND_THREADS), lds, h->stream, B); }
+    { ScopedTimer t(h, "cov_band_sel"); hipLaunchKernelGGL(ks, dim3(1), dim3(COVBAND_THREADS), lds, h->stream, B); }
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
 int cov_invert(sadvio_ba_handle* h, const CovRoutes& R, bool& usable) {
     usable = true;
     if (R.Np == 0) return SADVIO_OK;
+    if (R.band) return cov_invert_band(h, R);
     CovScratch& V = h->cv;
     MargScratch& M = h->mg;
     const int n = R.Np;
@@ -139,12 +212,84 @@ int cov_landmarks(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     return SADVIO_OK;
 }
 
+// 5 (band route). The columns of the pair blocks outside the band by substitution with L's band, one workgroup per distinct column
+// key-frame: the canonical block is (a, b), a > b in free index, and (b, a) is read as its transpose, so pair(a, b) and
+// pair(b, a)^T agree to the bit and a pair's bits do not depend on what else was asked for. The blocks asked for are gathered on the
+// device; one wait; SADVIO_E_NOT_USABLE with the outputs untouched when a pivot failed its test.
+int cov_read_back_band(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const CovRoutes& R, double* kf_cov, double* pair_cov, double* lmk_cov,
+                       int32_t* n_lmk_singular) {
+    const WinDev& d = h->plan.wins[w].d;
+    CovScratch& V = h->cv;
+    const int n = R.Np, dpf = d.dpf, bs = dpf * dpf;
+    const int nk = kf_cov ? rq->n_kf : 0, np = pair_cov ? rq->n_pair : 0, nblk = nk + np;
+    std::vector<int>& tab = V.h_gtab; std::vector<int>& xcol = V.h_xcol;
+    tab.assign(4 * (size_t)std::max(nblk, 1), 0); xcol.clear();
+    std::vector<int> x_of(d.n_free_kf, -1);
+    for (int e = 0; e < nblk; e++) {
+        const int ka = e < nk ? rq->kf[e] : rq->pair_a[e - nk], kb = e < nk ? ka : rq->pair_b[e - nk];
+        const int fa = h->plan.kf_fidx[d.kf_base + ka], fb = h->plan.kf_fidx[d.kf_base + kb];
+        int* T = &tab[4 * (size_t)e];
+        if (fa < 0 || fb < 0) { T[0] = COVBAND_G_ZERO; continue; }
+        if (std::abs(fa - fb) <= R.hb) { T[0] = COVBAND_G_SIG; T[1] = fa * dpf; T[2] = fb * dpf; continue; }
+        const int lo = std::min(fa, fb), hi = std::max(fa, fb);
+        if (x_of[lo] < 0) { x_of[lo] = (int)xcol.size(); xcol.push_back(lo * dpf); }
+        T[0] = fa > fb ? COVBAND_G_COL : COVBAND_G_COLT; T[1] = hi * dpf; T[3] = x_of[lo];
+    }
+    const CovBand B = cov_band_dev(h, R);
+    std::vector<double>& out = V.h_sig; std::vector<double>& lo = V.h_lout;
+    if (nblk > 0) {
+        HIP_TRY(V.gtab.alloc(tab.size())); HIP_TRY(V.gout.alloc((size_t)nblk * bs));
+        HIP_TRY(hipMemcpyAsync(V.gtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
+        if (!xcol.empty()) {
+            HIP_TRY(V.xcol.alloc(xcol.size())); HIP_TRY(V.X.alloc(xcol.size() * (size_t)dpf * n));
+            HIP_TRY(hipMemcpyAsync(V.xcol.p, xcol.data(), sizeof(int) * xcol.size(), hipMemcpyHostToDevice, h->stream));
+            ScopedTimer t(h, "cov_band_pairs");
+            hipLaunchKernelGGL(k_cov_band_cols, dim3((unsigned)xcol.size()), dim3(COVBAND_THREADS), 0, h->stream, B, (const int*)V.xcol.p, V.X.p);
+        }
+        {
+            ScopedTimer t(h, "cov_band_gather");
+            hipLaunchKernelGGL(k_cov_band_gather, dim3(nblk), dim3(COVBAND_THREADS), 0, h->stream, B, (const int*)V.gtab.p, (const double*)V.X.p, V.gout.p);
+        }
+        HIP_TRY(hipGetLastError());
+        out.resize((size_t)nblk * bs);
+        HIP_TRY(hipMemcpyAsync(out.data(), V.gout.p, sizeof(double) * (size_t)nblk * bs, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (R.want_lmk) {
+        lo.resize(9 * (size_t)d.n_lmk);
+        HIP_TRY(hipMemcpyAsync(lo.data(), V.lout.p, sizeof(double) * 9 * (size_t)d.n_lmk, hipMemcpyDeviceToHost, h->stream));
+    }
+    std::vector<int> st;
+    if (n_lmk_singular && d.n_lmk > 0) {
+        st.resize(d.n_lmk);
+        HIP_TRY(hipMemcpyAsync(st.data(), V.status.p, sizeof(int) * (size_t)d.n_lmk, hipMemcpyDeviceToHost, h->stream));
+    }
+    int flag[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(flag, V.bflag.p, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->cfg.profile_kernels) collect_timers(h);
+    if (flag[0] != 0) {
+        h->err = "covariance: the reduced information matrix is not positive definite (gauge not fixed: no constant key-frame, no prior)";
+        return SADVIO_E_NOT_USABLE;
+    }
+    if (nk > 0) memcpy(kf_cov, out.data(), sizeof(double) * (size_t)nk * bs);
+    if (np > 0) memcpy(pair_cov, out.data() + (size_t)nk * bs, sizeof(double) * (size_t)np * bs);
+    if (R.want_lmk)
+        for (int i = 0; i < R.n_lmk_out; i++) memcpy(lmk_cov + 9 * (size_t)i, &lo[9 * (size_t)(rq->n_lmk < 0 ? i : rq->lmk[i])], 72);
+    if (n_lmk_singular) {
+        int n_sing = 0;
+        for (int i = 0; i < R.n_lmk_out; i++) n_sing += st[rq->n_lmk < 0 ? i : rq->lmk[i]] == COV_LMK_SINGULAR ? 1 : 0;
+        *n_lmk_singular = n_sing;
+    }
+    return SADVIO_OK;
+}
+
 // 5. One wait; the caller's blocks are picked from Sigma_pp and the landmark table on the host
 int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const CovRoutes& R, double* kf_cov, double* pair_cov, double* lmk_cov,
                   int32_t* n_lmk_singular) {
     const WinDev& d = h->plan.wins[w].d;
     CovScratch& V = h->cv;
     const int n = R.Np, dpf = d.dpf;
+    if (R.band) return cov_read_back_band(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
     std::vector<double>& sig = V.h_sig; std::vector<double>& lo = V.h_lout;
     const bool want_pp = n > 0 && ((kf_cov && rq->n_kf > 0) || (pair_cov && rq->n_pair > 0));
     int n_sing = 0;

@@ -13,7 +13,8 @@
 //                   observing free key-frame, W (3 x 6) and sum Jp^T Jp (6 x 6), stored compactly at the landmark's observation range
 //   k_cov_schur     one workgroup per pair of free key-frames: the 6 x 6 block of S, summed over the landmarks in a FIXED order
 //                   (thread-strided partial sums, then a workgroup tree) — no floating-point atomics anywhere in this file, so that two
-//                   calls give the same bits
+//                   calls give the same bits. On the band route (cov_band_kernels.h) the pair comes from a table of the in-band
+//                   pairs instead of blockIdx: the same sums for fewer pairs
 //   k_cov_kept      rows / columns of the landmarks kept in the reduced system (one workgroup, observation after observation)
 //   k_cov_factors   PosePriordx, IMUFactor + IMUBiasFactor and the listed sparse-prior factors through the evaluators of
 //                   device_math.h / kernels.h (pose_prior_factor, imu_factor_body, sparse_eval): one workgroup, factor after factor
@@ -49,6 +50,7 @@ struct CovDev {
     double* S;               // [Np][Np] full symmetric
     const double* Sig;       // [Np][Np] Sigma_pp
     double* lout;            // [n_lmk][9]
+    const int* pair_tab;     // band route: [workgroups of k_cov_schur][2] the in-band key-frame pairs (a, b), a >= b; else null
 };
 
 __global__ void k_cov_tables(DevPtrs P, CovDev C, double* ptab) {
@@ -187,9 +189,13 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_assemble(DevPtrs P, CovDev 
 // The 6 x 6 pose block (a, b), a >= b, of S over the visual factors: sum_l [a == b] sum Jp^T Jp - W_a^T H_ll W_b.
 __global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur(DevPtrs P, CovDev C) {
     const WinDev W = P.win[C.w];
-    int a = 0;
-    while ((a + 1) * (a + 2) / 2 <= (int)blockIdx.x) a++;
-    const int b = (int)blockIdx.x - a * (a + 1) / 2;
+    int a = 0, b;
+    if (C.pair_tab) {   // band route: the pair comes from the table of in-band pairs
+        a = C.pair_tab[2 * blockIdx.x]; b = C.pair_tab[2 * blockIdx.x + 1];
+    } else {
+        while ((a + 1) * (a + 2) / 2 <= (int)blockIdx.x) a++;
+        b = (int)blockIdx.x - a * (a + 1) / 2;
+    }
     const int ca = a * W.dpf, cb = b * W.dpf;
     double acc[36];
 #pragma unroll

@@ -74,6 +74,27 @@ void launch_wfac(sadvio_ba_handle* h, double* A, long long ld, int N, double* y,
     }
 }
 
+// Rows below a block column of window w's S that can be non-zero, (hb + 1) * dpf: hb is the largest distance in free key-frame
+// index that a landmark, an IMU pair or a relative-pose factor of the sparsified prior couples. N_p for a window whose reduced system
+// keeps landmarks, carries a dense prior or has line landmarks (those fill S). One rule for the solve's band routes (plan_solve)
+// and the covariance's (cov_driver.h). hb_out: hb, where the rule applies.
+int window_bandwidth(const sadvio_ba_handle* h, int w, int* hb_out = nullptr) {
+    const WinDev& d = h->plan.wins[w].d;
+    int hb = h->plan.wins[w].hb_lmk;
+    for (const ImuDev& f : h->imus_per_win[w]) {
+        const int fi = h->plan.kf_fidx[f.kf_i], fj = h->plan.kf_fidx[f.kf_j];
+        if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
+    }
+    if (w < (int)h->sparse_per_win.size())
+        for (const sadvio_sparse_prior& sp : h->sparse_per_win[w])
+            if (sp.type == SADVIO_SPARSE_RELATIVE_POSE) {     // a relative-pose factor couples its two key-frames
+                const int fi = h->plan.kf_fidx[d.kf_base + sp.kf], fj = h->plan.kf_fidx[d.kf_base + sp.kf_b];
+                if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
+            }
+    if (hb_out) *hb_out = hb;
+    return (d.n_red > 0 || d.dp_n_full > 0 || d.line_end > d.line_begin) ? d.Np : std::min(d.Np, (hb + 1) * d.dpf);
+}
+
 // The reduced system of an out-of-LDS window (N_p > MAX_LDS_NP) is factored and solved in HBM by one of five routes (dense_chol.h),
 // chosen once per solve call (BigPlan::choose).
 enum class BigRoute {
@@ -391,18 +412,7 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
         if (!d.ld) continue;
         BigPlan& p = big[w];
         p.Np = d.Np; p.ld = d.ld; p.dpf = d.dpf; p.red_off = d.red_off; p.S_off = d.S_off;
-        int hb = h->plan.wins[w].hb_lmk;
-        for (const ImuDev& f : h->imus_per_win[w]) {
-            const int fi = h->plan.kf_fidx[f.kf_i], fj = h->plan.kf_fidx[f.kf_j];
-            if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
-        }
-        if (w < (int)h->sparse_per_win.size())
-            for (const sadvio_sparse_prior& sp : h->sparse_per_win[w])
-                if (sp.type == SADVIO_SPARSE_RELATIVE_POSE) {     // a relative-pose factor couples its two key-frames
-                    const int fi = h->plan.kf_fidx[d.kf_base + sp.kf], fj = h->plan.kf_fidx[d.kf_base + sp.kf_b];
-                    if (fi >= 0 && fj >= 0) hb = std::max(hb, std::abs(fi - fj));
-                }
-        p.bw = (d.n_red > 0 || d.dp_n_full > 0 || d.line_end > d.line_begin) ? d.Np : std::min(d.Np, (hb + 1) * d.dpf);
+        p.bw = window_bandwidth(h, w);
     }
     if (h->coll_fn && h->world > 1 && h->plan.n_big) {
         // every rank must factor the all-reduced S with the same (largest) bandwidth: gather the local ones
