@@ -676,7 +676,24 @@ typedef struct sadvio_cov_request {
  * Environment variable SADVIO_COV_BAND, read when the handle is created: unset, a bandable window takes the band route only where
  * the call was refused before (N_p >= 2047), so no window served before changes a bit; 1, every bandable window takes it (tests,
  * A/B timing); 0, never (the 2047-column refusal included). In sadvio_ba_get_kernel_times the route shows as the classes cov_band
- * (forward sweep), cov_band_sel (backward sweep), cov_band_pairs and cov_band_gather in place of cov_invert. */
+ * (forward sweep), cov_band_sel (backward sweep), cov_band_pairs and cov_band_gather in place of cov_invert.
+ * The square-root assembly. A landmark millimetres from a camera centre puts 1e12 and more into H_pp beside entries of S of 1e10;
+ * S = H_pp - sum_l H_pl H_ll^-1 H_lp then loses its digits to the subtraction (5e-4 of relative error in a key-frame block at 1 mm)
+ * and comes out indefinite at 0.1 mm. The second assembly forms the same S and landmark blocks without that difference: per
+ * eliminated landmark J_l = Q1 R (Gram-Schmidt with a second orthogonalisation pass), C_a = Q1^T J_p,a per observing free key-frame,
+ * the landmark's share of block (a, b) of S as the sum over its rows of A_a^T A_b with A_a = [row is a's] J_p,a - Q1 C_a (the pose rows
+ * projected on the complement of range(J_l), then squared), and Sigma_ll = R^-1 (I + C Sigma_pp C^T) R^-T. It stays at the float64
+ * floor whatever the landmark's depth, S cannot come out indefinite and Sigma_ll is positive semi-definite by construction. The
+ * singular-landmark rule is the one above stated through R (fewer than two observations, or r_ii^2 <= 64 eps |column i of J_l|^2); the
+ * other terms of S, the inversion (dense or band route), the pivot tests, the fixed order of every sum and the bit guarantees above are
+ * unchanged.
+ * Environment variable SADVIO_COV_SQRT, read when the handle is created: unset, the plain assembly runs first, and only when the
+ * pivot tests refuse its S (either route) the call assembles again in square-root form, inverts and tests again, and returns
+ * SADVIO_E_NOT_USABLE only if that fails too — the outputs stay untouched until a form has passed, no window served before changes a
+ * bit, and a window refused before pays one more assembly (and one further wait) before the same refusal; 1, the square-root
+ * assembly from the start (any front-end that does not cull landmarks closer than a few centimetres: the plain form's loss is silent
+ * before it is refused); 0, never. In sadvio_ba_get_kernel_times the assembly shows as the class cov_assemble_sqrt in place of
+ * cov_assemble (after a retry, both). */
 int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_request *rq, double *kf_cov, double *pair_cov,
                          double *lmk_cov, int32_t *n_lmk_singular);
 
@@ -698,6 +715,11 @@ int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_reques
  * route. The LDS and NONE items are processed in groups of windows whose work arrays stay under 1 GiB
  * (SADVIO_COV_BATCH_SCRATCH_MB overrides the figure; a window larger than the budget is a group of its own); the grouping does not
  * change a bit of the results.
+ * The square-root assembly (sadvio_ba_covariance, SADVIO_COV_SQRT): DENSE and BAND items go through the single call's steps and
+ * inherit its choice of assembly and its retry. With SADVIO_COV_SQRT=1 the LDS items are sent down the DENSE route (as
+ * SADVIO_COV_BATCH_LDS=0 does) and a NONE item's landmark blocks are R^-1 R^-T. With the variable unset, an LDS item that would get
+ * SADVIO_E_NOT_USABLE is first retried on its own through the single call's steps in square-root form (one further wait per such
+ * item); the bits of items that were served before do not change.
  * Unlike sadvio_ba_covariance, the call accepts a batch the throughput kernels solved (65 536 landmarks or more).
  * status (out) is SADVIO_OK, or SADVIO_E_NOT_USABLE for an item whose S has a pivot that is not safely positive (not finite, not
  * above 1e-12 / N_p, or below 1024 N_p eps of its diagonal entry of S: gauge not fixed). Such an item's outputs are untouched, the

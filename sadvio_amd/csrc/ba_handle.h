@@ -202,6 +202,11 @@ struct CovScratch {
     DevBuf<double> Lb, Linv, X, gout;
     DevBuf<int> pair_tab, gtab, xcol, bflag;
     std::vector<int> h_pair_tab, h_gtab, h_xcol;
+    // the square-root assembly (cov_kernels.h: k_cov_assemble_sqrt): J_p and Q1 rows and the entry of every observation | the
+    // key-frame -> landmark lists (cov_kf_lists.h)
+    DevBuf<double> sq_jp, sq_q;
+    DevBuf<int> sq_ent, kf_ptr, kf_lmk;
+    std::vector<int> h_kf_ptr, h_kf_lmk;
 };
 
 // Work buffers of sadvio_ba_covariance_batch (cov_batch_driver.h). The pools hold the work arrays (pool, ipool) and the results (rpool)
@@ -244,6 +249,7 @@ struct EnvCfg {
     int tile_rounds = 0, lm_subs = 0, band_c = 0;   // 0: not set
     int cov_batch_lds = 1, cov_batch_scratch_mb = 1024;   // sadvio_ba_covariance_batch: the in-LDS inverse (0: every item down the dense route, A/B) | scratch budget of one group
     int cov_band = -1;   // covariance, the band route (cov_band_kernels.h): -1 not set: only where the call was refused before (N_p >= 2047) | 1: every bandable window | 0: never
+    int cov_sqrt = -1;   // covariance, the square-root assembly (cov_kernels.h): -1 not set: only after the pivot tests refused the plain form | 1: from the start | 0: never
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {
@@ -252,7 +258,7 @@ struct EnvCfg {
         debug = num("SADVIO_DEBUG", 0); lm = num("SADVIO_LM", -1); pf_wg = num("SADVIO_PF_WG", -1);
         tile_rounds = num("SADVIO_TILE_ROUNDS", 0); lm_subs = num("SADVIO_LM_SUBS", 0); band_c = num("SADVIO_BAND_C", 0);
         cov_batch_lds = num("SADVIO_COV_BATCH_LDS", 1); cov_batch_scratch_mb = num("SADVIO_COV_BATCH_SCRATCH_MB", 1024);
-        cov_band = num("SADVIO_COV_BAND", -1);
+        cov_band = num("SADVIO_COV_BAND", -1); cov_sqrt = num("SADVIO_COV_SQRT", -1);
         if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);
         marg_pivoted = on("SADVIO_MARG_PIVOTED"); marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");

@@ -7,6 +7,10 @@
 // pinned host memory with one asynchronous copy, and the call waits once, after the last group. A unit above the cap (route DENSE)
 // goes item by item through cov_driver.h's steps as they are, with the wait that route has; so does a unit on the band route (route
 // BAND, cov_driver.h: cov_band_route), whatever its N_p.
+// The square-root assembly (cov_driver.h: cov_steps, SADVIO_COV_SQRT) exists on the single call's steps only. DENSE and BAND items
+// inherit its choice and its retry. With the variable = 1 the LDS items go down the DENSE route and the NONE items through the same
+// steps; with it unset, an LDS item whose unit failed the pivot test is retried on its own through those steps in square-root form
+// behind the call's wait (covb_retry_item), and items that were served keep their bits.
 //
 // After a solve by the throughput kernels (lm_kernels.h). sadvio_ba_covariance refuses such a batch; this call accepts it, on these
 // grounds. (i) Both solve paths keep two delta buffers per array and LmState::cur names the one holding the accepted state x: k_solve
@@ -61,6 +65,12 @@ int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* ite
     return SADVIO_OK;
 }
 
+// Does item I go through the single call's steps (cov_driver.h: cov_steps)? The DENSE and BAND routes; under SADVIO_COV_SQRT=1 a
+// NONE item too, for the landmark-block formula of the square-root assembly.
+bool covb_single(const sadvio_ba_handle* h, const sadvio_cov_batch_item& I) {
+    return I.route == SADVIO_COV_ROUTE_DENSE || I.route == SADVIO_COV_ROUTE_BAND || (I.route == SADVIO_COV_ROUTE_NONE && h->env.cov_sqrt == 1);
+}
+
 // 2. The route of every item; one unit per window that does not take the dense route
 void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, std::vector<CovbUnit>& units, std::vector<int>& unit_of) {
     std::vector<int> of_win(h->plan.wins.size(), -1);
@@ -69,9 +79,10 @@ void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, 
         sadvio_cov_batch_item& I = items[it];
         const WinDev& d = h->plan.wins[I.w].d;
         I.status = SADVIO_OK; I.n_lmk_singular = 0;
-        I.route = d.Np == 0 ? SADVIO_COV_ROUTE_NONE : (d.Np <= COVB_CAP && h->env.cov_batch_lds != 0 ? SADVIO_COV_ROUTE_LDS : SADVIO_COV_ROUTE_DENSE);
+        const bool lds = h->env.cov_batch_lds != 0 && h->env.cov_sqrt != 1;   // (the square-root assembly has no group kernels: its items go one by one)
+        I.route = d.Np == 0 ? SADVIO_COV_ROUTE_NONE : (d.Np <= COVB_CAP && lds ? SADVIO_COV_ROUTE_LDS : SADVIO_COV_ROUTE_DENSE);
         if (cov_band_route(h, I.w)) I.route = SADVIO_COV_ROUTE_BAND;   // (cov_driver.h: by default only a window the dense route refuses)
-        if (I.route == SADVIO_COV_ROUTE_DENSE || I.route == SADVIO_COV_ROUTE_BAND) continue;
+        if (covb_single(h, I)) continue;
         const CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
         if (of_win[I.w] < 0) {
             of_win[I.w] = (int)units.size();
@@ -87,21 +98,22 @@ void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, 
     }
 }
 
-// An item above the cap: the steps of sadvio_ba_covariance, unchanged (cov_check's tests were made for every item by covb_check)
+// An item above the cap: the steps of sadvio_ba_covariance, unchanged, with their choice of assembly and their retry (cov_check's
+// tests were made for every item by covb_check)
 int covb_dense_item(sadvio_ba_handle* h, sadvio_cov_batch_item& I) {
-    const CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
-    if (int rc = cov_assemble(h, I.w, R)) return rc;
-    bool usable = true;
-    if (int rc = cov_invert(h, R, usable)) return rc;
-    if (!usable) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->cfg.profile_kernels) collect_timers(h);
-        I.status = SADVIO_E_NOT_USABLE;
-        return SADVIO_OK;
-    }
-    if (int rc = cov_landmarks(h, I.w, R)) return rc;
-    const int rc = cov_read_back(h, I.w, &I.rq, R, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
-    if (rc == SADVIO_E_NOT_USABLE && R.band) { I.status = SADVIO_E_NOT_USABLE; return SADVIO_OK; }   // the band route's pivot flag comes with the wait
+    const int rc = cov_steps(h, I.w, &I.rq, cov_routes(h, I.w, &I.rq, I.lmk_cov), I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
+    if (rc == SADVIO_E_NOT_USABLE) { I.status = SADVIO_E_NOT_USABLE; return SADVIO_OK; }
+    return rc;
+}
+
+// An LDS item whose unit failed the pivot test, SADVIO_COV_SQRT unset: once more on its own through the single call's steps with the
+// square-root assembly, before SADVIO_E_NOT_USABLE is written
+int covb_retry_item(sadvio_ba_handle* h, sadvio_cov_batch_item& I) {
+    CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
+    R.sqrt = true;
+    const int rc = cov_attempt(h, I.w, &I.rq, R, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
+    if (rc == SADVIO_E_NOT_USABLE) return SADVIO_OK;
+    if (rc == SADVIO_OK) I.status = SADVIO_OK;
     return rc;
 }
 
@@ -270,7 +282,7 @@ int covb_run(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items) {
     std::vector<int> unit_of;
     covb_routes(h, n_item, items, units, unit_of);
     for (int it = 0; it < n_item; it++)
-        if (items[it].route == SADVIO_COV_ROUTE_DENSE || items[it].route == SADVIO_COV_ROUTE_BAND)
+        if (covb_single(h, items[it]))
             if (int rc = covb_dense_item(h, items[it])) return rc;
     if (units.empty()) return SADVIO_OK;
     std::vector<CovbGroup> groups;
@@ -284,7 +296,12 @@ int covb_run(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items) {
         if (int rc = covb_invert(h, units, g, d_units)) return rc;
         if (int rc = covb_landmarks(h, units, g, P, d_units)) return rc;
     }
-    return covb_read_back(h, n_item, items, units, unit_of);
+    if (int rc = covb_read_back(h, n_item, items, units, unit_of)) return rc;
+    if (h->env.cov_sqrt != 0)
+        for (int it = 0; it < n_item; it++)
+            if (unit_of[it] >= 0 && items[it].status == SADVIO_E_NOT_USABLE)
+                if (int rc = covb_retry_item(h, items[it])) return rc;
+    return SADVIO_OK;
 }
 
 }  // namespace

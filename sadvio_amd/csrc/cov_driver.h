@@ -4,6 +4,8 @@
 // BAND route; cov_band_route says when). On the band route k_cov_schur runs over the table of in-band key-frame pairs, no kernel
 // reads an entry of Sigma outside the band, pair blocks outside the band come from band substitution, and the host receives the
 // blocks asked for and nothing else.
+// S and the landmark blocks have two assemblies: the plain one (cov_assemble) and the square-root one (cov_assemble_sqrt), which
+// survives landmarks millimetres from a camera centre; cov_steps says which runs (SADVIO_COV_SQRT) and holds the retry.
 // The kernels are cov_kernels.h's; the factorisation of S and the triangular inverse are marg_driver.h's (factor_unpivoted,
 // prior_build_Z: the route sadvio_ba_sparsify takes to Sigma_k = Ak^-1), called as they are. Nothing of the solve is touched: the
 // delta buffers, the final records, the trace and the handle's prior are read only; the work buffers are the handle's CovScratch
@@ -13,6 +15,7 @@
 #include "ba_handle.h"
 #include "cov_band_kernels.h"
 #include "cov_kernels.h"
+#include "cov_kf_lists.h"
 #include "marg_driver.h"
 
 namespace {
@@ -29,6 +32,7 @@ struct CovRoutes {
     int n_lmk_out = 0;      // landmark blocks written
     bool band = false;      // the band route; then hb / bw / nb: block half-bandwidth, (hb + 1) * dpf, block column of the sweeps
     int hb = 0, bw = 0, nb = 0, dpf = 6;
+    bool sqrt = false;      // the square-root assembly (cov_assemble_sqrt) instead of the plain one
 };
 
 // The band route's block column: 6 for dpf 6, 5 for dpf 15 (as k_band_solve)
@@ -142,6 +146,60 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     return SADVIO_OK;
 }
 
+// 2 (square-root assembly). The same S in Gram form: per eliminated landmark J_l = Q1 R, C_a = Q1^T J_p,a, and block (a, b) of S the
+// sum over the landmark's rows of A_a^T A_b, A_a = [row is a's] J_p,a - Q1 C_a (cov_kernels.h) — never a difference of two large
+// matrices, so a landmark millimetres from a camera centre cannot turn S indefinite. The pair workgroups walk key-frame -> landmark
+// lists built here from the plan's observation lists and uploaded with the call. Shows as the class cov_assemble_sqrt.
+int cov_assemble_sqrt(sadvio_ba_handle* h, int w, const CovRoutes& R) {
+    const WinDev& d = h->plan.wins[w].d;
+    CovScratch& V = h->cv;
+    const size_t nl = (size_t)std::max(d.n_lmk, 1), no = (size_t)std::max(d.n_obs, 1), nn = (size_t)std::max(R.Np, 1) * std::max(R.Np, 1);
+    HIP_TRY(V.ptab.alloc((size_t)h->plan.n_kf_tot * POSE_TAB));
+    HIP_TRY(V.hll.alloc(6 * nl)); HIP_TRY(V.hinv.alloc(6 * nl)); HIP_TRY(V.status.alloc(nl)); HIP_TRY(V.ent_n.alloc(nl)); HIP_TRY(V.lout.alloc(9 * nl));
+    HIP_TRY(V.ent_col.alloc(no)); HIP_TRY(V.ent_w.alloc(COV_ENT_W * no));
+    HIP_TRY(V.sq_jp.alloc(12 * no)); HIP_TRY(V.sq_q.alloc(6 * no)); HIP_TRY(V.sq_ent.alloc(no));
+    HIP_TRY(V.S.alloc(nn)); HIP_TRY(V.Sig.alloc(nn));
+    HIP_TRY(hipMemsetAsync(V.S.p, 0, sizeof(double) * nn, h->stream));
+    SolveOpts so{};
+    so.huber_a = h->cov_huber_a;
+    const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
+    int n_schur = d.n_free_kf * (d.n_free_kf + 1) / 2;
+    if (R.band && R.Np > 0) {
+        std::vector<int>& tab = V.h_pair_tab;
+        tab.clear();
+        for (int a = 0; a < d.n_free_kf; a++)
+            for (int b = std::max(0, a - R.hb); b <= a; b++) { tab.push_back(a); tab.push_back(b); }
+        n_schur = (int)tab.size() / 2;
+        HIP_TRY(V.pair_tab.alloc(tab.size()));
+        HIP_TRY(hipMemcpyAsync(V.pair_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
+    }
+    cov_kf_lmk_lists(d.n_free_kf, d.n_lmk, h->plan.lmk_ob.data() + d.lmk_base, h->plan.lmk_oe.data() + d.lmk_base, h->plan.obs_kf.data(),
+                     h->plan.kf_fidx.data(), V.h_kf_ptr, V.h_kf_lmk);
+    HIP_TRY(V.kf_ptr.alloc(V.h_kf_ptr.size())); HIP_TRY(V.kf_lmk.alloc(V.h_kf_lmk.size()));
+    HIP_TRY(hipMemcpyAsync(V.kf_ptr.p, V.h_kf_ptr.data(), sizeof(int) * V.h_kf_ptr.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(V.kf_lmk.p, V.h_kf_lmk.data(), sizeof(int) * V.h_kf_lmk.size(), hipMemcpyHostToDevice, h->stream));
+    const CovDev C = cov_dev(h, w, R);
+    const CovSqrtDev Q{V.sq_jp.p, V.sq_q.p, V.sq_ent.p, V.kf_ptr.p, V.kf_lmk.p};
+    ScopedTimer t(h, "cov_assemble_sqrt");
+    const int n_tab = std::max(d.n_kf, d.n_lmk);
+    hipLaunchKernelGGL(k_cov_tables, dim3((n_tab + 255) / 256), dim3(256), 0, h->stream, P, C, V.ptab.p);
+    const int n_tiles = d.tile_end - d.tile_begin;
+    if (n_tiles > 0) hipLaunchKernelGGL(R.pix ? k_cov_assemble_sqrt<0> : k_cov_assemble_sqrt<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C, Q);
+    if (R.Np == 0) { HIP_TRY(hipGetLastError()); return SADVIO_OK; }
+    if (d.n_free_kf > 0) {
+        ScopedTimer ts(h, R.band ? "k_cov_schur_sqrt" : nullptr);
+        hipLaunchKernelGGL(k_cov_schur_sqrt, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C, Q);
+    }
+    if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
+    {
+        ScopedTimer tf(h, R.band ? "k_cov_factors" : nullptr);
+        hipLaunchKernelGGL(k_cov_factors, dim3(1), dim3(64), 0, h->stream, P, C);
+    }
+    if (R.dense) hipLaunchKernelGGL(k_cov_dense, dim3((unsigned)(((long long)d.dp_n * d.dp_n + 255) / 256)), dim3(256), 0, h->stream, P, C);
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
 // 3. Sigma_pp = S^-1: unpivoted Cholesky with every pivot tested, triangular inverse Z = G^-T, Sigma_pp = Z^T Z.
 // usable = false: a pivot is not safely positive (gauge not fixed).
 CovBand cov_band_dev(sadvio_ba_handle* h, const CovRoutes& R) {
@@ -207,7 +265,8 @@ int cov_landmarks(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     const CovDev C = cov_dev(h, w, R);
     const int per = COV_THREADS / R.G;
     ScopedTimer t(h, "k_cov_lmk");
-    hipLaunchKernelGGL(R.G == 16 ? k_cov_lmk<16> : k_cov_lmk<64>, dim3((d.n_lmk + per - 1) / per), dim3(COV_THREADS), 0, h->stream, P, C);
+    if (R.sqrt) hipLaunchKernelGGL((R.G == 16 ? k_cov_lmk<16, true> : k_cov_lmk<64, true>), dim3((d.n_lmk + per - 1) / per), dim3(COV_THREADS), 0, h->stream, P, C);
+    else hipLaunchKernelGGL(R.G == 16 ? k_cov_lmk<16> : k_cov_lmk<64>, dim3((d.n_lmk + per - 1) / per), dim3(COV_THREADS), 0, h->stream, P, C);
     HIP_TRY(hipGetLastError());
     return SADVIO_OK;
 }
@@ -321,11 +380,10 @@ int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, cons
     return SADVIO_OK;
 }
 
-int cov_run(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov, int32_t* n_lmk_singular) {
-    if (int rc = cov_check(h, w, rq, lmk_cov)) return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    const CovRoutes R = cov_routes(h, w, rq, lmk_cov);
-    if (int rc = cov_assemble(h, w, R)) return rc;
+// Steps 2 to 5 with the assembly R names. SADVIO_E_NOT_USABLE: a pivot of S failed its test; the outputs are untouched.
+int cov_attempt(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const CovRoutes& R, double* kf_cov, double* pair_cov, double* lmk_cov,
+                int32_t* n_lmk_singular) {
+    if (int rc = R.sqrt ? cov_assemble_sqrt(h, w, R) : cov_assemble(h, w, R)) return rc;
     bool usable = true;
     if (int rc = cov_invert(h, R, usable)) return rc;
     if (!usable) {
@@ -336,6 +394,27 @@ int cov_run(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, double* kf
     }
     if (int rc = cov_landmarks(h, w, R)) return rc;
     return cov_read_back(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+}
+
+// The assembly of a call (SADVIO_COV_SQRT, read once in EnvCfg). Unset: the plain one, and only when the pivot tests refuse its S
+// (behind the call's wait on either route) the square-root one, with a second inversion, a second test and one further wait; a window
+// the plain form serves keeps its bits, a refused one pays one more assembly before the same refusal. 1: square-root from the
+// start. 0: plain only.
+int cov_steps(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, CovRoutes R, double* kf_cov, double* pair_cov, double* lmk_cov,
+              int32_t* n_lmk_singular) {
+    R.sqrt = h->env.cov_sqrt == 1;
+    int rc = cov_attempt(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+    if (rc == SADVIO_E_NOT_USABLE && !R.sqrt && h->env.cov_sqrt != 0) {
+        R.sqrt = true;
+        rc = cov_attempt(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+    }
+    return rc;
+}
+
+int cov_run(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov, int32_t* n_lmk_singular) {
+    if (int rc = cov_check(h, w, rq, lmk_cov)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    return cov_steps(h, w, rq, cov_routes(h, w, rq, lmk_cov), kf_cov, pair_cov, lmk_cov, n_lmk_singular);
 }
 
 }  // namespace

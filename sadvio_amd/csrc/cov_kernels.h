@@ -20,6 +20,9 @@
 //                   device_math.h / kernels.h (pose_prior_factor, imu_factor_body, sparse_eval): one workgroup, factor after factor
 //   k_cov_dense     the dense prior's J^T J (WinDev::dp_off: H, formed at upload) through its column map
 //   k_cov_lmk       the landmark blocks: one landmark per group of G lanes (below)
+// S and the landmark blocks have a second assembly, the square-root one (k_cov_assemble_sqrt, k_cov_schur_sqrt, k_cov_lmk<G, true>,
+// further down): the same quantities without the difference above, for windows with landmarks millimetres from a camera centre.
+// cov_driver.h (cov_steps) says which runs. The kernels of the plain assembly are untouched by it.
 // A landmark whose H_ll is not positive definite (one observation; a pivot within 64 ulps of its diagonal entry) is left out of H
 // together with its observations and reported as singular. Part of the library's single translation unit; not a public header.
 #pragma once
@@ -253,6 +256,180 @@ __global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur(DevPtrs P, CovD
     }
 }
 
+// ---- the square-root assembly ----------------------------------------------------------------------------------------------------
+// The same S and landmark blocks without the difference H_pp - W^T H_ll W: a landmark millimetres from a camera centre puts 1e12
+// and more into H_pp beside entries of S of 1e10, and the plain form then loses S to rounding ("Near-camera landmarks").
+// Per eliminated landmark J_l (2m x 3) = Q1 R; C_a = Q1^T J_p,a; its share of block (a, b) of S is the Gram sum
+//   sum_r A_a[r]^T A_b[r],   A_a[r] = [row r is a's] J_p,a[r] - Q1[r] C_a      (the pose rows projected on the complement of range(J_l))
+// over all 2m rows, and Sigma_ll = R^-1 (I + C Sigma_pp C^T) R^-T. Nothing is subtracted from anything large, S cannot come out
+// indefinite, and Sigma_ll is positive semi-definite by construction. A landmark that is not eliminated has Q1 = 0, C = 0 and the
+// same sum is its J_p^T J_p. k_cov_kept / k_cov_factors / k_cov_dense add their terms as on the plain route.
+//
+// k_cov_assemble_sqrt: k_cov_assemble's shape (a workgroup per tile, a thread per landmark). Q1 by Gram-Schmidt column after column
+// with a second orthogonalisation pass (orthonormal to a few ulps while cond(J_l) eps < 1; R = chol(H_ll) would lose it with
+// cond(H_ll)), in place on the landmark's rows of CovSqrtDev::q. Singular: fewer than two observations, or r_ii^2 <= 64 eps |column i|^2 —
+// cov_sym3_inverse's pivot rule stated through R.
+// What the square-root assembly keeps beside CovDev (a kernel argument of its own: CovDev and with it the plain assembly's kernels stay
+// as they are). On this route CovDev::hll holds R (upper: 00 01 02 11 12 22) and CovDev::ent_w the couplings C_a (3 x 6).
+struct CovSqrtDev {
+    double* jp;              // [n_obs][12] the two J_p rows of every observation
+    double* q;               // [n_obs][6] the two rows of Q1 (zero for a landmark that is not eliminated)
+    int* ent;                // [n_obs] entry of the observation's key-frame among its landmark's entries, -1: constant key-frame
+    const int* kf_ptr;       // [n_free_kf + 1] CSR of the landmarks every free key-frame observes (cov_kf_lists.h) ...
+    const int* kf_lmk;       // ... window landmark indices, ascending
+};
+
+template <int FACTOR>
+__global__ __launch_bounds__(COV_THREADS) void k_cov_assemble_sqrt(DevPtrs P, CovDev C, CovSqrtDev Q1) {
+    const WinDev W = P.win[C.w];
+    const Tile T = P.tiles[W.tile_begin + blockIdx.x];
+    for (int i = threadIdx.x; i < T.n_lmk; i += blockDim.x) {
+        const int gl = tile_landmark(T, P.tile_lmk, i);
+        const int l = gl - W.lmk_base;
+        if (l < 0 || l >= W.n_lmk) continue;
+        const int ob = P.lmk_ob[gl], oe = P.lmk_oe[gl];
+        const long long e0 = ob - W.obs_base;
+        const double* xl = P.xl + (long long)C.cur * P.xl_stride + 3 * (long long)gl;
+        const double pw[3] = {P.lmk_p[3 * (long long)gl] + xl[0], P.lmk_p[3 * (long long)gl + 1] + xl[1], P.lmk_p[3 * (long long)gl + 2] + xl[2]};
+        const int lc = P.lmk_const ? P.lmk_const[gl] : 0;
+        int status = lc == 1 ? COV_LMK_CONST : (lc == 2 ? COV_LMK_REDUCED : COV_LMK_ELIMINATED);
+        const bool elim = status == COV_LMK_ELIMINATED;
+        double* Q = Q1.q + 6 * e0;         // row r of the landmark at Q[3 r]
+        double* JP = Q1.jp + 12 * e0;      // row r at JP[6 r]
+        int* EN = Q1.ent + e0;
+        const int rows = 2 * (oe - ob);
+        double cn[3] = {0.0, 0.0, 0.0};    // |column|^2 of J_l
+        int n = 0;
+        for (int o = ob; o < oe; o++) {
+            double Jp[12], Jl[6];
+            cov_obs_jacobians<FACTOR>(P, C, o, pw, Jp, Jl);
+            for (int q = 0; q < 12; q++) JP[12 * (o - ob) + q] = Jp[q];
+            for (int q = 0; q < 6; q++) Q[6 * (o - ob) + q] = elim ? Jl[q] : 0.0;
+            for (int c = 0; c < 3; c++) cn[c] += Jl[c] * Jl[c] + Jl[3 + c] * Jl[3 + c];
+            const int fi = P.kf_fidx[P.obs_kf[o]];
+            if (fi < 0) { EN[o - ob] = -1; continue; }
+            const int col = fi * W.dpf;
+            int e = 0;
+            while (e < n && C.ent_col[e0 + e] != col) e++;
+            EN[o - ob] = e;
+            if (e == n) {
+                n++;
+                C.ent_col[e0 + e] = col;
+                double* c18 = C.ent_w + (e0 + e) * COV_ENT_W;
+                for (int q = 0; q < COV_ENT_W; q++) c18[q] = 0.0;
+            }
+        }
+        double R[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (elim) {
+            const double tol = 64.0 * 2.220446049250313e-16;
+            bool ok = oe - ob >= 2;
+            for (int j = 0; j < 3 && ok; j++) {
+                for (int pass = 0; pass < 2; pass++)
+                    for (int k = 0; k < j; k++) {
+                        double s = 0.0;
+                        for (int r = 0; r < rows; r++) s += Q[3 * r + k] * Q[3 * r + j];
+                        for (int r = 0; r < rows; r++) Q[3 * r + j] -= s * Q[3 * r + k];
+                        R[k == 0 ? j : 3 + j - 1] += s;   // (0, j) | (1, 2)
+                    }
+                double nn = 0.0;
+                for (int r = 0; r < rows; r++) nn += Q[3 * r + j] * Q[3 * r + j];
+                if (!(nn > tol * cn[j])) { ok = false; break; }
+                const double rjj = sqrt(nn);
+                R[j == 0 ? 0 : (j == 1 ? 3 : 5)] = rjj;
+                for (int r = 0; r < rows; r++) Q[3 * r + j] /= rjj;
+            }
+            if (!ok) { status = COV_LMK_SINGULAR; n = 0; }
+        }
+        if (status == COV_LMK_ELIMINATED)   // C_a = Q1^T J_p,a, observation after observation
+            for (int o = ob; o < oe; o++) {
+                const int e = EN[o - ob];
+                if (e < 0) continue;
+                double* c18 = C.ent_w + (e0 + e) * COV_ENT_W;
+                const double* q = Q + 6 * (o - ob);
+                const double* jp = JP + 12 * (o - ob);
+                for (int a = 0; a < 3; a++)
+                    for (int c = 0; c < 6; c++) c18[6 * a + c] += q[a] * jp[c] + q[3 + a] * jp[6 + c];
+            }
+        for (int q = 0; q < 6; q++) C.hll[6 * (long long)l + q] = R[q];
+        C.status[l] = status;
+        C.ent_n[l] = n;
+    }
+}
+
+// The 6 x 6 pose block (a, b), a >= b, of S over the visual factors in Gram form. The workgroup walks the landmarks key-frame a
+// observes (CovSqrtDev::kf_ptr / kf_lmk, ascending landmark index: a fixed order) and looks for b among each landmark's entries; the partial
+// sums and the tree are k_cov_schur's.
+__global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur_sqrt(DevPtrs P, CovDev C, CovSqrtDev Q1) {
+    const WinDev W = P.win[C.w];
+    int a = 0, b;
+    if (C.pair_tab) {
+        a = C.pair_tab[2 * blockIdx.x]; b = C.pair_tab[2 * blockIdx.x + 1];
+    } else {
+        while ((a + 1) * (a + 2) / 2 <= (int)blockIdx.x) a++;
+        b = (int)blockIdx.x - a * (a + 1) / 2;
+    }
+    const int ca = a * W.dpf, cb = b * W.dpf;
+    double acc[36];
+#pragma unroll
+    for (int q = 0; q < 36; q++) acc[q] = 0.0;
+    const int it1 = Q1.kf_ptr[a + 1];
+    for (int it = Q1.kf_ptr[a] + (int)threadIdx.x; it < it1; it += COV_SCHUR_THREADS) {
+        const int l = Q1.kf_lmk[it];
+        const int n = C.ent_n[l];
+        if (n == 0) continue;
+        const int ob = P.lmk_ob[W.lmk_base + l], oe = P.lmk_oe[W.lmk_base + l];
+        const long long e0 = ob - W.obs_base;
+        int ea = -1, eb = -1;
+        for (int e = 0; e < n; e++) {
+            const int col = C.ent_col[e0 + e];
+            if (col == ca) ea = e;
+            if (col == cb) eb = e;
+        }
+        if (ea < 0 || eb < 0) continue;
+        double Ca[18], Cb[18];
+#pragma unroll
+        for (int q = 0; q < 18; q++) { Ca[q] = C.ent_w[(e0 + ea) * COV_ENT_W + q]; Cb[q] = C.ent_w[(e0 + eb) * COV_ENT_W + q]; }
+        for (int o = ob; o < oe; o++) {
+            const long long x = e0 + (o - ob);
+            const int en = Q1.ent[x];
+            const double* jp = Q1.jp + 12 * x;
+            const double* q = Q1.q + 6 * x;
+#pragma unroll
+            for (int row = 0; row < 2; row++) {
+                const double q0 = q[3 * row], q1 = q[3 * row + 1], q2 = q[3 * row + 2];
+                double Aa[6], Ab[6];
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    const double j = jp[6 * row + i];
+                    Aa[i] = (en == ea ? j : 0.0) - (q0 * Ca[i] + q1 * Ca[6 + i] + q2 * Ca[12 + i]);
+                    Ab[i] = (en == eb ? j : 0.0) - (q0 * Cb[i] + q1 * Cb[6 + i] + q2 * Cb[12 + i]);
+                }
+#pragma unroll
+                for (int i = 0; i < 6; i++)
+#pragma unroll
+                    for (int j = 0; j < 6; j++) acc[6 * i + j] += Aa[i] * Ab[j];
+            }
+        }
+    }
+    __shared__ double sh[COV_SCHUR_THREADS * 36];
+#pragma unroll
+    for (int q = 0; q < 36; q++) sh[threadIdx.x * 36 + q] = acc[q];
+    __syncthreads();
+    for (int s = COV_SCHUR_THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int q = 0; q < 36; q++) sh[threadIdx.x * 36 + q] += sh[(threadIdx.x + s) * 36 + q];
+        __syncthreads();
+    }
+    if (threadIdx.x < 36) {
+        const int i = threadIdx.x / 6, j = threadIdx.x - 6 * i;
+        if (a == b) C.S[(long long)(ca + i) * C.Np + ca + j] = 0.5 * (sh[6 * i + j] + sh[6 * j + i]);
+        else {
+            C.S[(long long)(ca + i) * C.Np + cb + j] = sh[6 * i + j];
+            C.S[(long long)(cb + j) * C.Np + ca + i] = sh[6 * i + j];
+        }
+    }
+}
+
 // Landmarks kept in the reduced system: Jl^T Jl and Jl^T Jp of their observations (Jp^T Jp went through k_cov_schur).
 template <int FACTOR>
 __global__ __launch_bounds__(64) void k_cov_kept(DevPtrs P, CovDev C) {
@@ -408,7 +585,9 @@ __global__ void k_cov_dense(DevPtrs P, CovDev C) {
 // by a butterfly inside the group — a fixed order, the same bits on every call. Sigma_pp (218 KB on the shipped VIO window) does
 // not fit LDS and is read from global memory through the caches: a landmark with k observing key-frames reads k^2 blocks of
 // 6 rows x 48 contiguous bytes; the matrix stays resident in L2 (4 MB per XCD), so HBM sees it once per XCD.
-template <int G>
+// SQRT (the square-root assembly): ent_w holds C and hll holds R; the same gather gives C Sigma_pp C^T, and the block is
+// R^-1 (I + C Sigma_pp C^T) R^-T, its upper triangle computed and mirrored.
+template <int G, bool SQRT = false>
 __global__ __launch_bounds__(COV_THREADS) void k_cov_lmk(DevPtrs P, CovDev C) {
     const WinDev W = P.win[C.w];
     const int l = blockIdx.x * (COV_THREADS / G) + threadIdx.x / G;
@@ -453,7 +632,28 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_lmk(DevPtrs P, CovDev C) {
         for (int m = G / 2; m > 0; m >>= 1) acc[i] += __shfl_xor(acc[i], m, G);
     if (!have || q != 0) return;
     double* out = C.lout + 9 * (long long)l;
-    if (status == COV_LMK_ELIMINATED) {
+    if (SQRT && status == COV_LMK_ELIMINATED) {
+        const double* R = C.hll + 6 * (long long)l;
+        const double M[9] = {1.0 + acc[0], 0.5 * (acc[1] + acc[3]), 0.5 * (acc[2] + acc[6]), 0.0, 1.0 + acc[4], 0.5 * (acc[5] + acc[7]), 0.0, 0.0, 1.0 + acc[8]};
+        double U[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // R^-1, upper
+        U[0] = 1.0 / R[0]; U[4] = 1.0 / R[3]; U[8] = 1.0 / R[5];
+        U[1] = -R[1] * U[4] / R[0];
+        U[5] = -R[4] * U[8] / R[3];
+        U[2] = -(R[1] * U[5] + R[2] * U[8]) / R[0];
+        double Tm[9];   // U M, M symmetric
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                double v = 0.0;
+                for (int k = i; k < 3; k++) v += U[3 * i + k] * (k <= j ? M[3 * k + j] : M[3 * j + k]);
+                Tm[3 * i + j] = v;
+            }
+        for (int i = 0; i < 3; i++)
+            for (int j = i; j < 3; j++) {
+                double v = 0.0;
+                for (int k = j; k < 3; k++) v += Tm[3 * i + k] * U[3 * j + k];
+                out[3 * i + j] = v; out[3 * j + i] = v;
+            }
+    } else if (status == COV_LMK_ELIMINATED) {
         const double* Hi = C.hinv + 6 * (long long)l;
         const double s01 = 0.5 * (acc[1] + acc[3]), s02 = 0.5 * (acc[2] + acc[6]), s12 = 0.5 * (acc[5] + acc[7]);
         out[0] = Hi[0] + acc[0]; out[1] = Hi[1] + s01; out[2] = Hi[2] + s02;
