@@ -749,6 +749,59 @@ typedef struct sadvio_cov_batch_item {
 
 int sadvio_ba_covariance_batch(sadvio_ba_handle *h, int32_t n_item, sadvio_cov_batch_item *items);
 
+/* ---- key-frame x landmark cross covariances of a solved window, and the innovation gate of candidate observations ----
+ * Candidate i names key-frame kf[i] (a) and landmark lmk[i] (l) of window `w`. The call returns the cross block Sigma(a, l) of
+ * Sigma = H^-1 and, with a candidate camera and measurement, the innovation covariance of that observation
+ *   P = J_a Sigma_aa J_a^T + J_a Sigma_al J_l^T + J_l Sigma_la J_a^T + J_l Sigma_ll J_l^T + I
+ * and the squared Mahalanobis distance maha2 = r^T P^-1 r of its residual: the uncertainty-aware counterpart of
+ * sadvio_ba_landmark_chi2 (maha2 <= 5.99 gates a match at 95 %, two degrees of freedom).
+ * Same H as sadvio_ba_covariance: Gauss-Newton at the final accepted state of the last solve, that solve's Huber corrector on the
+ * window's own factors, the same free parameters, singular-landmark rule and delta coordinates; Sigma_al = -sum_e Sigma_pp(a, c_e)
+ * W_e^T over the landmark's observing free key-frames, in list order (square-root assembly: -(sum_e Sigma_pp(a, c_e) C_e^T) R^-T).
+ * The candidate's own residual r and Jacobians J_a (2 x 6, on the pose part of the key-frame's block: the IMU states contribute
+ * nothing), J_l (2 x 3) are the window's factor type (pixel or angular) evaluated at that state with the candidate's camera and
+ * measurement, whitened by the camera's cam_sigma — so the noise term of P is I — and carry NO robust loss.
+ *   constant key-frame        Sigma_al = 0 and P = J_l Sigma_ll J_l^T + I
+ *   constant landmark         Sigma_al = 0 and P = J_a Sigma_aa J_a^T + I
+ *   landmark kept in the reduced system   Sigma_al is read from Sigma_pp at the landmark's reduced columns
+ *   singular landmark         all three outputs NaN and status SADVIO_CROSS_LMK_SINGULAR (also with a constant key-frame); the
+ *                             call still returns SADVIO_OK
+ *   pixel window, the projection fails Camera::project's tests (depth below 0.1, outside the image)   status
+ *                             SADVIO_CROSS_PROJ_INVALID; r = 0 as in the solve, so maha2 = 0; P is still formed from the Jacobians
+ *                             the factor keeps
+ * Calling rules as for sadvio_ba_covariance: any output pointer may be NULL; innov_cov or maha2 non-NULL with cam == NULL is
+ * SADVIO_E_INVALID_ARG, as are cam without meas and a cam index out of the caller's camera range; n = 0 returns SADVIO_OK and touches
+ * nothing. The same refusals with the same error texts: SADVIO_E_STATE before a solve or inside a begin_update bracket;
+ * SADVIO_E_INVALID_ARG for an index out of range, a sharded handle, line landmarks, a batch the throughput kernels solved, a
+ * reduced system of 2047 columns or more that is not bandable; SADVIO_E_NOT_USABLE with the outputs untouched when the pivot tests
+ * refuse S. The call inherits the choice of assembly and the retry (SADVIO_COV_SQRT) and the route (SADVIO_COV_BAND) of
+ * sadvio_ba_covariance; on the band route the whole block row Sigma(a, :) of every distinct key-frame asked for is formed by band
+ * substitution and EVERY candidate is served from it, so a candidate's bits do not depend on where its observers lie; no entry of
+ * Sigma outside the band is read. The call waits once for its results (plus the waits sadvio_ba_covariance itself has).
+ * Every sum is taken in a fixed order, no floating-point atomics: two calls return the same bits, a candidate's bits depend neither
+ * on the other candidates nor on its position, the output order is the request order and repeats are allowed. The solve's deltas,
+ * summaries, trace, the handle's prior and every bit sadvio_ba_covariance / _batch return are left as they are.
+ * In sadvio_ba_get_kernel_times the step shows as the class cov_cross, on the band route also cov_band_rows. A block row of more
+ * than 16 384 doubles (d = 6: N_p > 2 730; d = 15: N_p > 1 092) is read from global memory instead of LDS; the environment variable
+ * SADVIO_COV_CROSS_STAGE (read when the handle is created) lowers that figure (tests). */
+#define SADVIO_CROSS_OK            0
+#define SADVIO_CROSS_LMK_SINGULAR  1
+#define SADVIO_CROSS_PROJ_INVALID  2
+
+typedef struct sadvio_cov_cross_request {
+    int32_t n;            /* candidates */
+    const int32_t *kf;    /* [n] key-frame index of window w */
+    const int32_t *lmk;   /* [n] landmark index of window w */
+    const int32_t *cam;   /* [n] camera of the candidate observation (the caller's camera order, as obs_cam); NULL: cross blocks only */
+    const double *meas;   /* [n][2] pixel uv | [n][3] unit bearing, as obs_meas of the window's factor type; NULL iff cam is NULL */
+} sadvio_cov_cross_request;
+
+int sadvio_ba_covariance_cross(sadvio_ba_handle *h, int32_t w, const sadvio_cov_cross_request *rq,
+                               double *cross_cov,  /* [n][d][3]  Sigma(a, l): rows = the key-frame's d states (6 | 15), columns = the landmark */
+                               double *innov_cov,  /* [n][4]     P, row-major 2 x 2, of the WHITENED residual (so the noise term is I) */
+                               double *maha2,      /* [n]        r^T P^-1 r */
+                               int32_t *status);   /* [n]        SADVIO_CROSS_OK | _LMK_SINGULAR | _PROJ_INVALID */
+
 /* Average device time in microseconds per kernel class since the last set_windows, measured
  * with hipEvents on the handle's stream (cfg.profile_kernels = 1). `names` receives pointers
  * to static strings. Returns the number of classes written (<= cap). */

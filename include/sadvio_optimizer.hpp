@@ -201,6 +201,14 @@ inline void pose_covariance_ros(const Pose& T_f_w, const double* cov_wt36, doubl
         }
 }
 
+// The 95 % gate on a squared Mahalanobis distance (HipOptimizer::covarianceCross: maha2 of a candidate observation, dof = 2): true
+// when maha2 is at most the chi-square quantile of `dof` degrees of freedom (1: 3.841, 2: 5.991, 3: 7.815; any other dof: false).
+// A NaN (singular landmark) never passes.
+inline bool innovation_gate(double maha2, int dof = 2) {
+    const double q95[4] = {0.0, 3.841458820694124, 5.991464547107979, 7.814727903251179};
+    return dof >= 1 && dof <= 3 && maha2 >= 0.0 && maha2 <= q95[dof];
+}
+
 // The problem of AngularAdjustmentCERESAnalytic::landmarkOptimizationNoFov (AngularAdjustmentCERESAnalytic.cpp:775-851) in the
 // layout of sadvio_nofov_problem. Selection: a landmark that is initialised and not an outlier (:778); of its features, only
 // those of key-frames count (:788); the one on f is `feat`, the one on fp is `featp` (the last one wins, :792-800), every other
@@ -607,6 +615,56 @@ class HipOptimizer {
     }
     int block_dim() const { return _cov_dim; }   // 6 or 15: of the last window solve
 
+    // Cross covariances Sigma(frame, landmark) of the last window solve and the innovation gate of candidate observations
+    // (sadvio_ba_covariance_cross), addressed by the snapshot's ids as covariance() is: candidate i is (frame_ids[i], landmark_ids[i]).
+    // cross_cov [n][d][3] (d = block_dim()). With cams (camera of each candidate, the rig's order) and meas ([n][2] pixel uv, or
+    // [n][3] unit bearings for an angular solve): innov_cov [n][4], the 2 x 2 covariance of the whitened residual, and maha2 [n]
+    // (innovation_gate turns it into a decision); without cams both must be null. A camera is named as Feature::camera names it: its
+    // index among the cameras of the candidate's frame. status [n]: SADVIO_CROSS_*. Any output may be null. Returns false (last_error
+    // says why) as covariance() does.
+    bool covarianceCross(const std::vector<int64_t>& frame_ids, const std::vector<int64_t>& landmark_ids, const std::vector<int32_t>* cams,
+                         const std::vector<double>* meas, std::vector<double>* cross_cov, std::vector<double>* innov_cov,
+                         std::vector<double>* maha2, std::vector<int32_t>* status = nullptr) {
+        auto find = [](const std::vector<int64_t>& ids, int64_t id) {
+            for (size_t i = 0; i < ids.size(); i++) if (ids[i] == id) return (int32_t)i;
+            return (int32_t)-1;
+        };
+        const size_t n = frame_ids.size();
+        if (landmark_ids.size() != n || (cams && cams->size() != n) || ((cams == nullptr) != (meas == nullptr))) {
+            _err = "covarianceCross: the candidate arrays differ in length";
+            return false;
+        }
+        std::vector<int32_t> kf, lm;
+        for (int64_t id : frame_ids) kf.push_back(find(_cov_kf_id, id));
+        for (int64_t id : landmark_ids) lm.push_back(find(_cov_lmk_id, id));
+        for (const std::vector<int32_t>* v : {&kf, &lm})
+            for (int32_t i : *v) if (i < 0) { _err = "covarianceCross: an id is not part of the last solved window"; return false; }
+        std::vector<double> xc(3 * (size_t)_cov_dim * n), pc(4 * n), m2(n);
+        std::vector<int32_t> st(n);
+        sadvio_cov_cross_request rq{};
+        rq.n = (int32_t)n; rq.kf = kf.data(); rq.lmk = lm.data();
+        std::vector<int32_t> wc;   // window camera = first camera of the frame + the camera's index in the frame
+        if (cams) {
+            for (size_t i = 0; i < n; i++) {
+                const int32_t last = (size_t)kf[i] + 1 < _cov_cam_base.size() ? _cov_cam_base[(size_t)kf[i] + 1] : _cov_n_cam;
+                if ((size_t)kf[i] >= _cov_cam_base.size() || (*cams)[i] < 0 || _cov_cam_base[kf[i]] + (*cams)[i] >= last) {
+                    _err = "covarianceCross: camera index out of range";
+                    return false;
+                }
+                wc.push_back(_cov_cam_base[kf[i]] + (*cams)[i]);
+            }
+        }
+        rq.cam = cams ? wc.data() : nullptr; rq.meas = meas ? meas->data() : nullptr;
+        const int rc = sadvio_ba_covariance_cross(_h, 0, &rq, cross_cov && n ? xc.data() : nullptr, innov_cov && n ? pc.data() : nullptr,
+                                                  maha2 && n ? m2.data() : nullptr, status && n ? st.data() : nullptr);
+        if (rc != SADVIO_OK) { _err = sadvio_ba_last_error(_h); return false; }
+        if (cross_cov) cross_cov->swap(xc);
+        if (innov_cov) innov_cov->swap(pc);
+        if (maha2) maha2->swap(m2);
+        if (status) status->swap(st);
+        return true;
+    }
+
     bool has_prior() const { return _prior.valid; }
     int prior_rows() const { return _prior.n_full; }
     int prior_cols() const { return _prior.n; }
@@ -886,6 +944,7 @@ class HipOptimizer {
         if (rc != SADVIO_OK && rc != SADVIO_E_NOT_USABLE) { _err = sadvio_ba_last_error(_h); return false; }   // state untouched
         if (rc == SADVIO_E_NOT_USABLE) return false;
         _cov_kf_id = F.kf_id; _cov_lmk_id = F.lmk_id; _cov_dim = vio ? 15 : 6;   // what covariance() addresses
+        _cov_cam_base = F.cam_base; _cov_n_cam = (int)F.cam_sigma.size();           // ... and where a frame's cameras start in the window
         std::vector<double> dpose(6 * (size_t)nkf), dl(3 * (size_t)std::max(F.w.n_lmk, 1)), dv(3 * (size_t)nkf), dba(3 * (size_t)nkf), dbg(3 * (size_t)nkf);
         if (sadvio_ba_get_deltas(_h, 0, dpose.data(), dl.data(), dv.data(), dba.data(), dbg.data()) != SADVIO_OK) { _err = sadvio_ba_last_error(_h); return false; }
         for (int i = 0; i < nkf; i++) {                                                  // AOptimizer.cpp:329-332
@@ -947,6 +1006,8 @@ class HipOptimizer {
     std::vector<int64_t> _sparse_lmk_id;        // [2 k], [2 k + 1]: ids of lmk0 / lmk1 of factor k
     int64_t _sparse_kf_id = -1;
     std::vector<int64_t> _cov_kf_id, _cov_lmk_id;   // ids of the last solved window, in its order
+    std::vector<int> _cov_cam_base;                  // first window camera of each of its frames
+    int _cov_n_cam = 0;
     int _cov_dim = 6;
 };
 

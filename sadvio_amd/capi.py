@@ -125,7 +125,12 @@ class CovBatchItemC(C.Structure):
                 ("kf_cov", _dp), ("pair_cov", _dp), ("lmk_cov", _dp)]
 
 
+class CovCrossRequestC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("kf", _ip), ("lmk", _ip), ("cam", _ip), ("meas", _dp)]
+
+
 COV_ROUTE_NONE, COV_ROUTE_LDS, COV_ROUTE_DENSE, COV_ROUTE_BAND = 0, 1, 2, 3   # SADVIO_COV_ROUTE_*
+CROSS_OK, CROSS_LMK_SINGULAR, CROSS_PROJ_INVALID = 0, 1, 2                    # SADVIO_CROSS_*
 PRIOR_RESIDENT = -1
 # SADVIO_EIG_CUT_*: the C ABI's default (a zero-initialised request) is the reference's absolute 1e-12; this harness and the
 # oracle's wrapper default to "noise_floor" because the parity tests compare n_full, which only that mode makes reproducible
@@ -448,6 +453,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.sadvio_ba_covariance.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CovRequestC), _dp, _dp, _dp, _ip]
     if hasattr(lib, "sadvio_ba_covariance_batch"):   # (nor this one)
         lib.sadvio_ba_covariance_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CovBatchItemC)]
+    if hasattr(lib, "sadvio_ba_covariance_cross"):   # (nor this one)
+        lib.sadvio_ba_covariance_cross.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CovCrossRequestC), _dp, _dp, _dp, _ip]
     lib.sadvio_ba_landmark_chi2.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, _dp, _ip]
     if hasattr(lib, "sadvio_ba_landmark_chi2_models"):   # (an older build loaded through SADVIO_BA_LIB does not export it)
         lib.sadvio_ba_landmark_chi2_models.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, C.POINTER(CameraModelC), _dp, C.c_double,
@@ -848,6 +855,40 @@ class Backend:
             return {"rc": rc, "error": msg.decode() if msg else "", "kf": kc, "pair": pc, "lmk": lc}
         self._check(rc, "covariance")
         return {"rc": rc, "kf": kc, "pair": pc, "lmk": lc, "n_lmk_singular": int(ns.value)}
+
+    def covariance_cross(self, w: int = 0, kf=(), lmk=(), cam=None, meas=None, raw_rc: bool = False, want_innov=None):
+        """Cross covariances Sigma(kf[i], lmk[i]) of window w and, with cam / meas (the candidate observation's camera and
+        measurement: pixel uv [n, 2] or unit bearing [n, 3]), the innovation covariance and squared Mahalanobis distance of each
+        candidate (sadvio_ba_covariance_cross). Returns {"cross" [n, d, 3], "innov" [n, 2, 2], "maha2" [n], "status" [n]} — "innov"
+        and "maha2" stay as allocated here (zeros) without cam. raw_rc=True returns {"rc", "error"} plus the untouched outputs for
+        a refused call instead of raising. want_innov=True asks for the innovation outputs even without cam (the library refuses)."""
+        win = self.windows[w] if 0 <= w < len(self.windows) else self.windows[0]
+        d = 15 if win.has_imu else 6
+        ka = np.ascontiguousarray(kf, dtype=np.int32).reshape(-1)
+        la = np.ascontiguousarray(lmk, dtype=np.int32).reshape(-1)
+        n = len(ka)
+        if len(la) != n:
+            raise ValueError("covariance_cross: kf and lmk differ in length")
+        rq = CovCrossRequestC()
+        rq.n, rq.kf, rq.lmk = n, ka.ctypes.data_as(_ip), la.ctypes.data_as(_ip)
+        ca = ma = None
+        if cam is not None:
+            ca = np.ascontiguousarray(cam, dtype=np.int32).reshape(-1)
+            rq.cam = ca.ctypes.data_as(_ip)
+        if meas is not None:
+            ma = np.ascontiguousarray(meas, dtype=np.float64).reshape(n, -1)
+            rq.meas = _ptr(ma)
+        innov = (cam is not None) if want_innov is None else want_innov
+        xc = np.zeros((n, d, 3)); pc = np.zeros((n, 2, 2)); m2 = np.zeros(n); st = np.zeros(n, dtype=np.int32)
+        rc = self.lib.sadvio_ba_covariance_cross(self.h, w, C.byref(rq), _ptr(xc) if n else _dp(), _ptr(pc) if (n and innov) else _dp(),
+                                                 _ptr(m2) if (n and innov) else _dp(), st.ctypes.data_as(_ip) if n else _ip())
+        out = {"rc": rc, "cross": xc, "innov": pc, "maha2": m2, "status": st}
+        if rc != SADVIO_OK and raw_rc:
+            msg = self.lib.sadvio_ba_last_error(self.h)
+            out["error"] = msg.decode() if msg else ""
+            return out
+        self._check(rc, "covariance_cross")
+        return out
 
     def cov_batch_items(self, items, fill: float = 0.0):
         """The sadvio_cov_batch_item array of `items` (dicts w=.., kf=.., pairs=.., lmk=.. with the meanings of covariance()) and the

@@ -991,6 +991,19 @@ int sadvio_ba_covariance_batch(sadvio_ba_handle* h, int32_t n_item, sadvio_cov_b
 
 }  // extern "C"
 
+#include "cov_cross_driver.h"   // below cov_driver.h: its steps up to cov_landmarks are the single call's
+
+extern "C" {
+
+// ---- key-frame x landmark cross covariances and the innovation gate of candidate observations ----
+int sadvio_ba_covariance_cross(sadvio_ba_handle* h, int32_t w, const sadvio_cov_cross_request* rq, double* cross_cov, double* innov_cov, double* maha2,
+                               int32_t* status) {
+    if (!h) return SADVIO_E_INVALID_ARG;
+    return covx_run(h, w, rq, cross_cov, innov_cov, maha2, status);
+}
+
+}  // extern "C"
+
 #include "rel_driver.h"
 
 extern "C" {

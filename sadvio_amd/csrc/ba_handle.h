@@ -209,6 +209,16 @@ struct CovScratch {
     std::vector<int> h_kf_ptr, h_kf_lmk;
 };
 
+// Work buffers of sadvio_ba_covariance_cross (cov_cross_driver.h), grown on demand: the call's tables in one int upload (plan order |
+// workgroup table | request kf, lmk | global camera | block row of each candidate | band route: first column of each block row), the
+// candidate measurements, the band route's solved block rows, and the results (cross | innov | maha2; status).
+struct CovCrossScratch {
+    DevBuf<int> ints, status;
+    DevBuf<double> meas, rows, out;
+    std::vector<int> h_ints, h_status;
+    std::vector<double> h_out;
+};
+
 // Work buffers of sadvio_ba_covariance_batch (cov_batch_driver.h). The pools hold the work arrays (pool, ipool) and the results (rpool)
 // of one group of windows and only ever grow; the pinned block holds the unit tables and receives every group's results, one copy
 // per group, read after the call's one wait.
@@ -250,6 +260,7 @@ struct EnvCfg {
     int cov_batch_lds = 1, cov_batch_scratch_mb = 1024;   // sadvio_ba_covariance_batch: the in-LDS inverse (0: every item down the dense route, A/B) | scratch budget of one group
     int cov_band = -1;   // covariance, the band route (cov_band_kernels.h): -1 not set: only where the call was refused before (N_p >= 2047) | 1: every bandable window | 0: never
     int cov_sqrt = -1;   // covariance, the square-root assembly (cov_kernels.h): -1 not set: only after the pivot tests refused the plain form | 1: from the start | 0: never
+    int cov_cross_stage = -1;   // covariance_cross: doubles of a block row k_cov_cross stages in LDS (tests: both sides of the limit); -1 not set: COVX_STAGE_MAX
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {
@@ -259,6 +270,7 @@ struct EnvCfg {
         tile_rounds = num("SADVIO_TILE_ROUNDS", 0); lm_subs = num("SADVIO_LM_SUBS", 0); band_c = num("SADVIO_BAND_C", 0);
         cov_batch_lds = num("SADVIO_COV_BATCH_LDS", 1); cov_batch_scratch_mb = num("SADVIO_COV_BATCH_SCRATCH_MB", 1024);
         cov_band = num("SADVIO_COV_BAND", -1); cov_sqrt = num("SADVIO_COV_SQRT", -1);
+        cov_cross_stage = num("SADVIO_COV_CROSS_STAGE", -1);
         if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);
         marg_pivoted = on("SADVIO_MARG_PIVOTED"); marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
@@ -303,6 +315,7 @@ struct sadvio_ba_handle {
     MargScratch mg;
     CovScratch cv;
     CovBatchScratch cvb;
+    CovCrossScratch cx;
     RelScratch rel;
     double cov_huber_a = 0.0;   // huber_a of the last solve: sadvio_ba_covariance corrects the visual factors as that solve did
     bool cov_use_lm = false;    // ... and whether the throughput kernels ran it (covariance is then refused)
