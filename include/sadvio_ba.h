@@ -58,8 +58,9 @@ typedef struct sadvio_ba_config {
     int32_t device;          /* HIP device ordinal */
     int32_t profile_kernels; /* 1: bracket every kernel class with hipEvents (see get_kernel_times) */
     int32_t use_graph;       /* 1: replay the iteration sequence from a captured hipGraph */
-    int32_t reserved;
+    int32_t reserved;        /* flags; 0 = none. SADVIO_CFG_LONG_TRACKS: accept landmarks with more than 64 observations (see sadvio_flat_window) */
 } sadvio_ba_config;
+#define SADVIO_CFG_LONG_TRACKS 1
 
 /*
  * One sliding window, flattened (SoA, index based). Replaces the object-graph walk of
@@ -71,7 +72,21 @@ typedef struct sadvio_ba_config {
  *   - landmark included iff isInitialized && !isOutlier (…Analytic.cpp:239);
  *   - observation included iff its sensor's frame is a key-frame of the window (…Analytic.cpp:256-258).
  * Observations are CSR by landmark. All arrays are caller-owned; set_window copies them.
+ *
+ * Observations per landmark. A handle created with sadvio_ba_config.reserved = 0 takes at most 64 observations per landmark and
+ * refuses the window otherwise ("a landmark has more than 64 observations"), as every handle always did: callers that rely on that
+ * refusal keep it. A handle created with SADVIO_CFG_LONG_TRACKS takes any number of observations up to SADVIO_MAX_LONG_TRACK_OBS, from
+ * up to SADVIO_MAX_LONG_TRACK_KF distinct key-frames. Landmarks of at most 64 observations are solved in the landmark tiles; one with
+ * more is a LONG TRACK: inside the same LM step it is linearised, eliminated and back-substituted by kernels of its own (DESIGN.md
+ * "Long tracks"), and its index and its place in every output array are what they would be anyway. A long track is free or
+ * constant, carries real observations only and cannot be kept in the reduced system: see set_dense_prior / set_sparse_priors, and
+ * the calls that refuse a window holding one (sadvio_ba_covariance*, sadvio_ba_marginalize*, sadvio_ba_sparsify naming one), all
+ * with SADVIO_E_INVALID_ARG and a text that names long tracks. A window sharded over several GPUs has no long path: it is refused
+ * at 65 observations whatever the flag. On a handle with the flag, SADVIO_LONG_MIN in the environment (read by sadvio_ba_create; an
+ * integer in [2, 65], default 65; tests and A/B timing) sends every landmark with at least that many observations down the long path.
  */
+#define SADVIO_MAX_LONG_TRACK_OBS 4096 /* observations of one landmark */
+#define SADVIO_MAX_LONG_TRACK_KF 512   /* distinct key-frames observing one landmark with more than 64 observations */
 typedef struct sadvio_flat_window {
     int32_t n_kf;
     int32_t n_cam;
@@ -244,7 +259,11 @@ void sadvio_ba_destroy(sadvio_ba_handle *h);
 
 /* Upload `n_windows` independent windows (a batch: independent sub-windows solved
  * concurrently; n_windows = 1 is the reference's case). Replaces addResidualsLocalMap
- * (…Analytic.cpp:197-314). Clears any factors set by earlier set_* calls. */
+ * (…Analytic.cpp:197-314). Clears any factors set by earlier set_* calls.
+ * On a handle created with SADVIO_CFG_LONG_TRACKS landmarks with more than 64 observations are accepted (long tracks, see
+ * sadvio_flat_window); SADVIO_E_INVALID_ARG with its own
+ * text for a landmark above SADVIO_MAX_LONG_TRACK_OBS observations or seen from more than SADVIO_MAX_LONG_TRACK_KF key-frames, and
+ * "a landmark has more than 64 observations" on a window sharded over several GPUs and on every handle created without the flag. */
 int sadvio_ba_set_windows(sadvio_ba_handle *h, int32_t n_windows, const sadvio_flat_window *windows);
 /* One layout build per key-frame: between begin_update and commit_update, set_windows and the factor setters that follow it
  * (set_pose_priors, set_imu_factors, set_sparse_priors, set_dense_prior, set_lines) only RECORD their arguments (validated and
@@ -277,7 +296,9 @@ int sadvio_ba_set_imu_factors(sadvio_ba_handle *h, int32_t w, int32_t n, const s
  * (or sadvio_ba_set_prior) left on the device, the way the reference keeps `_marginalization_last` inside the optimizer
  * (AOptimizer.h:88-90): nothing crosses PCIe; `n` is then ignored, `r0` must be NULL, and the caller only names the
  * variables of THIS window that the prior's columns refer to (it owns the id -> index bookkeeping, like the reference's
- * _map_frame_idx / _map_lmk_idx). */
+ * _map_frame_idx / _map_lmk_idx).
+ * A kept landmark must not be a long track (more than 64 observations, see sadvio_flat_window): SADVIO_E_INVALID_ARG, and the
+ * window keeps the prior it had. */
 #define SADVIO_PRIOR_RESIDENT (-1)
 int sadvio_ba_set_dense_prior(sadvio_ba_handle *h, int32_t w, int32_t n_full, int32_t n,
                               const double *J, const double *r0, int32_t kf_keep, int32_t kf_col,
@@ -463,7 +484,9 @@ int sadvio_ba_comm_init_rccl(sadvio_ba_handle *h, int32_t rank, int32_t world, c
  * (ncclCommCount / ncclCommUserRank / ncclCommCuDevice), otherwise from set_collective. Any pointer may be NULL. */
 int sadvio_ba_comm_info(sadvio_ba_handle *h, int32_t *nranks, int32_t *rank, int32_t *device, int32_t *is_rccl);
 
-/* Sparse (NFR) prior factors of window `w`; replaces the previous list (n = 0 clears it). */
+/* Sparse (NFR) prior factors of window `w`; replaces the previous list (n = 0 clears it). A factor that touches a long track
+ * (a landmark with more than 64 observations, see sadvio_flat_window), or pose-to-landmark factors whose two pseudo-observations
+ * each would take a landmark past 64, are refused with SADVIO_E_INVALID_ARG; the window keeps the list it had. */
 int sadvio_ba_set_sparse_priors(sadvio_ba_handle *h, int32_t w, int32_t n, const sadvio_sparse_prior *factors);
 
 /* Run the Levenberg-Marquardt solve of every uploaded window: replaces the body of

@@ -297,8 +297,10 @@ inline bool nofov_flatten(const LocalMapSnapshot& map, int f, int fp, const Pose
 
 class HipOptimizer {
   public:
-    explicit HipOptimizer(int device = 0, bool angular = false) : _angular(angular) {
-        sadvio_ba_config cfg{device, 0, 1, 0};
+    // long_tracks: landmarks with more than 64 observations are accepted (SADVIO_CFG_LONG_TRACKS, sadvio_ba.h); such a window cannot be
+    // marginalised or asked for covariances yet
+    explicit HipOptimizer(int device = 0, bool angular = false, bool long_tracks = false) : _angular(angular) {
+        sadvio_ba_config cfg{device, 0, 1, long_tracks ? SADVIO_CFG_LONG_TRACKS : 0};
         if (sadvio_ba_create(&cfg, &_h) != SADVIO_OK) throw std::runtime_error("sadvio: no usable gfx950 device");
     }
     ~HipOptimizer() { sadvio_ba_destroy(_h); }
@@ -840,6 +842,7 @@ class HipOptimizer {
                 sadvio_imu_factor f = p.f; f.kf_i = p.frame_i; f.kf_j = p.frame_j;
                 F.imus.push_back(f);
             }
+        // (a landmark may carry more than 64 observations: the library solves such long tracks beside its landmark tiles, sadvio_ba.h)
         sadvio_flat_window& w = F.w;
         w.n_kf = nkf; w.n_cam = (int)F.cam_sigma.size(); w.n_lmk = (int)F.lmk_src.size(); w.n_obs = (int)F.obs_kf.size();
         w.factor_type = _angular ? SADVIO_FACTOR_ANGULAR : SADVIO_FACTOR_PIXEL; w.has_imu = vio ? 1 : 0;

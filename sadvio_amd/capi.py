@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SADVIO_BA_LIB") or os.path.join(_HERE, "csrc", "libsadvio_ba.so")   # override: A/B measurement builds
 
 SADVIO_OK = 0
+CFG_LONG_TRACKS = 1   # sadvio_ba_config.reserved: SADVIO_CFG_LONG_TRACKS
 E_INVALID_ARG, E_NOT_USABLE, E_HIP, E_RCCL, E_NO_DEVICE, E_STATE, E_REFUSED = -1, -2, -3, -4, -5, -6, -7
 FACTOR_PIXEL, FACTOR_ANGULAR = 0, 1
 TERM_NAMES = {0: "NO_CONVERGENCE", 1: "FUNCTION_TOL", 2: "PARAMETER_TOL", 3: "GRADIENT_TOL", 4: "MIN_RADIUS",
@@ -474,9 +475,10 @@ def _ptr(a: Optional[np.ndarray]):
 class Backend:
     """Thin OO wrapper of one `sadvio_ba_handle` (one HIP stream, device-resident windows)."""
 
-    def __init__(self, device: int = 0, profile_kernels: bool = False, use_graph: bool = False):
+    def __init__(self, device: int = 0, profile_kernels: bool = False, use_graph: bool = False, long_tracks: bool = False):
+        """long_tracks: SADVIO_CFG_LONG_TRACKS, the handle accepts landmarks with more than 64 observations."""
         self.lib = load_library()
-        cfg = Config(device=device, profile_kernels=int(profile_kernels), use_graph=int(use_graph), reserved=0)
+        cfg = Config(device=device, profile_kernels=int(profile_kernels), use_graph=int(use_graph), reserved=CFG_LONG_TRACKS if long_tracks else 0)
         self.h = C.c_void_p()
         rc = self.lib.sadvio_ba_create(C.byref(cfg), C.byref(self.h))
         if rc != SADVIO_OK:

@@ -55,6 +55,8 @@ int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
     h->env.read();
     h->up.trace = (h->env.debug & 8192) != 0;
     if (cfg) h->cfg = *cfg;
+    // long tracks are served by handles that ask for them: every other handle refuses a 65th observation as it always did
+    if (h->cfg.reserved & SADVIO_CFG_LONG_TRACKS) h->env.long_min = h->env.long_min_env ? h->env.long_min_env : MAX_LMK_OBS + 1;
     h->device = dev;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return SADVIO_E_HIP; }
     if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) h->side = nullptr;   // optional: without it everything is serial
@@ -343,6 +345,10 @@ int sadvio_ba_set_dense_prior(sadvio_ba_handle* h, int32_t w, int32_t n_full, in
         for (int i = 0; i < n_keep; i++) {
             if (lmk_col[i] < 0) continue;
             if (lmk_index[i] < 0 || lmk_index[i] >= d.n_lmk || lmk_col[i] + 3 > n) { h->err = "set_dense_prior: kept landmark out of range"; return SADVIO_E_INVALID_ARG; }
+            if (lmk_is_long(h, w, lmk_index[i])) {
+                h->err = "set_dense_prior: landmark " + std::to_string(lmk_index[i]) + " is a long track (more than 64 observations): it cannot be kept in the reduced system";
+                return SADVIO_E_INVALID_ARG;
+            }
             for (int a = 0; a < 3; a++) {
                 if (used[lmk_col[i] + a]) { h->err = "set_dense_prior: overlapping column blocks"; return SADVIO_E_INVALID_ARG; }
                 used[lmk_col[i] + a] = 1;
@@ -402,6 +408,23 @@ int sadvio_ba_set_sparse_priors(sadvio_ba_handle* h, int32_t w, int32_t n, const
             return SADVIO_E_INVALID_ARG;
         }
     }
+    // long tracks (long_kernels.h) carry real observations only and are never held in the reduced system
+    if (h->env.long_min > 0 && h->world == 1 && !h->coll_fn) {
+        const std::vector<int32_t>& op = h->src[w].lmk_obs_ptr;
+        std::vector<int> pseudo(std::max(d.n_lmk, 1), 0);
+        for (int i = 0; i < n; i++) {
+            const sadvio_sparse_prior& s = f[i];
+            if (s.type == SADVIO_SPARSE_IMU_PRIOR || s.type == SADVIO_SPARSE_RELATIVE_POSE) continue;
+            if (lmk_is_long(h, w, s.lmk0) || (s.type == SADVIO_SPARSE_LMK_TO_LMK && lmk_is_long(h, w, s.lmk1))) {
+                h->err = "set_sparse_priors: factor " + std::to_string(i) + " touches a long track (a landmark with more than 64 observations)";
+                return SADVIO_E_INVALID_ARG;
+            }
+            if (s.type == SADVIO_SPARSE_POSE_TO_LMK && (int)op.size() > s.lmk0 + 1 && op[s.lmk0 + 1] - op[s.lmk0] + (pseudo[s.lmk0] += 2) > MAX_LMK_OBS) {
+                h->err = "set_sparse_priors: factor " + std::to_string(i) + " would make its landmark a long track (more than 64 observations with the factors' pseudo-observations)";
+                return SADVIO_E_INVALID_ARG;
+            }
+        }
+    }
     h->sparse_per_win[w].assign(f, f + n);
     if (h->defer) { h->pending = true; return SADVIO_OK; }
     return layout_build(h);  // eliminable pose-to-landmark factors become pseudo-observations: the tiles change
@@ -420,6 +443,7 @@ int sadvio_ba_marginalize(sadvio_ba_handle* h, int32_t w, const sadvio_marg_requ
     if (h->defer) { h->err = "marginalize between begin_update and commit_update"; return SADVIO_E_STATE; }
     if (!rq || w < 0 || w >= (int)h->plan.wins.size()) { h->err = "marginalize: bad argument"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "marginalize: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
+    if (int rc = refuse_long(h, w, "marginalize")) return rc;
     return marginalize(h, w, rq, res, lmk_col_out, J_out, r0_out);
 }
 
@@ -470,6 +494,7 @@ int sadvio_ba_marginalize_relative(sadvio_ba_handle* h, int32_t w, int32_t kf_a,
     if (h->world > 1) { h->err = "marginalize_relative: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
     const WinDev& d = h->plan.wins[w].d;
     if (kf_a < 0 || kf_a >= d.n_kf || kf_b < 0 || kf_b >= d.n_kf || kf_a == kf_b) { h->err = "marginalize_relative: bad key-frame index"; return SADVIO_E_INVALID_ARG; }
+    if (int rc = refuse_long(h, w, "marginalize_relative")) return rc;
     if (d.has_imu) { h->err = "marginalize_relative: frames with IMU states are not supported (the reference's own column layout for them is inconsistent, BundleAdjustmentCERESAnalytic.cpp:705-737)"; return SADVIO_E_INVALID_ARG; }
     return marginalize_relative(h, w, kf_a, kf_b, eig_cut_mode, inf36, Ak144);
 }
@@ -483,6 +508,8 @@ int sadvio_ba_sparsify(sadvio_ba_handle* h, int32_t w, int32_t vio, int32_t nf, 
     if (h->defer) { h->err = "sparsify between begin_update and commit_update"; return SADVIO_E_STATE; }
     if (w < 0 || w >= (int)h->plan.wins.size() || !n_out || !out || n_keep < 0 || (n_keep > 0 && (!lmk_index || !lmk_col))) { h->err = "sparsify: bad argument"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "sparsify: the window is sharded over several GPUs (linearisation values of a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
+    for (int i = 0; i < n_keep; i++)
+        if (lmk_is_long(h, w, lmk_index[i])) { h->err = "sparsify: landmark " + std::to_string(lmk_index[i]) + " is a long track (more than 64 observations)"; return SADVIO_E_INVALID_ARG; }
     return sparsify(h, w, vio, nf, n, J, kf_keep, kf_col, n_keep, lmk_index, lmk_col, n_out, out);
 }
 
@@ -972,6 +999,7 @@ extern "C" {
 int sadvio_ba_covariance(sadvio_ba_handle* h, int32_t w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov,
                          int32_t* n_lmk_singular) {
     if (!h) return SADVIO_E_INVALID_ARG;
+    if (int rc = refuse_long(h, w, "covariance")) return rc;
     return cov_run(h, w, rq, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
 }
 
@@ -986,6 +1014,8 @@ extern "C" {
 // ---- the covariances of many windows of the solved batch in one call ----
 int sadvio_ba_covariance_batch(sadvio_ba_handle* h, int32_t n_item, sadvio_cov_batch_item* items) {
     if (!h) return SADVIO_E_INVALID_ARG;
+    for (int i = 0; items && i < n_item; i++)
+        if (int rc = refuse_long(h, items[i].w, "covariance_batch")) return rc;
     return covb_run(h, n_item, items);
 }
 
@@ -999,6 +1029,7 @@ extern "C" {
 int sadvio_ba_covariance_cross(sadvio_ba_handle* h, int32_t w, const sadvio_cov_cross_request* rq, double* cross_cov, double* innov_cov, double* maha2,
                                int32_t* status) {
     if (!h) return SADVIO_E_INVALID_ARG;
+    if (int rc = refuse_long(h, w, "covariance_cross")) return rc;
     return covx_run(h, w, rq, cross_cov, innov_cov, maha2, status);
 }
 
@@ -1013,6 +1044,7 @@ extern "C" {
 int sadvio_ba_marginalize_relative_batch(sadvio_ba_handle* h, int32_t w, int32_t n_pair, const int32_t* kf_a, const int32_t* kf_b, int32_t eig_cut_mode,
                                          double* inf36, double* Ak144, double* T_a_b, int32_t* n_shared, int32_t* status) {
     if (!h) return SADVIO_E_INVALID_ARG;
+    if (int rc = refuse_long(h, w, "marginalize_relative_batch")) return rc;
     return rel_run(h, w, n_pair, kf_a, kf_b, eig_cut_mode, inf36, Ak144, T_a_b, n_shared, status);
 }
 

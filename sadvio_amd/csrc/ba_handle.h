@@ -21,6 +21,7 @@
 #include "dense_chol.h"
 #include "marg_kernels.h"
 #include "lm_kernels.h"
+#include "long_kernels.h"
 #include "viinit_kernels.h"
 #include "nofov_kernels.h"
 
@@ -261,6 +262,9 @@ struct EnvCfg {
     int cov_band = -1;   // covariance, the band route (cov_band_kernels.h): -1 not set: only where the call was refused before (N_p >= 2047) | 1: every bandable window | 0: never
     int cov_sqrt = -1;   // covariance, the square-root assembly (cov_kernels.h): -1 not set: only after the pivot tests refused the plain form | 1: from the start | 0: never
     int cov_cross_stage = -1;   // covariance_cross: doubles of a block row k_cov_cross stages in LDS (tests: both sides of the limit); -1 not set: COVX_STAGE_MAX
+    int long_min = 0;   // 0: the handle was created without SADVIO_CFG_LONG_TRACKS (no long path); else 65, or SADVIO_LONG_MIN in [2, 65] (tests, A/B timing): a landmark
+                        // with at least this many observations takes the long path (long_kernels.h). Set by sadvio_ba_create, behind read()
+    int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range)
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {
@@ -271,6 +275,8 @@ struct EnvCfg {
         cov_batch_lds = num("SADVIO_COV_BATCH_LDS", 1); cov_batch_scratch_mb = num("SADVIO_COV_BATCH_SCRATCH_MB", 1024);
         cov_band = num("SADVIO_COV_BAND", -1); cov_sqrt = num("SADVIO_COV_SQRT", -1);
         cov_cross_stage = num("SADVIO_COV_CROSS_STAGE", -1);
+        long_min_env = num("SADVIO_LONG_MIN", 0);
+        if (long_min_env < 2 || long_min_env > MAX_LMK_OBS + 1) long_min_env = 0;
         if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);
         marg_pivoted = on("SADVIO_MARG_PIVOTED"); marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
@@ -343,6 +349,7 @@ struct sadvio_ba_handle {
     DevBuf<double> d_lmk_p, d_xl, d_s_lmk;
     DevBuf<unsigned char> d_lmk_const;
     DevBuf<int> d_lmk_ob, d_lmk_oe, d_obs_kf, d_obs_cam, d_tile_kf, d_tile_row, d_tile_lmk;
+    DevBuf<int> d_long_rec, d_long_kf, d_long_slot;   // tables of the long tracks (long_kernels.h, LayoutPlan::long_rec)
     DevBuf<int> d_pre_lane, d_pre_kf;     // first-round packets of the latency kernels (kernels.h: DevPtrs::pre_lane), few-tile submissions only
     bool pre_dirty = false;
     DevBuf<int> d_rank_col; DevBuf<double> d_rank_x;       // refine_rank_by_eigenvalue (guarded calls only): pivot column per step, the solved vectors
@@ -393,6 +400,21 @@ int kclass_id(sadvio_ba_handle* h, const char* name) {
     KernelClass k; k.name = name;
     h->kclasses.push_back(k);
     return (int)h->kclasses.size() - 1;
+}
+
+// Long tracks (long_kernels.h) are served by the window solve and the per-landmark probes; the entry points that walk a landmark's
+// observations in lane groups of their own refuse a window that has one (DESIGN.md "Long tracks": follow-ups).
+bool window_has_long(const sadvio_ba_handle* h, int w) {
+    return w >= 0 && w < (int)h->plan.wins.size() && h->plan.wins[w].long_end > h->plan.wins[w].long_begin;
+}
+int refuse_long(sadvio_ba_handle* h, int w, const char* what) {
+    if (!h->uploaded || h->defer || !window_has_long(h, w)) return SADVIO_OK;
+    h->err = std::string(what) + ": the window has long tracks (landmarks with more than 64 observations), which this call does not serve";
+    return SADVIO_E_INVALID_ARG;
+}
+// landmark l of window w as the NEXT layout will see it (the caller's copy: valid between begin_update and commit_update too)
+bool lmk_is_long(const sadvio_ba_handle* h, int w, int l) {
+    return w >= 0 && w < (int)h->src.size() && src_lmk_is_long(h->src[w], l, h->env.long_min, h->world, h->coll_fn != nullptr);
 }
 
 struct ScopedTimer {

@@ -176,7 +176,11 @@ constexpr int MAX_TILE_FREE_KF = 20; // free ones: LDS tile <= 120 x 121 / 2 dou
 constexpr int MAX_GEMM_FREE_KF = 5;  // tiles touching <= 8 free key-frames accumulate through the MFMA contraction
 constexpr int MAX_WIN_CAM = 8;       // cameras per window staged in LDS
 constexpr int STAGE_VALS = 18;       // Jp[12] Jl[6] exchanged between the lanes of a landmark group
-constexpr int MAX_LMK_OBS = 64;      // observations per landmark (one lane each)
+constexpr int MAX_LMK_OBS = 64;      // observations per landmark of a tile (one lane each); longer tracks: long_kernels.h
+constexpr int MAX_LONG_OBS = 4096;   // observations of a long track (SADVIO_MAX_LONG_TRACK_OBS)
+constexpr int MAX_LONG_KF = 512;     // distinct key-frames observing a long track: its Y strip, 18 doubles each, is 72 KB of LDS (SADVIO_MAX_LONG_TRACK_KF)
+constexpr int LONG_THREADS = 256;    // k_long_lin / k_long_back: one workgroup per long track
+constexpr int LONG_REC = 6;          // ints of a long track's record (LayoutPlan::long_rec)
 constexpr int SOLVE_THREADS = 512;
 constexpr int SOLVE_KFC_STRIDE = 32; // doubles per parked key-frame: free index | x 6 | T0 12 | v, ba, bg at x 9
 constexpr int SOLVE_KFC = 32;        // k_solve<0>: key-frames / priors whose back-half inputs are parked in LDS across the factorisation

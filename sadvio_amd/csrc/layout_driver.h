@@ -32,6 +32,7 @@ LayoutIn layout_inputs(sadvio_ba_handle* h) {
     in.world = h->world; in.has_coll = h->coll_fn != nullptr;
     in.tile_rounds = h->env.tile_rounds; in.lm = h->env.lm; in.lm_subs = h->env.lm_subs;
     in.contig_tiles = h->env.contig_tiles; in.no_lpt = h->env.no_lpt; in.no_pre = h->env.no_pre;
+    in.long_min = h->env.long_min;
     return in;
 }
 
@@ -198,6 +199,10 @@ int layout_build(sadvio_ba_handle* h) {
     queue_table(h, h->d_lmk_ob, P.lmk_ob); queue_table(h, h->d_lmk_oe, P.lmk_oe); queue_table(h, h->d_obs_kf, P.obs_kf);
     queue_table(h, h->d_obs_cam, P.obs_cam); queue_table(h, h->d_obs_meas, P.obs_meas); queue_table(h, h->d_tile_kf, P.tile_kf);
     queue_table(h, h->d_tile_row, P.tile_row); queue_table(h, h->d_tile_lmk, P.tile_lmk); queue_table(h, h->d_obs_slot, P.obs_slot);
+    if (P.n_long > 0) {   // (a layout without long tracks uploads what it uploaded before)
+        HIP_TRY(h->d_long_rec.alloc(P.long_rec.size())); HIP_TRY(h->d_long_kf.alloc(P.long_kf.size())); HIP_TRY(h->d_long_slot.alloc(P.long_slot.size()));
+        queue_table(h, h->d_long_rec, P.long_rec); queue_table(h, h->d_long_kf, P.long_kf); queue_table(h, h->d_long_slot, P.long_slot);
+    }
     // First-round packets: what a lane of k_build / k_backsub needs to address the inputs of its tile's FIRST landmark round, laid out
     // by (tile, 8-lane granule) so that the loads hang on blockIdx alone: one int4 per 8 lanes, | landmark | its first observation |
     // its observation count + valid << 16 | position of the 8 lanes' first one in the landmark's group |, and per tile the first PRE_KF

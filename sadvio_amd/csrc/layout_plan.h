@@ -3,8 +3,9 @@
 // plans). Every kernel trusts these tables without bounds checks; tests/cpp/test_layout_plan.cpp holds them to hand-derived values.
 //
 // Steps of a full build, in order (layout_plan): layout_views (camera de-duplication, pseudo-observations of eliminable
-// pose-to-landmark factors), layout_windows (window records and bases), then per window layout_concat, layout_sort (per-landmark
-// key-frame order, obs_perm) and layout_tiles (contiguous or packed cut), then layout_chunks (chunk tables and work lists of the
+// pose-to-landmark factors), layout_windows (window records and bases), layout_long (which landmarks are long tracks: more
+// observations than a lane group holds; they stay out of the tiles), then per window layout_concat, layout_sort (per-landmark
+// key-frame order, obs_perm), layout_long_lists (key-frame lists of the long tracks) and layout_tiles (contiguous or packed cut), then layout_chunks (chunk tables and work lists of the
 // throughput kernels) and layout_reduced_plan (reduced systems: Np, ld, S_off, kept landmarks, dense-prior column maps, lines).
 // A change of the factor lists that leaves the tiles alone re-runs layout_reduced_plan only.
 #pragma once
@@ -43,6 +44,7 @@ struct HostWin {
     WinDev d;
     std::vector<int64_t> kf_id, lmk_id;
     int hb_lmk = 0;  // max distance (in free key-frame index) between two key-frames observing one landmark
+    int long_begin = 0, long_end = 0;   // the window's slice of the long list (LayoutPlan::long_rec)
 };
 
 struct DensePriorHost {
@@ -65,6 +67,8 @@ struct LineSetHost {   // deep copy of a sadvio_line_set
 // key-frame, and ~2 MB of fresh std::vectors per call are ~500 page faults (more than the layout arithmetic itself).
 struct LayoutScratch {
     std::vector<int> pack_order, pack_cut, pkf, run_max, mark, add, kfs, slot_of;
+    std::vector<int> rem, rem_ptr, rem_kf, rem_run;   // a window with long tracks: the landmarks left to the tiles and their compact CSR (tile_pack)
+    std::vector<long long> long_key;
     std::vector<char> held;
 };
 
@@ -82,6 +86,8 @@ struct LayoutIn {
     bool has_coll = false;   // a collective hook is set (a sharded window keeps the contiguous cut)
     int tile_rounds = 0, lm = -1, lm_subs = 0;   // SADVIO_TILE_ROUNDS, SADVIO_LM, SADVIO_LM_SUBS (0 / -1: not set)
     bool contig_tiles = false, no_lpt = false, no_pre = false;   // no_pre decides pre_ok only
+    int long_min = 0;   // 0: no long path (a landmark with more than 64 observations is refused); else a landmark with at least this many observations
+                        // is a long track (SADVIO_CFG_LONG_TRACKS: 65, or SADVIO_LONG_MIN)
 };
 
 struct DensePrep { long long off; int nf, n, w; };   // a window's dense prior in dp_data: offset, rows, columns, window
@@ -98,6 +104,12 @@ struct LayoutPlan {
     int n_kf_tot = 0, n_cam_tot = 0, n_lmk_tot = 0, n_obs_tot = 0;
     int max_n_kf = 0, max_npose = 0;
     bool user_lmk_const = false;                   // a window came with lmk_const
+    // layout_long, layout_long_lists: the long tracks (long_kernels.h), windows in order. long_rec: per track | global landmark |
+    // window | first entry of long_kf | distinct observing key-frames | first entry of long_slot | observations |; long_kf: those
+    // key-frames (global, ascending); long_slot: per observation of the track, in device order, its index into that list
+    std::vector<int> long_rec, long_kf, long_slot;
+    std::vector<char> is_long;                     // [n_lmk_tot]
+    int n_long = 0, long_max_kf = 0;
     // layout_concat, layout_sort: the concatenated arrays
     std::vector<double> kf_T0, kf_vel, kf_ba, kf_bg, cam_K, cam_T, cam_isig, lmk_p, obs_meas;
     std::vector<int> kf_fidx, lmk_ob, lmk_oe, obs_kf, obs_cam;
@@ -270,6 +282,68 @@ inline void layout_windows(int n_windows, const sadvio_flat_window* wins, Layout
     P.n_kf_tot = kf_b; P.n_cam_tot = cam_b; P.n_lmk_tot = lmk_b; P.n_obs_tot = obs_b;
 }
 
+// Is landmark l of caller's window S a long track: by its REAL observations, so that a factor list never moves a landmark between
+// the two paths. A window sharded over several GPUs has no long path.
+inline bool src_lmk_is_long(const SrcWin& S, int l, int long_min, int world, bool has_coll) {
+    if (long_min <= 0 || world > 1 || has_coll || l < 0 || l + 1 >= (int)S.lmk_obs_ptr.size()) return false;
+    return S.lmk_obs_ptr[l + 1] - S.lmk_obs_ptr[l] >= long_min;
+}
+
+// The long list: landmarks with at least long_min observations are linearised, eliminated and back-substituted by kernels of their
+// own (long_kernels.h), one workgroup each, and stay out of the tiles. Their index, their CSR entries and their place in every
+// output array are untouched. Such a landmark carries real observations only; a landmark that passes MAX_LMK_OBS through
+// pseudo-observations alone fits neither path. Fills HostWin::long_begin / long_end, is_long and the first two fields of long_rec.
+inline int layout_long(const LayoutIn& in, LayoutPlan& P, std::string& err) {
+    const int n_windows = (int)P.wins.size();
+    P.long_rec.clear(); P.long_kf.clear(); P.long_slot.clear();
+    P.is_long.assign(std::max(P.n_lmk_tot, 1), 0);
+    P.n_long = 0; P.long_max_kf = 0;
+    for (int w = 0; w < n_windows; w++) {
+        const sadvio_flat_window& F = P.views[w];
+        const SrcWin& S = (*in.src)[w];
+        HostWin& H = P.wins[w];
+        H.long_begin = P.n_long;
+        for (int l = 0; l < F.n_lmk; l++) {
+            const int n_aug = F.lmk_obs_ptr[l + 1] - F.lmk_obs_ptr[l];
+            if (!src_lmk_is_long(S, l, in.long_min, in.world, in.has_coll)) {
+                if (n_aug <= MAX_LMK_OBS) continue;
+                if (in.long_min <= 0 || in.world > 1 || in.has_coll || n_aug == S.lmk_obs_ptr[l + 1] - S.lmk_obs_ptr[l]) err = "set_windows: a landmark has more than 64 observations";
+                else err = "long tracks: the pseudo-observations of pose-to-landmark factors take a landmark past 64 observations";
+                return SADVIO_E_INVALID_ARG;
+            }
+            if (n_aug != S.lmk_obs_ptr[l + 1] - S.lmk_obs_ptr[l]) { err = "long tracks: a pose-to-landmark factor of the sparse prior touches a landmark on the long path"; return SADVIO_E_INVALID_ARG; }
+            if (n_aug > MAX_LONG_OBS) { err = "set_windows: a long track has more than " + std::to_string(MAX_LONG_OBS) + " observations"; return SADVIO_E_INVALID_ARG; }
+            P.is_long[H.d.lmk_base + l] = 1;
+            const int rec[LONG_REC] = {H.d.lmk_base + l, w, 0, 0, 0, n_aug};
+            P.long_rec.insert(P.long_rec.end(), rec, rec + LONG_REC);
+            P.n_long++;
+        }
+        H.long_end = P.n_long;
+    }
+    return SADVIO_OK;
+}
+
+// Key-frame lists of window w's long tracks, from the sorted observations (layout_sort left the window-local key-frames in ls.pkf)
+inline int layout_long_lists(LayoutPlan& P, int w, std::string& err) {
+    const HostWin& H = P.wins[w];
+    const WinDev& d = H.d;
+    const auto& pkf = P.ls.pkf;
+    for (int i = H.long_begin; i < H.long_end; i++) {
+        int* rec = &P.long_rec[(size_t)LONG_REC * i];
+        const int gl = rec[0], o0 = P.lmk_ob[gl] - d.obs_base, o1 = P.lmk_oe[gl] - d.obs_base;
+        rec[2] = (int)P.long_kf.size(); rec[4] = (int)P.long_slot.size();
+        int prev = -1, n = 0;
+        for (int o = o0; o < o1; o++) {
+            if (pkf[o] != prev) { P.long_kf.push_back(d.kf_base + pkf[o]); prev = pkf[o]; n++; }
+            P.long_slot.push_back(n - 1);
+        }
+        rec[3] = n;
+        if (n > MAX_LONG_KF) { err = "set_windows: a long track is observed from more than " + std::to_string(MAX_LONG_KF) + " key-frames"; return SADVIO_E_INVALID_ARG; }
+        P.long_max_kf = std::max(P.long_max_kf, n);
+    }
+    return SADVIO_OK;
+}
+
 // Sizes of the concatenated arrays (once per build) ...
 inline void layout_concat_begin(LayoutPlan& P) {
     const int kf_b = P.n_kf_tot, cam_b = P.n_cam_tot, lmk_b = P.n_lmk_tot, obs_b = P.n_obs_tot;
@@ -331,7 +405,7 @@ inline int layout_sort(const LayoutIn& in, LayoutPlan& P, int w, std::string& er
     const int* fidx_w = P.kf_fidx.data() + d.kf_base;
     for (int l = 0; l < F.n_lmk; l++) {
         const int o0 = F.lmk_obs_ptr[l], o1 = F.lmk_obs_ptr[l + 1];
-        if (o1 - o0 > MAX_LMK_OBS) { err = "set_windows: a landmark has more than 64 observations"; return SADVIO_E_INVALID_ARG; }
+        // (more than MAX_LMK_OBS observations: a long track, or refused by layout_long)
         int run = 0, rm = 0, prev = -1, lo = 1 << 30, hi = -1;
         for (int o = o0; o < o1; o++) {
             const int kf = F.obs_kf[o];
@@ -362,18 +436,29 @@ inline int layout_sort(const LayoutIn& in, LayoutPlan& P, int w, std::string& er
         const int o0 = F.lmk_obs_ptr[l], o1 = F.lmk_obs_ptr[l + 1], k_n = o1 - o0;
         // tracks are short: insertion sort (stable) on packed keys (key-frame << 8 | position) held in a local array —
         // no indirection through the caller's arrays inside the sort
-        long long key[MAX_LMK_OBS];
+        long long key_short[MAX_LMK_OBS];
+        long long* key = key_short;
+        int shift = 8;
         const int32_t* okf = F.obs_kf + o0;
-        for (int k = 0; k < k_n; k++) key[k] = ((long long)okf[k] << 8) | k;
-        for (int a = 1; a < k_n; a++) {
-            const long long v = key[a];
-            int b = a - 1;
-            while (b >= 0 && key[b] > v) { key[b + 1] = key[b]; b--; }
-            key[b + 1] = v;
+        if (k_n > MAX_LMK_OBS) {
+            // a long track (at most MAX_LONG_OBS observations: layout_long): a 16-bit position field, and the keys, all distinct, through std::sort
+            static_assert(MAX_LONG_OBS <= 65536, "the sort key of a long track carries the observation position in 16 bits");
+            P.ls.long_key.resize(k_n);
+            key = P.ls.long_key.data(); shift = 16;
+            for (int k = 0; k < k_n; k++) key[k] = ((long long)okf[k] << 16) | k;
+            std::sort(key, key + k_n);
+        } else {
+            for (int k = 0; k < k_n; k++) key[k] = ((long long)okf[k] << 8) | k;
+            for (int a = 1; a < k_n; a++) {
+                const long long v = key[a];
+                int b = a - 1;
+                while (b >= 0 && key[b] > v) { key[b + 1] = key[b]; b--; }
+                key[b + 1] = v;
+            }
         }
         int run = 0, rm = 0, prev = -1;
         for (int k = 0; k < k_n; k++) {
-            const int rel = (int)(key[k] & 255);
+            const int rel = (int)(key[k] & ((1 << shift) - 1));
             const int src = o0 + rel, dst = o0 + k;
             const int kf = okf[rel], c = F.obs_cam[src];
             pkf[dst] = kf;
@@ -394,7 +479,8 @@ inline int layout_sort(const LayoutIn& in, LayoutPlan& P, int w, std::string& er
 
 // Is the throughput path wanted: its chunk tables cost host time (a second, sorted copy of the observation constants), so they are
 // only built where it can run; its tiles are runs of consecutive landmarks throughout
-inline bool layout_want_lm(const LayoutIn& in, const LayoutPlan& P) { return in.lm >= 0 ? in.lm != 0 : P.n_lmk_tot >= 65536; }
+// (a batch with long tracks is solved by the latency kernels: the chunk tables hold at most 64 observations per landmark)
+inline bool layout_want_lm(const LayoutIn& in, const LayoutPlan& P) { return P.n_long == 0 && (in.lm >= 0 ? in.lm != 0 : P.n_lmk_tot >= 65536); }
 
 // Tiles of window w. Every landmark gets a group of G lanes (G = pow2 >= the tile's largest observation count); a workgroup of
 // BUILD_WAVES waves holds BUILD_WAVES * 64 / G landmarks per round. Contiguous cut: runs of consecutive landmarks, a tile is cut
@@ -416,7 +502,22 @@ inline int layout_tiles(const LayoutIn& in, LayoutPlan& P, int w, std::string& e
     d.tile_begin = (int)P.tiles.size();
     const bool packed = n_windows == 1 && tile_rounds == 1 && F.n_lmk > 0 && in.world == 1 && !in.has_coll && !layout_want_lm(in, P) && !in.contig_tiles;
     auto& order = ls.pack_order; auto& cut = ls.pack_cut;
-    if (packed) {
+    // Long tracks (layout_long) pass through the cut as landmarks without observations and are left out of the tiles' landmark lists:
+    // the tiles are those of the same window with these landmarks emptied. Their tiles list their landmarks (lmk_off >= 0) either way.
+    const bool has_long = P.wins[w].long_end > P.wins[w].long_begin;
+    const char* is_long = P.is_long.data() + d.lmk_base;
+    const bool listed = packed || has_long;
+    if (packed && has_long) {
+        auto& rp = ls.rem_ptr; auto& rk = ls.rem_kf; auto& rr = ls.rem_run;
+        rp.assign(1, 0); rk.clear(); rr.assign(F.n_lmk, 0);
+        for (int gl = 0; gl < F.n_lmk; gl++) {
+            if (!is_long[gl]) { rk.insert(rk.end(), pkf.begin() + F.lmk_obs_ptr[gl], pkf.begin() + F.lmk_obs_ptr[gl + 1]); rr[gl] = run_max[gl]; }
+            rp.push_back((int)rk.size());
+        }
+        if (rk.empty()) rk.push_back(0);
+        const TilePackIn tp{F.n_lmk, F.n_kf, rp.data(), rk.data(), F.kf_const, rr.data(), BUILD_WAVES * 64, MAX_TILE_KF, MAX_TILE_FREE_KF, MAX_GEMM_FREE_KF};
+        tile_pack(tp, order, cut);
+    } else if (packed) {
         const TilePackIn tp{F.n_lmk, F.n_kf, F.lmk_obs_ptr, pkf.data(), F.kf_const, run_max.data(), BUILD_WAVES * 64, MAX_TILE_KF, MAX_TILE_FREE_KF, MAX_GEMM_FREE_KF};
         tile_pack(tp, order, cut);
     }
@@ -428,17 +529,18 @@ inline int layout_tiles(const LayoutIn& in, LayoutPlan& P, int w, std::string& e
     while (l < F.n_lmk || (int)P.tiles.size() == d.tile_begin) {
         Tile t{};
         t.w = w; t.lmk0 = d.lmk_base + (l < F.n_lmk ? lm_at(l) : l); t.kmax = 1; t.G = 8;
-        t.lmk_off = packed ? (int)P.tile_lmk.size() : -1;
+        t.lmk_off = listed ? (int)P.tile_lmk.size() : -1;
         t.dpf = d.dpf;  // Np, red_off, S_off, ld: layout_reduced_plan
         t.cam_base = d.cam_base; t.n_cam = F.n_cam;
         t.first_of_window = ((int)P.tiles.size() == d.tile_begin) ? 1 : 0;
         kfs.clear();
-        int nfree = 0, tile_run_max = 0;
+        int nfree = 0, tile_run_max = 0, n_skipped = 0;
         const int l_begin = l;
         while (l < F.n_lmk) {
             const int gl = lm_at(l);
             if (packed && l == cut[next_cut]) break;
-            const int k = F.lmk_obs_ptr[gl + 1] - F.lmk_obs_ptr[gl];
+            const bool lg = has_long && is_long[gl];
+            const int k = lg ? 0 : F.lmk_obs_ptr[gl + 1] - F.lmk_obs_ptr[gl];
             int G = t.G;
             while (G < k) G <<= 1;
             const int cap = tile_rounds * BUILD_WAVES * (64 / G);  // landmarks per tile (tile_rounds rounds per wave)
@@ -446,7 +548,7 @@ inline int layout_tiles(const LayoutIn& in, LayoutPlan& P, int w, std::string& e
             // key-frames this landmark would add
             add.clear();
             int add_free = 0;
-            for (int o = F.lmk_obs_ptr[gl]; o < F.lmk_obs_ptr[gl + 1]; o++) {
+            for (int o = F.lmk_obs_ptr[gl]; o < F.lmk_obs_ptr[gl] + k; o++) {
                 const int kf = pkf[o];
                 if (mark[kf] != (int)P.tiles.size()) {
                     mark[kf] = (int)P.tiles.size();
@@ -465,19 +567,23 @@ inline int layout_tiles(const LayoutIn& in, LayoutPlan& P, int w, std::string& e
             nfree += add_free;
             t.G = G;
             t.kmax = std::max(t.kmax, k);
-            tile_run_max = std::max(tile_run_max, run_max[gl]);
-            if (packed) P.tile_lmk.push_back(d.lmk_base + gl);
+            if (lg) n_skipped++;
+            else {
+                tile_run_max = std::max(tile_run_max, run_max[gl]);
+                if (listed) P.tile_lmk.push_back(d.lmk_base + gl);
+            }
             l++;
             if (!packed && !fits_hard) break;  // a single landmark exceeding the capacity: global-atomics tile
         }
         if (packed) next_cut++;
-        t.n_lmk = l - l_begin;
-        t.lmk1 = t.lmk0 + t.n_lmk;   // (a packed tile: the count only; its landmarks are tile_lmk's)
+        t.n_lmk = l - l_begin - n_skipped;
+        t.lmk1 = t.lmk0 + t.n_lmk;   // (a tile that lists its landmarks: the count only; they are tile_lmk's)
         std::sort(kfs.begin(), kfs.end());
         t.lds_mode = ((int)kfs.size() <= MAX_TILE_KF && nfree <= MAX_TILE_FREE_KF) ? ((nfree <= MAX_GEMM_FREE_KF && tile_run_max <= (has_asrc ? 4 : 2) && t.G == 8) ? 2 : 1) : 0;
         if (t.lds_mode == 2 && tile_run_max > 2) P.gemm_run4 = true;   // needs the RARE variant of k_build (pseudo-observations: it is taken)
         if (t.lds_mode == 2) P.max_gemm_free = std::max(P.max_gemm_free, nfree);
-        // (a guard, not reachable today: a landmark has at most 64 observations, and a tile of several landmarks lists at most MAX_TILE_KF key-frames)
+        // (a guard, not reachable today: a landmark of a tile has at most 64 observations, and a tile of several landmarks lists at most
+        // MAX_TILE_KF key-frames; long tracks are not in the tiles' lists)
         if ((int)kfs.size() > 64) { err = "set_windows: a landmark is observed from more than 64 key-frames"; return SADVIO_E_INVALID_ARG; }
         t.kf_off = (int)P.tile_kf.size(); t.n_kf = (int)kfs.size(); t.n_free = t.lds_mode ? nfree : 0;
         int rank = 0;
@@ -490,9 +596,11 @@ inline int layout_tiles(const LayoutIn& in, LayoutPlan& P, int w, std::string& e
             else if (t.lds_mode) P.tile_row.push_back(6 * rank++);
             else P.tile_row.push_back(6 * P.kf_fidx[d.kf_base + kf]);  // global mode: 6 * free index of the window
         }
-        for (int li = l_begin; li < l; li++)
+        for (int li = l_begin; li < l; li++) {
+            if (has_long && is_long[lm_at(li)]) continue;   // (its observations carry no tile slot: long_slot)
             for (int o = F.lmk_obs_ptr[lm_at(li)]; o < F.lmk_obs_ptr[lm_at(li) + 1]; o++)
                 P.obs_slot[d.obs_base + o] = (unsigned char)slot_of[pkf[o]];
+        }
         P.max_tile_kf = std::max(P.max_tile_kf, t.n_kf);
         P.max_tile_free = std::max(P.max_tile_free, t.n_free);
         P.tiles.push_back(t);
@@ -563,6 +671,9 @@ inline void layout_chunks(const LayoutIn& in, LayoutPlan& P) {
     P.lm_n_sub = (int)P.sub.size() / 2;
     if (P.tile_kf.empty()) { P.tile_kf.push_back(0); P.tile_row.push_back(-1); }   // (no table is uploaded empty)
     if (P.tile_lmk.empty()) P.tile_lmk.push_back(0);
+    if (P.long_rec.empty()) P.long_rec.assign(LONG_REC, 0);
+    if (P.long_kf.empty()) P.long_kf.push_back(0);
+    if (P.long_slot.empty()) P.long_slot.push_back(0);
     // first-round packets of the latency kernels (k_pre_packets): few-tile submissions only, the single-window / small-batch regime
     P.pre_ok = !P.tiles.empty() && P.tiles.size() <= PRE_MAX_TILES && !in.no_pre;
 }
@@ -580,6 +691,19 @@ inline int layout_reduced_plan(const LayoutIn& in, LayoutPlan& P, std::string& e
             err = "the handle's prior changed after set_dense_prior(SADVIO_PRIOR_RESIDENT) attached it to a window: attach it again"; return SADVIO_E_STATE;
         }
     }
+    // a long track is eliminated by its own kernels: it cannot be held in the reduced system (refused before anything of the plan changes)
+    if (P.n_long > 0)
+        for (int w = 0; w < n_windows && w < (int)dpriors.size(); w++) {
+            const int lb = P.wins[w].d.lmk_base;
+            const DensePriorHost& D = dpriors[w];
+            bool bad = false;
+            for (size_t i = 0; i < D.lmk_index.size(); i++) bad |= D.n_full > 0 && D.lmk_col[i] >= 0 && P.is_long[lb + D.lmk_index[i]];
+            for (const sadvio_sparse_prior& sp : (*in.sparse_per_win)[w]) {
+                if (sp.type != SADVIO_SPARSE_IMU_PRIOR && sp.type != SADVIO_SPARSE_RELATIVE_POSE) bad |= P.is_long[lb + sp.lmk0] != 0;
+                if (sp.type == SADVIO_SPARSE_LMK_TO_LMK) bad |= P.is_long[lb + sp.lmk1] != 0;
+            }
+            if (bad) { err = "long tracks: a prior factor keeps or touches a landmark on the long path"; return SADVIO_E_INVALID_ARG; }
+        }
     int red_b = 0; long long s_b = 0;
     P.max_np = 0; P.n_big = 0;
     auto& lmk_red = P.lmk_red; auto& lmk_const = P.lmk_const_red; auto& kept = P.kept; auto& dp_ints = P.dp_ints;
@@ -728,12 +852,15 @@ inline int layout_plan(const LayoutIn& in, LayoutPlan& P, std::string& err, Lap&
         }
     }
     layout_windows(n_windows, P.views.data(), P);
+    if (const int rc = layout_long(in, P, err)) return rc;
     lap("  validate");
     layout_concat_begin(P);
     for (int w = 0; w < n_windows; w++) {
         layout_concat(P, w);
         lap("  concat");
         int rc = layout_sort(in, P, w, err);
+        if (rc != SADVIO_OK) return rc;
+        rc = layout_long_lists(P, w, err);
         if (rc != SADVIO_OK) return rc;
         lap("  sort+permute");
         rc = layout_tiles(in, P, w, err);

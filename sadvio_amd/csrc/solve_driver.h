@@ -158,11 +158,14 @@ struct SolvePlan {
     int n_kf_tot, n_pf, n_lo, dp_max_nf, dp_max_n, reset_blocks, table_blocks, max_win_tiles, lm_n_sub, lm_sub_obs, n_big;
     bool pix, rare, with_imu, use_lm, extras, fork;
     bool coll_band;        // sharded: only the band of the one window's S travels (coll_buf = the packed copy)
-    size_t lds_build, lds_back, lds_solve, lds_bobs, lds_pass0, lds_pass;
+    size_t lds_build, lds_back, lds_solve, lds_bobs, lds_pass0, lds_pass, lds_long_lin, lds_long_back;
     BuildFn k_build;
     BacksubFn k_backsub;
     decltype(&k_build_kept<0>) k_build_kept;
     decltype(&k_build_obs<0>) k_build_obs;
+    LongArgs lg;                              // long tracks (long_kernels.h): their kernels are launched when lg.n_long > 0
+    decltype(&k_long_lin<0>) k_long_lin;
+    decltype(&k_long_back<0>) k_long_back;
     decltype(&k_lm_pass<0, false>) k_lm_pass, k_lm_pass0;
     decltype(&k_solve<0, false>) k_solve, k_solve_front, k_solve_back;
     // workspaces of the out-of-LDS routes. They are part of the key in their own right: a workspace that grows moves, and a graph
@@ -361,6 +364,14 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     plan.k_build = build_variant(pix, rare, with_imu);
     plan.k_backsub = backsub_variant(pix, rare, with_imu);
     plan.k_build_kept = pix ? k_build_kept<0> : k_build_kept<1>;
+    if (h->plan.n_long > 0) {
+        plan.lg.n_long = h->plan.n_long; plan.lg.max_kf = h->plan.long_max_kf;
+        plan.lg.rec = h->d_long_rec.p; plan.lg.kf = h->d_long_kf.p; plan.lg.slot = h->d_long_slot.p;
+        plan.k_long_lin = pix ? k_long_lin<0> : k_long_lin<1>;
+        plan.k_long_back = pix ? k_long_back<0> : k_long_back<1>;
+        plan.lds_long_lin = long_lds_bytes(plan.lg.max_kf); plan.lds_long_back = long_lds_bytes(0);
+        HIP_TRY(hipFuncSetAttribute((const void*)plan.k_long_lin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_long_lin));
+    }
     // large plain batches: the throughput kernels of lm_kernels.h (SADVIO_LM=1 / 0 forces / forbids them, for tests and A/B runs)
     bool use_lm = h->plan.lm_ok && !rare && !h->coll_fn && h->world == 1 && h->plan.lm_landmarks >= 65536;
     if (h->env.lm >= 0) use_lm = h->plan.lm_ok && !rare && !h->coll_fn && h->world == 1 && h->env.lm != 0;
@@ -489,6 +500,7 @@ bool enqueue_solve(sadvio_ba_handle* h, const SolvePlan& pl, const std::vector<B
         { ScopedTimer t(h, "k_build"); hipLaunchKernelGGL(pl.k_build, dim3(n_tiles + (with_imu ? n_pf : 0)), dim3(BUILD_THREADS), pl.lds_build, h->stream, P, s, mtk, pl.strip_doubles, pl.Rp); }
         if (n_pf && (use_lm || !with_imu)) { ScopedTimer t(h, "k_pf_lin"); hipLaunchKernelGGL(k_pf_eval<false>, dim3(n_pf), dim3(BUILD_THREADS), 0, h->stream, P, s); }
         if (n_kept) { ScopedTimer t(h, "k_build_kept"); hipLaunchKernelGGL(pl.k_build_kept, dim3((n_kept + 127) / 128), dim3(128), 0, h->stream, P, s); }
+        if (pl.lg.n_long) { ScopedTimer t(h, "k_long_lin"); hipLaunchKernelGGL(pl.k_long_lin, dim3(pl.lg.n_long), dim3(LONG_THREADS), pl.lds_long_lin, h->stream, P, pl.lg, s); }
         if (pl.dp_max_nf > 0) {
             ScopedTimer t(h, "k_prior_r+gh");
             const int colb = (pl.dp_max_n + 3) / 4;
@@ -546,6 +558,7 @@ bool enqueue_solve(sadvio_ba_handle* h, const SolvePlan& pl, const std::vector<B
         }
         else
         { ScopedTimer t(h, "k_backsub"); hipLaunchKernelGGL(pl.k_backsub, dim3(n_tiles + (with_imu ? n_pf : 0)), dim3(BUILD_THREADS), pl.lds_back, h->stream, P, s, mtk); }
+        if (pl.lg.n_long) { ScopedTimer t(h, "k_long_back"); hipLaunchKernelGGL(pl.k_long_back, dim3(pl.lg.n_long), dim3(LONG_THREADS), pl.lds_long_back, h->stream, P, pl.lg, s); }
         if (fork) (void)hipStreamWaitEvent(h->stream, h->ev_cost, 0);
         if (h->coll_fn) {
             { ScopedTimer t(h, "k_rank_partials"); hipLaunchKernelGGL(k_rank_partials, dim3(n_win), dim3(64), 0, h->stream, P, s, 1); }
