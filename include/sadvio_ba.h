@@ -58,9 +58,12 @@ typedef struct sadvio_ba_config {
     int32_t device;          /* HIP device ordinal */
     int32_t profile_kernels; /* 1: bracket every kernel class with hipEvents (see get_kernel_times) */
     int32_t use_graph;       /* 1: replay the iteration sequence from a captured hipGraph */
-    int32_t reserved;        /* flags; 0 = none. SADVIO_CFG_LONG_TRACKS: accept landmarks with more than 64 observations (see sadvio_flat_window) */
+    int32_t reserved;        /* flags; 0 = none. SADVIO_CFG_LONG_TRACKS: accept landmarks with more than 64 observations (see sadvio_flat_window);
+                                SADVIO_CFG_LONG_TRACK_PRIORS: ... and marginalise, sparsify and hold them under priors. A refused combination:
+                                SADVIO_E_INVALID_ARG, the text through sadvio_ba_last_error(NULL) */
 } sadvio_ba_config;
 #define SADVIO_CFG_LONG_TRACKS 1
+#define SADVIO_CFG_LONG_TRACK_PRIORS 2 /* with SADVIO_CFG_LONG_TRACKS: marginalize, sparsify and the prior setters serve long tracks */
 
 /*
  * One sliding window, flattened (SoA, index based). Replaces the object-graph walk of
@@ -78,11 +81,25 @@ typedef struct sadvio_ba_config {
  * refusal keep it. A handle created with SADVIO_CFG_LONG_TRACKS takes any number of observations up to SADVIO_MAX_LONG_TRACK_OBS, from
  * up to SADVIO_MAX_LONG_TRACK_KF distinct key-frames. Landmarks of at most 64 observations are solved in the landmark tiles; one with
  * more is a LONG TRACK: inside the same LM step it is linearised, eliminated and back-substituted by kernels of its own (DESIGN.md
- * "Long tracks"), and its index and its place in every output array are what they would be anyway. A long track is free or
- * constant, carries real observations only and cannot be kept in the reduced system: see set_dense_prior / set_sparse_priors, and
- * the calls that refuse a window holding one (sadvio_ba_covariance*, sadvio_ba_marginalize*, sadvio_ba_sparsify naming one), all
- * with SADVIO_E_INVALID_ARG and a text that names long tracks. A window sharded over several GPUs has no long path: it is refused
- * at 65 observations whatever the flag. On a handle with the flag, SADVIO_LONG_MIN in the environment (read by sadvio_ba_create; an
+ * "Long tracks"), and its index and its place in every output array are what they would be anyway. On a handle with that flag
+ * alone a long track is free or constant, carries real observations only and cannot be kept in the reduced system: see
+ * set_dense_prior / set_sparse_priors, and the calls that refuse a window holding one (sadvio_ba_covariance*, sadvio_ba_marginalize*,
+ * sadvio_ba_sparsify naming one), all with SADVIO_E_INVALID_ARG and a text that names long tracks: callers that rely on those
+ * refusals keep them.
+ *
+ * Long tracks under a prior. A handle created with SADVIO_CFG_LONG_TRACKS | SADVIO_CFG_LONG_TRACK_PRIORS steps a sliding window that
+ * holds long tracks (SADVIO_CFG_LONG_TRACK_PRIORS without SADVIO_CFG_LONG_TRACKS: sadvio_ba_create fails with SADVIO_E_INVALID_ARG):
+ *   - sadvio_ba_marginalize takes a window with long tracks; one may stand in lmk_keep or lmk_marg;
+ *   - sadvio_ba_sparsify takes a long track among its kept landmarks;
+ *   - sadvio_ba_set_dense_prior keeps a long track in the reduced system like any landmark (3 columns behind the poses);
+ *   - sadvio_ba_set_sparse_priors: a landmark-prior or landmark-to-landmark factor holds its long track in the reduced system; a
+ *     pose-to-landmark factor on a free long track HOLDS it there too (on a landmark of the tiles such a factor rides the
+ *     elimination as two pseudo-observations; a long track carries real observations only, with or without this flag).
+ *   A held long track costs what any held landmark costs: 3 more columns of the reduced system in every LM step, and one thread
+ *   per observation of it adding its rows (k_build_kept); its pose-pose part is still summed by the long kernels.
+ *   sadvio_ba_covariance, _covariance_batch, _covariance_cross, sadvio_ba_marginalize_relative and _relative_batch refuse a window
+ *   with long tracks as before, with this flag or without it.
+ * A window sharded over several GPUs has no long path: it is refused at 65 observations whatever the flags. On a handle with the flag, SADVIO_LONG_MIN in the environment (read by sadvio_ba_create; an
  * integer in [2, 65], default 65; tests and A/B timing) sends every landmark with at least that many observations down the long path.
  */
 #define SADVIO_MAX_LONG_TRACK_OBS 4096 /* observations of one landmark */
@@ -298,7 +315,7 @@ int sadvio_ba_set_imu_factors(sadvio_ba_handle *h, int32_t w, int32_t n, const s
  * variables of THIS window that the prior's columns refer to (it owns the id -> index bookkeeping, like the reference's
  * _map_frame_idx / _map_lmk_idx).
  * A kept landmark must not be a long track (more than 64 observations, see sadvio_flat_window): SADVIO_E_INVALID_ARG, and the
- * window keeps the prior it had. */
+ * window keeps the prior it had; a handle created with SADVIO_CFG_LONG_TRACK_PRIORS keeps a long track like any landmark. */
 #define SADVIO_PRIOR_RESIDENT (-1)
 int sadvio_ba_set_dense_prior(sadvio_ba_handle *h, int32_t w, int32_t n_full, int32_t n,
                               const double *J, const double *r0, int32_t kf_keep, int32_t kf_col,
@@ -486,7 +503,9 @@ int sadvio_ba_comm_info(sadvio_ba_handle *h, int32_t *nranks, int32_t *rank, int
 
 /* Sparse (NFR) prior factors of window `w`; replaces the previous list (n = 0 clears it). A factor that touches a long track
  * (a landmark with more than 64 observations, see sadvio_flat_window), or pose-to-landmark factors whose two pseudo-observations
- * each would take a landmark past 64, are refused with SADVIO_E_INVALID_ARG; the window keeps the list it had. */
+ * each would take a landmark past 64, are refused with SADVIO_E_INVALID_ARG; the window keeps the list it had. On a handle created
+ * with SADVIO_CFG_LONG_TRACK_PRIORS a factor may touch a long track: it holds the landmark in the reduced system, a pose-to-landmark
+ * factor included (see sadvio_flat_window, "Long tracks under a prior"); the second refusal stays. */
 int sadvio_ba_set_sparse_priors(sadvio_ba_handle *h, int32_t w, int32_t n, const sadvio_sparse_prior *factors);
 
 /* Run the Levenberg-Marquardt solve of every uploaded window: replaces the body of
@@ -831,6 +850,9 @@ int sadvio_ba_covariance_cross(sadvio_ba_handle *h, int32_t w, const sadvio_cov_
 int sadvio_ba_get_kernel_times(sadvio_ba_handle *h, int32_t cap, const char **names, double *avg_us,
                                int64_t *launches);
 
+/* Text of the last error of handle `h` (owned by the handle; valid until its next failing call or sadvio_ba_destroy).
+ * h = NULL: why the calling THREAD's last sadvio_ba_create refused its configuration (SADVIO_E_INVALID_ARG) — the text is kept per
+ * thread, is cleared by that thread's next sadvio_ba_create and is valid until then; "null handle" when there is none. */
 const char *sadvio_ba_last_error(sadvio_ba_handle *h);
 const char *sadvio_ba_version(void);
 

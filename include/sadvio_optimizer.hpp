@@ -298,10 +298,13 @@ inline bool nofov_flatten(const LocalMapSnapshot& map, int f, int fp, const Pose
 class HipOptimizer {
   public:
     // long_tracks: landmarks with more than 64 observations are accepted (SADVIO_CFG_LONG_TRACKS, sadvio_ba.h); such a window cannot be
-    // marginalised or asked for covariances yet
-    explicit HipOptimizer(int device = 0, bool angular = false, bool long_tracks = false) : _angular(angular) {
-        sadvio_ba_config cfg{device, 0, 1, long_tracks ? SADVIO_CFG_LONG_TRACKS : 0};
-        if (sadvio_ba_create(&cfg, &_h) != SADVIO_OK) throw std::runtime_error("sadvio: no usable gfx950 device");
+    // asked for covariances yet, and is marginalised, sparsified and given priors on its long tracks only with long_track_priors
+    // (SADVIO_CFG_LONG_TRACK_PRIORS; needs long_tracks)
+    explicit HipOptimizer(int device = 0, bool angular = false, bool long_tracks = false, bool long_track_priors = false) : _angular(angular) {
+        sadvio_ba_config cfg{device, 0, 1, (long_tracks ? SADVIO_CFG_LONG_TRACKS : 0) | (long_track_priors ? SADVIO_CFG_LONG_TRACK_PRIORS : 0)};
+        const int rc = sadvio_ba_create(&cfg, &_h);
+        if (rc == SADVIO_E_INVALID_ARG) throw std::runtime_error(std::string("sadvio: ") + sadvio_ba_last_error(nullptr));
+        if (rc != SADVIO_OK) throw std::runtime_error("sadvio: no usable gfx950 device");
     }
     ~HipOptimizer() { sadvio_ba_destroy(_h); }
     HipOptimizer(const HipOptimizer&) = delete;

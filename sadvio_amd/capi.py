@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("SADVIO_BA_LIB") or os.path.join(_HERE, "csrc", "libsa
 
 SADVIO_OK = 0
 CFG_LONG_TRACKS = 1   # sadvio_ba_config.reserved: SADVIO_CFG_LONG_TRACKS
+CFG_LONG_TRACK_PRIORS = 2   # ... SADVIO_CFG_LONG_TRACK_PRIORS (with CFG_LONG_TRACKS)
 E_INVALID_ARG, E_NOT_USABLE, E_HIP, E_RCCL, E_NO_DEVICE, E_STATE, E_REFUSED = -1, -2, -3, -4, -5, -6, -7
 FACTOR_PIXEL, FACTOR_ANGULAR = 0, 1
 TERM_NAMES = {0: "NO_CONVERGENCE", 1: "FUNCTION_TOL", 2: "PARAMETER_TOL", 3: "GRADIENT_TOL", 4: "MIN_RADIUS",
@@ -475,12 +476,18 @@ def _ptr(a: Optional[np.ndarray]):
 class Backend:
     """Thin OO wrapper of one `sadvio_ba_handle` (one HIP stream, device-resident windows)."""
 
-    def __init__(self, device: int = 0, profile_kernels: bool = False, use_graph: bool = False, long_tracks: bool = False):
-        """long_tracks: SADVIO_CFG_LONG_TRACKS, the handle accepts landmarks with more than 64 observations."""
+    def __init__(self, device: int = 0, profile_kernels: bool = False, use_graph: bool = False, long_tracks: bool = False,
+                 long_track_priors: bool = False):
+        """long_tracks: SADVIO_CFG_LONG_TRACKS, the handle accepts landmarks with more than 64 observations.
+        long_track_priors: SADVIO_CFG_LONG_TRACK_PRIORS (needs long_tracks), marginalize, sparsify and the prior setters serve them."""
         self.lib = load_library()
-        cfg = Config(device=device, profile_kernels=int(profile_kernels), use_graph=int(use_graph), reserved=CFG_LONG_TRACKS if long_tracks else 0)
+        flags = (CFG_LONG_TRACKS if long_tracks else 0) | (CFG_LONG_TRACK_PRIORS if long_track_priors else 0)
+        cfg = Config(device=device, profile_kernels=int(profile_kernels), use_graph=int(use_graph), reserved=flags)
         self.h = C.c_void_p()
         rc = self.lib.sadvio_ba_create(C.byref(cfg), C.byref(self.h))
+        if rc == E_INVALID_ARG:
+            msg = self.lib.sadvio_ba_last_error(None)
+            raise SadvioError(f"sadvio_ba_create failed: rc={rc}: {msg.decode() if msg else ''}")
         if rc != SADVIO_OK:
             raise SadvioError(f"sadvio_ba_create failed: rc={rc} (no gfx950 device? there is no CPU fallback)")
         self.windows: List[FlatWindow] = []

@@ -9,6 +9,11 @@
 #include "solve_driver.h"
 #include "layout_driver.h"
 
+namespace {
+// why sadvio_ba_create refused its configuration: there is no handle to hold the text, sadvio_ba_last_error(NULL) returns it
+thread_local std::string create_err;
+}  // namespace
+
 extern "C" {
 
 int sadvio_ba_device_count(void) {
@@ -43,6 +48,11 @@ void sadvio_ba_default_options(sadvio_solve_options* o) {
 int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
     if (!out) return SADVIO_E_INVALID_ARG;
     *out = nullptr;
+    create_err.clear();
+    if (cfg && (cfg->reserved & SADVIO_CFG_LONG_TRACK_PRIORS) && !(cfg->reserved & SADVIO_CFG_LONG_TRACKS)) {
+        create_err = "create: SADVIO_CFG_LONG_TRACK_PRIORS needs SADVIO_CFG_LONG_TRACKS (a handle without the long path has no long track to carry a prior on)";
+        return SADVIO_E_INVALID_ARG;
+    }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return SADVIO_E_NO_DEVICE;
     int dev = cfg ? cfg->device : 0;
@@ -57,6 +67,8 @@ int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
     if (cfg) h->cfg = *cfg;
     // long tracks are served by handles that ask for them: every other handle refuses a 65th observation as it always did
     if (h->cfg.reserved & SADVIO_CFG_LONG_TRACKS) h->env.long_min = h->env.long_min_env ? h->env.long_min_env : MAX_LMK_OBS + 1;
+    // ... and marginalised, sparsified and held by priors on handles that ask for that as well: every other handle keeps those refusals
+    h->env.long_priors = (h->cfg.reserved & SADVIO_CFG_LONG_TRACK_PRIORS) != 0;
     h->device = dev;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return SADVIO_E_HIP; }
     if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) h->side = nullptr;   // optional: without it everything is serial
@@ -345,7 +357,7 @@ int sadvio_ba_set_dense_prior(sadvio_ba_handle* h, int32_t w, int32_t n_full, in
         for (int i = 0; i < n_keep; i++) {
             if (lmk_col[i] < 0) continue;
             if (lmk_index[i] < 0 || lmk_index[i] >= d.n_lmk || lmk_col[i] + 3 > n) { h->err = "set_dense_prior: kept landmark out of range"; return SADVIO_E_INVALID_ARG; }
-            if (lmk_is_long(h, w, lmk_index[i])) {
+            if (lmk_is_refused_long(h, w, lmk_index[i])) {   // (SADVIO_CFG_LONG_TRACK_PRIORS: kept like any landmark, layout_reduced_plan)
                 h->err = "set_dense_prior: landmark " + std::to_string(lmk_index[i]) + " is a long track (more than 64 observations): it cannot be kept in the reduced system";
                 return SADVIO_E_INVALID_ARG;
             }
@@ -408,18 +420,19 @@ int sadvio_ba_set_sparse_priors(sadvio_ba_handle* h, int32_t w, int32_t n, const
             return SADVIO_E_INVALID_ARG;
         }
     }
-    // long tracks (long_kernels.h) carry real observations only and are never held in the reduced system
+    // long tracks (long_kernels.h) carry real observations only; they are held in the reduced system on a handle created with
+    // SADVIO_CFG_LONG_TRACK_PRIORS only (there a pose-to-landmark factor on one holds it as well: layout_views)
     if (h->env.long_min > 0 && h->world == 1 && !h->coll_fn) {
         const std::vector<int32_t>& op = h->src[w].lmk_obs_ptr;
         std::vector<int> pseudo(std::max(d.n_lmk, 1), 0);
         for (int i = 0; i < n; i++) {
             const sadvio_sparse_prior& s = f[i];
             if (s.type == SADVIO_SPARSE_IMU_PRIOR || s.type == SADVIO_SPARSE_RELATIVE_POSE) continue;
-            if (lmk_is_long(h, w, s.lmk0) || (s.type == SADVIO_SPARSE_LMK_TO_LMK && lmk_is_long(h, w, s.lmk1))) {
+            if (lmk_is_refused_long(h, w, s.lmk0) || (s.type == SADVIO_SPARSE_LMK_TO_LMK && lmk_is_refused_long(h, w, s.lmk1))) {
                 h->err = "set_sparse_priors: factor " + std::to_string(i) + " touches a long track (a landmark with more than 64 observations)";
                 return SADVIO_E_INVALID_ARG;
             }
-            if (s.type == SADVIO_SPARSE_POSE_TO_LMK && (int)op.size() > s.lmk0 + 1 && op[s.lmk0 + 1] - op[s.lmk0] + (pseudo[s.lmk0] += 2) > MAX_LMK_OBS) {
+            if (s.type == SADVIO_SPARSE_POSE_TO_LMK && !lmk_is_long(h, w, s.lmk0) && (int)op.size() > s.lmk0 + 1 && op[s.lmk0 + 1] - op[s.lmk0] + (pseudo[s.lmk0] += 2) > MAX_LMK_OBS) {
                 h->err = "set_sparse_priors: factor " + std::to_string(i) + " would make its landmark a long track (more than 64 observations with the factors' pseudo-observations)";
                 return SADVIO_E_INVALID_ARG;
             }
@@ -443,7 +456,10 @@ int sadvio_ba_marginalize(sadvio_ba_handle* h, int32_t w, const sadvio_marg_requ
     if (h->defer) { h->err = "marginalize between begin_update and commit_update"; return SADVIO_E_STATE; }
     if (!rq || w < 0 || w >= (int)h->plan.wins.size()) { h->err = "marginalize: bad argument"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "marginalize: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
-    if (int rc = refuse_long(h, w, "marginalize")) return rc;
+    // (SADVIO_CFG_LONG_TRACK_PRIORS: served. marg_layout lists one item per observation from lmk_ob / lmk_oe / obs_perm, which hold a long
+    // track's observations like any others, and k_marg_obs takes an item by its device index: nothing there walks a lane group)
+    if (!h->env.long_priors)
+        if (int rc = refuse_long(h, w, "marginalize")) return rc;
     return marginalize(h, w, rq, res, lmk_col_out, J_out, r0_out);
 }
 
@@ -509,7 +525,7 @@ int sadvio_ba_sparsify(sadvio_ba_handle* h, int32_t w, int32_t vio, int32_t nf, 
     if (w < 0 || w >= (int)h->plan.wins.size() || !n_out || !out || n_keep < 0 || (n_keep > 0 && (!lmk_index || !lmk_col))) { h->err = "sparsify: bad argument"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "sparsify: the window is sharded over several GPUs (linearisation values of a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
     for (int i = 0; i < n_keep; i++)
-        if (lmk_is_long(h, w, lmk_index[i])) { h->err = "sparsify: landmark " + std::to_string(lmk_index[i]) + " is a long track (more than 64 observations)"; return SADVIO_E_INVALID_ARG; }
+        if (lmk_is_refused_long(h, w, lmk_index[i])) { h->err = "sparsify: landmark " + std::to_string(lmk_index[i]) + " is a long track (more than 64 observations)"; return SADVIO_E_INVALID_ARG; }
     return sparsify(h, w, vio, nf, n, J, kf_keep, kf_col, n_keep, lmk_index, lmk_col, n_out, out);
 }
 
@@ -1181,7 +1197,8 @@ int sadvio_ba_get_kernel_times(sadvio_ba_handle* h, int32_t cap, const char** na
     return n;
 }
 
-const char* sadvio_ba_last_error(sadvio_ba_handle* h) { return h ? h->err.c_str() : "null handle"; }
+// (a NULL handle: why this thread's last sadvio_ba_create refused its configuration, if it did)
+const char* sadvio_ba_last_error(sadvio_ba_handle* h) { return h ? h->err.c_str() : (create_err.empty() ? "null handle" : create_err.c_str()); }
 const char* sadvio_ba_version(void) { return "sadvio-ba-mi355x 0.5 (gfx950)"; }
 
 }  // extern "C"

@@ -265,6 +265,7 @@ struct EnvCfg {
     int long_min = 0;   // 0: the handle was created without SADVIO_CFG_LONG_TRACKS (no long path); else 65, or SADVIO_LONG_MIN in [2, 65] (tests, A/B timing): a landmark
                         // with at least this many observations takes the long path (long_kernels.h). Set by sadvio_ba_create, behind read()
     int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range)
+    bool long_priors = false;   // SADVIO_CFG_LONG_TRACK_PRIORS: marginalize, sparsify and the prior setters serve long tracks. Set by sadvio_ba_create
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {
@@ -416,6 +417,9 @@ int refuse_long(sadvio_ba_handle* h, int w, const char* what) {
 bool lmk_is_long(const sadvio_ba_handle* h, int w, int l) {
     return w >= 0 && w < (int)h->src.size() && src_lmk_is_long(h->src[w], l, h->env.long_min, h->world, h->coll_fn != nullptr);
 }
+// ... and is it one that this handle's back-end calls (marginalize, sparsify, the prior setters) refuse: every long track, unless the
+// handle was created with SADVIO_CFG_LONG_TRACK_PRIORS
+bool lmk_is_refused_long(const sadvio_ba_handle* h, int w, int l) { return !h->env.long_priors && lmk_is_long(h, w, l); }
 
 struct ScopedTimer {
     sadvio_ba_handle* h;

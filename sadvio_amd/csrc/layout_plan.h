@@ -88,6 +88,7 @@ struct LayoutIn {
     bool contig_tiles = false, no_lpt = false, no_pre = false;   // no_pre decides pre_ok only
     int long_min = 0;   // 0: no long path (a landmark with more than 64 observations is refused); else a landmark with at least this many observations
                         // is a long track (SADVIO_CFG_LONG_TRACKS: 65, or SADVIO_LONG_MIN)
+    bool long_priors = false;   // SADVIO_CFG_LONG_TRACK_PRIORS: a prior may keep a long track in the reduced system (false: such a prior is refused)
 };
 
 struct DensePrep { long long off; int nf, n, w; };   // a window's dense prior in dp_data: offset, rows, columns, window
@@ -168,6 +169,8 @@ inline int check_flat_window(const sadvio_flat_window& F, int w, std::string& er
     return SADVIO_OK;
 }
 
+inline bool src_lmk_is_long(const SrcWin& S, int l, int long_min, int world, bool has_coll);   // below, with layout_long
+
 // Views of the windows as they are tiled. Cameras with equal (K, T, sigma) are stored once. Which sparse factors ride the Schur
 // elimination as pseudo-observations: PoseToLandmark factors whose landmark is free and not held in the reduced system for another
 // reason (dense prior, landmark prior / landmark chain factor).
@@ -213,6 +216,9 @@ inline void layout_views(const LayoutIn& in, LayoutPlan& P) {
         for (const auto& s : sp) {
             if (s.type == SADVIO_SPARSE_LMK_PRIOR) held[s.lmk0] = 1;
             if (s.type == SADVIO_SPARSE_LMK_TO_LMK) { held[s.lmk0] = 1; held[s.lmk1] = 1; }
+            // a long track carries real observations only: a pose-to-landmark factor on one holds it in the reduced system and becomes
+            // a listed factor whose second block is a reduced column (without long_priors layout_long refuses the factor, as it did)
+            if (s.type == SADVIO_SPARSE_POSE_TO_LMK && in.long_priors && src_lmk_is_long(S, s.lmk0, in.long_min, in.world, in.has_coll)) held[s.lmk0] = 1;
         }
         std::vector<std::vector<int>> extra(S.v.n_lmk);  // per landmark: the window's sparse factors to append
         bool any = false;
@@ -691,8 +697,11 @@ inline int layout_reduced_plan(const LayoutIn& in, LayoutPlan& P, std::string& e
             err = "the handle's prior changed after set_dense_prior(SADVIO_PRIOR_RESIDENT) attached it to a window: attach it again"; return SADVIO_E_STATE;
         }
     }
-    // a long track is eliminated by its own kernels: it cannot be held in the reduced system (refused before anything of the plan changes)
-    if (P.n_long > 0)
+    // without long_priors a long track cannot be held in the reduced system (refused before anything of the plan changes). With it
+    // keep_landmark below takes a long track as it takes any landmark: lmk_red, lmk_const_red = 2 and ALL its observations on the kept
+    // list (k_build_kept: one thread each, no per-landmark cap); it stays on the long list, whose kernels sum its pose-pose part and
+    // take its step from the reduced solution (long_kernels.h, lcode == 2)
+    if (P.n_long > 0 && !in.long_priors)
         for (int w = 0; w < n_windows && w < (int)dpriors.size(); w++) {
             const int lb = P.wins[w].d.lmk_base;
             const DensePriorHost& D = dpriors[w];

@@ -10,6 +10,10 @@
 // like a global-mode tile's. A track of at most LONG_THREADS observations keeps its linearisation in registers between the passes;
 // longer ones linearise twice. Not tuned: DESIGN.md "Long tracks".
 //
+// A long track that a prior keeps in the reduced system (lmk_const = 2; handles created with SADVIO_CFG_LONG_TRACK_PRIORS) stays on the
+// long list: k_long_lin adds its pose-pose part and its cost and eliminates nothing, k_build_kept adds its rows and columns from the
+// kept list, k_long_back takes its step from the reduced solution. DESIGN.md "Long tracks under a prior".
+//
 // Window totals: the linearisation's cost, fixed cost and gradient maximum are added to the k_build partial of the window's first
 // tile (k_solve sums those; k_long_lin runs behind k_build on the stream), the back-substitution's four sums to the slot's IterAcc
 // (behind k_solve, which zeroes them), as k_prior_m and k_line_eval do.
@@ -106,8 +110,13 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A
     long_stage_cams(P, W, camTab);
     for (int i = tid; i < 18 * T.n_kf; i += LONG_THREADS) Y[i] = 0.0;
     const int gl = T.gl, ob = P.lmk_ob[gl], oe = ob + T.n_obs;
-    const int lcode = P.lmk_const ? P.lmk_const[gl] : 0;   // 0 free, 1 constant (a long track is never kept in the reduced system)
-    const bool lfree = lcode == 0;
+    // 0 free (eliminated here), 1 constant, 2 kept in the reduced system by a prior (layout_reduced_plan: keep_landmark). A kept track
+    // is not eliminated: as for a kept landmark of a tile (k_build), its pose-pose part goes the usual way with r~ = r, its observations
+    // are counted in the cost, and its rows / columns, its gradient and its diagonal are added by k_build_kept, one thread per
+    // observation. So it forms no H_ll, no g_l, no Y and no Schur pairs, writes no s_lmk and adds nothing to gmax here (the reduced
+    // gradient carries g_l)
+    const int lcode = P.lmk_const ? P.lmk_const[gl] : 0;
+    const bool lfree = lcode == 0, lkept = lcode == 2;
     const double* xl = P.xl + (long long)st.cur * P.xl_stride + 3 * (long long)gl;
     const double pw[3] = {P.lmk_p[3 * (long long)gl] + xl[0], P.lmk_p[3 * (long long)gl + 1] + xl[1], P.lmk_p[3 * (long long)gl + 2] + xl[2]};
     const double* ptab = P.ptab + (long long)st.cur * P.ptab_stride;
@@ -121,6 +130,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A
         long_linearize<FACTOR>(P, ptab, camTab, W, o, pw, lfree, lcode != 1, L);
         if (L.counted) acc[9] += L.rho;
         else { acc[10] += L.rho; L.r[0] = 0.0; L.r[1] = 0.0; }
+        if (lkept) continue;   // the costs only
         acc[0] += L.Jl[0] * L.Jl[0] + L.Jl[3] * L.Jl[3];
         acc[1] += L.Jl[0] * L.Jl[1] + L.Jl[3] * L.Jl[4];
         acc[2] += L.Jl[0] * L.Jl[2] + L.Jl[3] * L.Jl[5];
@@ -147,7 +157,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A
         }
         long_damped_inverse(P, H, s, st.radius, Mi);
     }
-    li_vec(Mi, g, gam);
+    li_vec(Mi, g, gam);   // (zero unless the track is eliminated here)
     if (tid == 0) {
         // the window's totals: onto the k_build partial of its first tile (complete: k_build ran before this kernel)
         TileAcc* ta = P.tacc + (long long)(slot & 1) * P.n_tiles + W.tile_begin;
@@ -168,11 +178,16 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A
             if (!L.counted) { L.r[0] = 0.0; L.r[1] = 0.0; }
         }
         if (L.row < 0) continue;   // constant key-frame
-        double N[6];
-        li_row(Mi, L.Jl[0], L.Jl[1], L.Jl[2], N);
-        li_row(Mi, L.Jl[3], L.Jl[4], L.Jl[5], N + 3);
-        const double rt0 = L.r[0] - (N[0] * gam[0] + N[1] * gam[1] + N[2] * gam[2]);
-        const double rt1 = L.r[1] - (N[3] * gam[0] + N[4] * gam[1] + N[5] * gam[2]);
+        // N = Jl Li^T and the reduced residual r~ = r - N gamma of an eliminated track; a constant or kept one has no elimination
+        // term: gred = gfull
+        double N[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        double rt0 = L.r[0], rt1 = L.r[1];
+        if (lfree) {
+            li_row(Mi, L.Jl[0], L.Jl[1], L.Jl[2], N);
+            li_row(Mi, L.Jl[3], L.Jl[4], L.Jl[5], N + 3);
+            rt0 -= N[0] * gam[0] + N[1] * gam[1] + N[2] * gam[2];
+            rt1 -= N[3] * gam[0] + N[4] * gam[1] + N[5] * gam[2];
+        }
         const int base = L.row * dpf;
         double* y = Y + 18 * (size_t)A.slot[T.slot_off + (o - ob)];
 #pragma unroll
@@ -189,7 +204,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A
             }
         }
     }
-    if (!lfree) return;   // a constant landmark couples nothing
+    if (!lfree) return;   // a constant landmark couples nothing; a kept one couples through its own columns (k_build_kept)
     __syncthreads();
     // the Schur term -Y_a Y_b^T of every pair of free observing key-frames a >= b (the list ascends: so do their rows)
     const int wv = tid >> 6, ln = tid & 63;
@@ -227,8 +242,11 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_back(DevPtrs P, LongArgs 
     double* red = camTab + MAX_WIN_CAM * 17;
     long_stage_cams(P, W, camTab);
     const int gl = T.gl, ob = P.lmk_ob[gl], oe = ob + T.n_obs;
+    // 0 free, 1 constant, 2 kept in the reduced system by a prior: its step is part of the reduced solution (k_solve counted |step|^2
+    // there), so no H_ll, no t and no inverse are formed; |candidate|^2 is counted here, as k_backsub does for the kept landmarks of
+    // its tiles (the long path runs on one device only: no rank to choose)
     const int lcode = P.lmk_const ? P.lmk_const[gl] : 0;
-    const bool lfree = lcode == 0;
+    const bool lfree = lcode == 0, lkept = lcode == 2;
     const int cur = st.cur;
     const double* xl = P.xl + (long long)cur * P.xl_stride + 3 * (long long)gl;
     double* xlc = P.xl + (long long)(1 - cur) * P.xl_stride + 3 * (long long)gl;
@@ -245,7 +263,8 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_back(DevPtrs P, LongArgs 
     ObsLin L;
     L.valid = false;
     double e0 = 0.0, e1 = 0.0;   // predicted residual r + Jp dp of the observation
-    for (int o = ob + tid; o < oe; o += LONG_THREADS) {
+    // (a kept track needs none of the sums: the pass only leaves the linearisation in registers for pass 2, where it stays there)
+    for (int o = ob + tid; o < oe && !(lkept && !single); o += LONG_THREADS) {
         long_linearize<FACTOR>(P, ptab, camTab, W, o, pw, lcode != 1, lcode != 1, L);
         if (!L.counted) { L.r[0] = 0.0; L.r[1] = 0.0; }
         e0 = L.r[0]; e1 = L.r[1];
@@ -254,6 +273,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_back(DevPtrs P, LongArgs 
 #pragma unroll
             for (int i = 0; i < 6; i++) { e0 += L.Jp[i] * d[i]; e1 += L.Jp[6 + i] * d[i]; }
         }
+        if (lkept) continue;
         acc[0] += L.Jl[0] * L.Jl[0] + L.Jl[3] * L.Jl[3];
         acc[1] += L.Jl[0] * L.Jl[1] + L.Jl[3] * L.Jl[4];
         acc[2] += L.Jl[0] * L.Jl[2] + L.Jl[3] * L.Jl[5];
@@ -264,22 +284,30 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_back(DevPtrs P, LongArgs 
         acc[7] += L.Jl[1] * e0 + L.Jl[4] * e1;
         acc[8] += L.Jl[2] * e0 + L.Jl[5] * e1;
     }
-    long_block_sum(acc, red);
-    double Mi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (lfree) {
-        const double s[3] = {P.s_lmk[3 * (long long)gl], P.s_lmk[3 * (long long)gl + 1], P.s_lmk[3 * (long long)gl + 2]};
-        long_damped_inverse(P, acc, s, st.radius, Mi);
+    double d0, d1, d2;
+    if (lkept) {   // (the same branch in every thread of the workgroup: no barrier of long_block_sum is skipped by some)
+        // the landmark's step from the reduced solution (k_solve left it behind the poses' steps)
+        const double* dr = dp + P.lmk_red[gl];
+        d0 = dr[0]; d1 = dr[1]; d2 = dr[2];
+    } else {
+        long_block_sum(acc, red);
+        double Mi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (lfree) {
+            const double s[3] = {P.s_lmk[3 * (long long)gl], P.s_lmk[3 * (long long)gl + 1], P.s_lmk[3 * (long long)gl + 2]};
+            long_damped_inverse(P, acc, s, st.radius, Mi);
+        }
+        // delta_l = -M^-1 t = -Li^T (Li t)
+        double ut[3], vt[3];
+        li_vec(Mi, acc + 6, ut);
+        li_tvec(Mi, ut, vt);
+        d0 = -vt[0]; d1 = -vt[1]; d2 = -vt[2];
     }
-    // delta_l = -M^-1 t = -Li^T (Li t)
-    double ut[3], vt[3];
-    li_vec(Mi, acc + 6, ut);
-    li_tvec(Mi, ut, vt);
-    const double d0 = -vt[0], d1 = -vt[1], d2 = -vt[2];
     const double c0 = x0[0] + d0, c1 = x0[1] + d1, c2 = x0[2] + d2;
     double sums[4] = {0.0, 0.0, 0.0, 0.0};   // candidate cost | model cost change | |step|^2 | |candidate|^2
     if (tid == 0) {
         xlc[0] = c0; xlc[1] = c1; xlc[2] = c2;
         if (lfree) { sums[2] = d0 * d0 + d1 * d1 + d2 * d2; sums[3] = c0 * c0 + c1 * c1 + c2 * c2; }
+        else if (lkept) sums[3] = c0 * c0 + c1 * c1 + c2 * c2;
     }
     // pass 2: model cost change and the residual at the candidate of every block of the program
     const double pwc[3] = {p0[0] + c0, p0[1] + c1, p0[2] + c2};
