@@ -59,11 +59,13 @@ typedef struct sadvio_ba_config {
     int32_t profile_kernels; /* 1: bracket every kernel class with hipEvents (see get_kernel_times) */
     int32_t use_graph;       /* 1: replay the iteration sequence from a captured hipGraph */
     int32_t reserved;        /* flags; 0 = none. SADVIO_CFG_LONG_TRACKS: accept landmarks with more than 64 observations (see sadvio_flat_window);
-                                SADVIO_CFG_LONG_TRACK_PRIORS: ... and marginalise, sparsify and hold them under priors. A refused combination:
+                                SADVIO_CFG_LONG_TRACK_PRIORS: ... and marginalise, sparsify and hold them under priors;
+                                SADVIO_CFG_LONG_TRACK_COVARIANCE: ... and serve covariances of windows that hold them. A refused combination:
                                 SADVIO_E_INVALID_ARG, the text through sadvio_ba_last_error(NULL) */
 } sadvio_ba_config;
 #define SADVIO_CFG_LONG_TRACKS 1
 #define SADVIO_CFG_LONG_TRACK_PRIORS 2 /* with SADVIO_CFG_LONG_TRACKS: marginalize, sparsify and the prior setters serve long tracks */
+#define SADVIO_CFG_LONG_TRACK_COVARIANCE 4 /* with SADVIO_CFG_LONG_TRACKS: sadvio_ba_covariance and _covariance_cross serve windows with long tracks */
 
 /*
  * One sliding window, flattened (SoA, index based). Replaces the object-graph walk of
@@ -99,6 +101,17 @@ typedef struct sadvio_ba_config {
  *   per observation of it adding its rows (k_build_kept); its pose-pose part is still summed by the long kernels.
  *   sadvio_ba_covariance, _covariance_batch, _covariance_cross, sadvio_ba_marginalize_relative and _relative_batch refuse a window
  *   with long tracks as before, with this flag or without it.
+ *
+ * Covariances of windows with long tracks. A handle created with SADVIO_CFG_LONG_TRACKS | SADVIO_CFG_LONG_TRACK_COVARIANCE (without
+ * SADVIO_CFG_LONG_TRACKS: sadvio_ba_create fails with SADVIO_E_INVALID_ARG, the text through sadvio_ba_last_error(NULL)) serves
+ * sadvio_ba_covariance and sadvio_ba_covariance_cross on a window that holds long tracks: both assemblies (SADVIO_COV_SQRT), both
+ * routes (dense, band) and the retry, with the bit guarantees of those calls. A long track's landmark block, its cross blocks and the
+ * innovation of a candidate observation of it are what they are for any landmark: eliminated, constant (zeros), or — together with
+ * SADVIO_CFG_LONG_TRACK_PRIORS — kept in the reduced system by a prior. The flag is independent of SADVIO_CFG_LONG_TRACK_PRIORS
+ * (reserved = 1 | 4 and 1 | 2 | 4 are both valid). A handle without it keeps every refusal above with the same text. With it,
+ * sadvio_ba_covariance_batch (its kernels hold S in LDS and walk the landmark tiles only), sadvio_ba_marginalize_relative and
+ * sadvio_ba_marginalize_relative_batch still refuse a window with long tracks, with the same text. On any handle a window without
+ * long tracks takes the launches it always took and returns the same bits. DESIGN.md "Covariances of windows with long tracks".
  * A window sharded over several GPUs has no long path: it is refused at 65 observations whatever the flags. On a handle with the flag, SADVIO_LONG_MIN in the environment (read by sadvio_ba_create; an
  * integer in [2, 65], default 65; tests and A/B timing) sends every landmark with at least that many observations down the long path.
  */
@@ -735,7 +748,10 @@ typedef struct sadvio_cov_request {
  * bit, and a window refused before pays one more assembly (and one further wait) before the same refusal; 1, the square-root
  * assembly from the start (any front-end that does not cull landmarks closer than a few centimetres: the plain form's loss is silent
  * before it is refused); 0, never. In sadvio_ba_get_kernel_times the assembly shows as the class cov_assemble_sqrt in place of
- * cov_assemble (after a retry, both). */
+ * cov_assemble (after a retry, both).
+ * A window with long tracks (see sadvio_flat_window) is refused with SADVIO_E_INVALID_ARG and a text that names them, unless the handle
+ * was created with SADVIO_CFG_LONG_TRACK_COVARIANCE: then it is served as any window, its long tracks through two kernels of their
+ * own (classes k_cov_long, inside the assembly's span, and k_cov_lmk_long in sadvio_ba_get_kernel_times). */
 int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_request *rq, double *kf_cov, double *pair_cov,
                          double *lmk_cov, int32_t *n_lmk_singular);
 
@@ -772,7 +788,9 @@ int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_reques
  * that is not bandable.
  * n_item = 0 returns SADVIO_OK and touches nothing.
  * No floating-point atomics: two calls return the same bits, and an item's bits depend neither on the other items of the call nor
- * on its position among them. The solve's deltas, summaries, trace and the handle's prior are left untouched. */
+ * on its position among them. The solve's deltas, summaries, trace and the handle's prior are left untouched.
+ * A window with long tracks is refused (SADVIO_E_INVALID_ARG, a text that names them) on every handle, one created with
+ * SADVIO_CFG_LONG_TRACK_COVARIANCE included: call sadvio_ba_covariance per window there. */
 #define SADVIO_COV_ROUTE_NONE  0
 #define SADVIO_COV_ROUTE_LDS   1
 #define SADVIO_COV_ROUTE_DENSE 2
@@ -825,7 +843,9 @@ int sadvio_ba_covariance_batch(sadvio_ba_handle *h, int32_t n_item, sadvio_cov_b
  * summaries, trace, the handle's prior and every bit sadvio_ba_covariance / _batch return are left as they are.
  * In sadvio_ba_get_kernel_times the step shows as the class cov_cross, on the band route also cov_band_rows. A block row of more
  * than 16 384 doubles (d = 6: N_p > 2 730; d = 15: N_p > 1 092) is read from global memory instead of LDS; the environment variable
- * SADVIO_COV_CROSS_STAGE (read when the handle is created) lowers that figure (tests). */
+ * SADVIO_COV_CROSS_STAGE (read when the handle is created) lowers that figure (tests).
+ * A window with long tracks: refused as by sadvio_ba_covariance, and served on a handle created with
+ * SADVIO_CFG_LONG_TRACK_COVARIANCE — a candidate on a long track is a candidate like any other. */
 #define SADVIO_CROSS_OK            0
 #define SADVIO_CROSS_LMK_SINGULAR  1
 #define SADVIO_CROSS_PROJ_INVALID  2

@@ -297,11 +297,14 @@ inline bool nofov_flatten(const LocalMapSnapshot& map, int f, int fp, const Pose
 
 class HipOptimizer {
   public:
-    // long_tracks: landmarks with more than 64 observations are accepted (SADVIO_CFG_LONG_TRACKS, sadvio_ba.h); such a window cannot be
-    // asked for covariances yet, and is marginalised, sparsified and given priors on its long tracks only with long_track_priors
-    // (SADVIO_CFG_LONG_TRACK_PRIORS; needs long_tracks)
-    explicit HipOptimizer(int device = 0, bool angular = false, bool long_tracks = false, bool long_track_priors = false) : _angular(angular) {
-        sadvio_ba_config cfg{device, 0, 1, (long_tracks ? SADVIO_CFG_LONG_TRACKS : 0) | (long_track_priors ? SADVIO_CFG_LONG_TRACK_PRIORS : 0)};
+    // long_tracks: landmarks with more than 64 observations are accepted (SADVIO_CFG_LONG_TRACKS, sadvio_ba.h); such a window is
+    // marginalised, sparsified and given priors on its long tracks only with long_track_priors (SADVIO_CFG_LONG_TRACK_PRIORS), and asked
+    // for covariances (covariance(), covarianceCross(); not the batch call) only with long_track_covariance
+    // (SADVIO_CFG_LONG_TRACK_COVARIANCE). Both need long_tracks and are independent of each other
+    explicit HipOptimizer(int device = 0, bool angular = false, bool long_tracks = false, bool long_track_priors = false,
+                          bool long_track_covariance = false) : _angular(angular) {
+        sadvio_ba_config cfg{device, 0, 1, (long_tracks ? SADVIO_CFG_LONG_TRACKS : 0) | (long_track_priors ? SADVIO_CFG_LONG_TRACK_PRIORS : 0) |
+                                               (long_track_covariance ? SADVIO_CFG_LONG_TRACK_COVARIANCE : 0)};
         const int rc = sadvio_ba_create(&cfg, &_h);
         if (rc == SADVIO_E_INVALID_ARG) throw std::runtime_error(std::string("sadvio: ") + sadvio_ba_last_error(nullptr));
         if (rc != SADVIO_OK) throw std::runtime_error("sadvio: no usable gfx950 device");

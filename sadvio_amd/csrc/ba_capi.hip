@@ -53,6 +53,10 @@ int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
         create_err = "create: SADVIO_CFG_LONG_TRACK_PRIORS needs SADVIO_CFG_LONG_TRACKS (a handle without the long path has no long track to carry a prior on)";
         return SADVIO_E_INVALID_ARG;
     }
+    if (cfg && (cfg->reserved & SADVIO_CFG_LONG_TRACK_COVARIANCE) && !(cfg->reserved & SADVIO_CFG_LONG_TRACKS)) {
+        create_err = "create: SADVIO_CFG_LONG_TRACK_COVARIANCE needs SADVIO_CFG_LONG_TRACKS (a handle without the long path has no long track to form a covariance of)";
+        return SADVIO_E_INVALID_ARG;
+    }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return SADVIO_E_NO_DEVICE;
     int dev = cfg ? cfg->device : 0;
@@ -69,6 +73,8 @@ int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
     if (h->cfg.reserved & SADVIO_CFG_LONG_TRACKS) h->env.long_min = h->env.long_min_env ? h->env.long_min_env : MAX_LMK_OBS + 1;
     // ... and marginalised, sparsified and held by priors on handles that ask for that as well: every other handle keeps those refusals
     h->env.long_priors = (h->cfg.reserved & SADVIO_CFG_LONG_TRACK_PRIORS) != 0;
+    // ... and asked for covariances (the single call and the cross call) on handles that ask for that: independent of the priors' flag
+    h->env.long_cov = (h->cfg.reserved & SADVIO_CFG_LONG_TRACK_COVARIANCE) != 0;
     h->device = dev;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return SADVIO_E_HIP; }
     if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) h->side = nullptr;   // optional: without it everything is serial
@@ -1015,7 +1021,8 @@ extern "C" {
 int sadvio_ba_covariance(sadvio_ba_handle* h, int32_t w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov,
                          int32_t* n_lmk_singular) {
     if (!h) return SADVIO_E_INVALID_ARG;
-    if (int rc = refuse_long(h, w, "covariance")) return rc;
+    if (!h->env.long_cov)   // (SADVIO_CFG_LONG_TRACK_COVARIANCE: served, cov_long_kernels.h)
+        if (int rc = refuse_long(h, w, "covariance")) return rc;
     return cov_run(h, w, rq, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
 }
 
@@ -1045,7 +1052,8 @@ extern "C" {
 int sadvio_ba_covariance_cross(sadvio_ba_handle* h, int32_t w, const sadvio_cov_cross_request* rq, double* cross_cov, double* innov_cov, double* maha2,
                                int32_t* status) {
     if (!h) return SADVIO_E_INVALID_ARG;
-    if (int rc = refuse_long(h, w, "covariance_cross")) return rc;
+    if (!h->env.long_cov)
+        if (int rc = refuse_long(h, w, "covariance_cross")) return rc;
     return covx_run(h, w, rq, cross_cov, innov_cov, maha2, status);
 }
 

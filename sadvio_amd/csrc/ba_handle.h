@@ -197,6 +197,7 @@ struct MargScratch {
 struct CovScratch {
     DevBuf<double> ptab, hll, hinv, ent_w, ent_hpp, S, Sig, lout, V, Lx, G, Z;
     DevBuf<int> status, ent_n, ent_col, step_of;
+    DevBuf<int> is_long;   // windows with long tracks: the landmarks k_cov_long filled (cov_long_kernels.h)
     std::vector<double> h_sig, h_lout;
     // the band route (cov_band_kernels.h): L's band and the inverse pivot blocks | the solved columns of the out-of-band pairs | the
     // gathered blocks; the in-band pair table of k_cov_schur | the gather table | the pivot flag
@@ -266,6 +267,7 @@ struct EnvCfg {
                         // with at least this many observations takes the long path (long_kernels.h). Set by sadvio_ba_create, behind read()
     int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range)
     bool long_priors = false;   // SADVIO_CFG_LONG_TRACK_PRIORS: marginalize, sparsify and the prior setters serve long tracks. Set by sadvio_ba_create
+    bool long_cov = false;      // SADVIO_CFG_LONG_TRACK_COVARIANCE: covariance and covariance_cross serve a window with long tracks. Set by sadvio_ba_create
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {

@@ -6,16 +6,21 @@
 // blocks asked for and nothing else.
 // S and the landmark blocks have two assemblies: the plain one (cov_assemble) and the square-root one (cov_assemble_sqrt), which
 // survives landmarks millimetres from a camera centre; cov_steps says which runs (SADVIO_COV_SQRT) and holds the retry.
+// A window with long tracks (handles created with SADVIO_CFG_LONG_TRACK_COVARIANCE; every other handle is refused in ba_capi.hip) adds
+// cov_assemble_long to either assembly and k_cov_lmk_long to cov_landmarks (cov_long_kernels.h); without long tracks no launch changes.
 // The kernels are cov_kernels.h's; the factorisation of S and the triangular inverse are marg_driver.h's (factor_unpivoted,
 // prior_build_Z: the route sadvio_ba_sparsify takes to Sigma_k = Ak^-1), called as they are. Nothing of the solve is touched: the
 // delta buffers, the final records, the trace and the handle's prior are read only; the work buffers are the handle's CovScratch
 // and, inside the two borrowed routines, MargScratch.
 // Part of the library's single translation unit (ba_capi.hip, which includes it below marg_driver.h); not a public header.
 #pragma once
+#include <cassert>
+#include <climits>
 #include "ba_handle.h"
 #include "cov_band_kernels.h"
 #include "cov_kernels.h"
 #include "cov_kf_lists.h"
+#include "cov_long_kernels.h"
 #include "marg_driver.h"
 
 namespace {
@@ -33,6 +38,7 @@ struct CovRoutes {
     bool band = false;      // the band route; then hb / bw / nb: block half-bandwidth, (hb + 1) * dpf, block column of the sweeps
     int hb = 0, bw = 0, nb = 0, dpf = 6;
     bool sqrt = false;      // the square-root assembly (cov_assemble_sqrt) instead of the plain one
+    int n_long = 0, long_first = 0, long_max_kf = 0;   // long tracks of the window, its first on the long list, LongArgs::max_kf (k_cov_long, k_cov_lmk_long)
 };
 
 // The band route's block column: 6 for dpf 6, 5 for dpf 15 (as k_band_solve)
@@ -88,6 +94,7 @@ CovRoutes cov_routes(const sadvio_ba_handle* h, int w, const sadvio_cov_request*
     R.G = d.n_free_kf <= 8 ? 16 : 64;
     R.band = cov_band_route(h, w, &R.hb, &R.bw);
     R.nb = cov_band_nb(d.dpf); R.dpf = d.dpf;
+    R.long_first = h->plan.wins[w].long_begin; R.n_long = h->plan.wins[w].long_end - R.long_first; R.long_max_kf = h->plan.long_max_kf;
     return R;
 }
 
@@ -99,7 +106,43 @@ CovDev cov_dev(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     C.ent_col = V.ent_col.p; C.ent_w = V.ent_w.p; C.ent_hpp = V.ent_hpp.p;
     C.S = V.S.p; C.Sig = V.Sig.p; C.lout = V.lout.p;
     C.pair_tab = R.band ? V.pair_tab.p : nullptr;
+    C.is_long = R.n_long > 0 ? V.is_long.p : nullptr;
     return C;
+}
+
+// The long list as the covariance kernels take it (the solve plan's LongArgs, solve_driver.h)
+LongArgs cov_long_args(const sadvio_ba_handle* h) {
+    LongArgs A{};
+    A.n_long = h->plan.n_long; A.max_kf = h->plan.long_max_kf;
+    A.rec = h->d_long_rec.p; A.kf = h->d_long_kf.p; A.slot = h->d_long_slot.p;
+    return A;
+}
+
+// On the band route every pair of free key-frames that observe one long track lies inside the band: window_bandwidth counts the
+// track. (Asserted below unless NDEBUG is defined; k_cov_lmk_long reads Sigma_pp at those pairs only.)
+[[maybe_unused]] bool cov_long_in_band(const sadvio_ba_handle* h, int w, const CovRoutes& R) {
+    for (int i = R.long_first; i < R.long_first + R.n_long; i++) {
+        const int* rec = &h->plan.long_rec[(size_t)LONG_REC * i];
+        int lo = INT_MAX, hi = -1;
+        for (int k = 0; k < rec[3]; k++) {
+            const int f = h->plan.kf_fidx[h->plan.long_kf[rec[2] + k]];
+            if (f >= 0) { lo = std::min(lo, f); hi = std::max(hi, f); }
+        }
+        if (hi - lo > R.hb) return false;
+    }
+    return true;
+}
+
+// 2 (long tracks). The window's long tracks into the tables the tile assembly just filled for every other landmark: behind
+// k_cov_tables and the tile assembly, in front of k_cov_schur(_sqrt). Q: the square-root assembly's tables (R.sqrt), else unused.
+int cov_assemble_long(sadvio_ba_handle* h, const CovRoutes& R, const DevPtrs& P, const CovDev& C, const CovSqrtDev& Q) {
+    if (R.n_long == 0) return SADVIO_OK;
+    assert(!R.band || cov_long_in_band(h, C.w, R));
+    HIP_TRY(hipMemsetAsync(C.is_long, 0, sizeof(int) * (size_t)h->plan.wins[C.w].d.n_lmk, h->stream));
+    auto k = R.sqrt ? (R.pix ? k_cov_long<0, true> : k_cov_long<1, true>) : (R.pix ? k_cov_long<0, false> : k_cov_long<1, false>);
+    ScopedTimer t(h, "k_cov_long");
+    hipLaunchKernelGGL(k, dim3(R.n_long), dim3(LONG_THREADS), cov_long_lds_bytes(R.long_max_kf), h->stream, P, C, Q, cov_long_args(h), R.long_first);
+    return SADVIO_OK;
 }
 
 // 2. Allocate; linearise at x*; S = H_pp - sum_l H_pl H_ll^-1 H_lp, full symmetric, in V.S
@@ -111,6 +154,7 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     HIP_TRY(V.hll.alloc(6 * nl)); HIP_TRY(V.hinv.alloc(6 * nl)); HIP_TRY(V.status.alloc(nl)); HIP_TRY(V.ent_n.alloc(nl)); HIP_TRY(V.lout.alloc(9 * nl));
     HIP_TRY(V.ent_col.alloc(no)); HIP_TRY(V.ent_w.alloc(COV_ENT_W * no)); HIP_TRY(V.ent_hpp.alloc(COV_ENT_HPP * no));
     HIP_TRY(V.S.alloc(nn)); HIP_TRY(V.Sig.alloc(nn));
+    if (R.n_long > 0) HIP_TRY(V.is_long.alloc(nl));
     HIP_TRY(hipMemsetAsync(V.S.p, 0, sizeof(double) * nn, h->stream));
     SolveOpts so{};
     so.huber_a = h->cov_huber_a;
@@ -131,9 +175,10 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     hipLaunchKernelGGL(k_cov_tables, dim3((n_tab + 255) / 256), dim3(256), 0, h->stream, P, C, V.ptab.p);
     const int n_tiles = d.tile_end - d.tile_begin;
     if (n_tiles > 0) hipLaunchKernelGGL(R.pix ? k_cov_assemble<0> : k_cov_assemble<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C);
+    if (int rc = cov_assemble_long(h, R, P, C, CovSqrtDev{})) return rc;
     if (R.Np == 0) return SADVIO_OK;
     if (d.n_free_kf > 0) {
-        ScopedTimer ts(h, R.band ? "k_cov_schur" : nullptr);   // (band route: a class of its own inside cov_assemble's span, for the profile)
+        ScopedTimer ts(h, R.band || R.n_long > 0 ? "k_cov_schur" : nullptr);   // (band route, long tracks: a class of its own inside cov_assemble's span, for the profile)
         hipLaunchKernelGGL(k_cov_schur, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C);
     }
     if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
@@ -159,6 +204,7 @@ int cov_assemble_sqrt(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     HIP_TRY(V.ent_col.alloc(no)); HIP_TRY(V.ent_w.alloc(COV_ENT_W * no));
     HIP_TRY(V.sq_jp.alloc(12 * no)); HIP_TRY(V.sq_q.alloc(6 * no)); HIP_TRY(V.sq_ent.alloc(no));
     HIP_TRY(V.S.alloc(nn)); HIP_TRY(V.Sig.alloc(nn));
+    if (R.n_long > 0) HIP_TRY(V.is_long.alloc(nl));
     HIP_TRY(hipMemsetAsync(V.S.p, 0, sizeof(double) * nn, h->stream));
     SolveOpts so{};
     so.huber_a = h->cov_huber_a;
@@ -185,9 +231,10 @@ int cov_assemble_sqrt(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     hipLaunchKernelGGL(k_cov_tables, dim3((n_tab + 255) / 256), dim3(256), 0, h->stream, P, C, V.ptab.p);
     const int n_tiles = d.tile_end - d.tile_begin;
     if (n_tiles > 0) hipLaunchKernelGGL(R.pix ? k_cov_assemble_sqrt<0> : k_cov_assemble_sqrt<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C, Q);
+    if (int rc = cov_assemble_long(h, R, P, C, Q)) return rc;
     if (R.Np == 0) { HIP_TRY(hipGetLastError()); return SADVIO_OK; }
     if (d.n_free_kf > 0) {
-        ScopedTimer ts(h, R.band ? "k_cov_schur_sqrt" : nullptr);
+        ScopedTimer ts(h, R.band || R.n_long > 0 ? "k_cov_schur_sqrt" : nullptr);
         hipLaunchKernelGGL(k_cov_schur_sqrt, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C, Q);
     }
     if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
@@ -264,6 +311,10 @@ int cov_landmarks(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
     const CovDev C = cov_dev(h, w, R);
     const int per = COV_THREADS / R.G;
+    if (R.n_long > 0) {   // the long tracks' blocks: k_cov_lmk below skips them (CovDev::is_long)
+        ScopedTimer tl(h, "k_cov_lmk_long");
+        hipLaunchKernelGGL(R.sqrt ? k_cov_lmk_long<true> : k_cov_lmk_long<false>, dim3(R.n_long), dim3(LONG_THREADS), 0, h->stream, P, C, cov_long_args(h), R.long_first);
+    }
     ScopedTimer t(h, "k_cov_lmk");
     if (R.sqrt) hipLaunchKernelGGL((R.G == 16 ? k_cov_lmk<16, true> : k_cov_lmk<64, true>), dim3((d.n_lmk + per - 1) / per), dim3(COV_THREADS), 0, h->stream, P, C);
     else hipLaunchKernelGGL(R.G == 16 ? k_cov_lmk<16> : k_cov_lmk<64>, dim3((d.n_lmk + per - 1) / per), dim3(COV_THREADS), 0, h->stream, P, C);

@@ -23,6 +23,8 @@
 // S and the landmark blocks have a second assembly, the square-root one (k_cov_assemble_sqrt, k_cov_schur_sqrt, k_cov_lmk<G, true>,
 // further down): the same quantities without the difference above, for windows with landmarks millimetres from a camera centre.
 // cov_driver.h (cov_steps) says which runs. The kernels of the plain assembly are untouched by it.
+// Long tracks (landmarks the planner keeps out of the tiles) get their rows of the same tables from k_cov_long and their landmark
+// blocks from k_cov_lmk_long (cov_long_kernels.h); every other kernel here reads them like any landmark.
 // A landmark whose H_ll is not positive definite (one observation; a pivot within 64 ulps of its diagonal entry) is left out of H
 // together with its observations and reported as singular. Part of the library's single translation unit; not a public header.
 #pragma once
@@ -54,6 +56,7 @@ struct CovDev {
     const double* Sig;       // [Np][Np] Sigma_pp
     double* lout;            // [n_lmk][9]
     const int* pair_tab;     // band route: [workgroups of k_cov_schur][2] the in-band key-frame pairs (a, b), a >= b; else null
+    int* is_long;            // [n_lmk] 1: a long track, filled by k_cov_long and left to k_cov_lmk_long (cov_long_kernels.h); null: the window has none
 };
 
 __global__ void k_cov_tables(DevPtrs P, CovDev C, double* ptab) {
@@ -587,50 +590,11 @@ __global__ void k_cov_dense(DevPtrs P, CovDev C) {
 // 6 rows x 48 contiguous bytes; the matrix stays resident in L2 (4 MB per XCD), so HBM sees it once per XCD.
 // SQRT (the square-root assembly): ent_w holds C and hll holds R; the same gather gives C Sigma_pp C^T, and the block is
 // R^-1 (I + C Sigma_pp C^T) R^-T, its upper triangle computed and mirrored.
-template <int G, bool SQRT = false>
-__global__ __launch_bounds__(COV_THREADS) void k_cov_lmk(DevPtrs P, CovDev C) {
-    const WinDev W = P.win[C.w];
-    const int l = blockIdx.x * (COV_THREADS / G) + threadIdx.x / G;
-    const int q = threadIdx.x % G;
-    const bool have = l < W.n_lmk;
-    const int status = have ? C.status[l] : COV_LMK_CONST;
-    const int n = (have && status == COV_LMK_ELIMINATED) ? C.ent_n[l] : 0;
-    const long long e0 = have ? P.lmk_ob[W.lmk_base + l] - W.obs_base : 0;
-    double acc[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) acc[i] = 0.0;
-    for (int idx = q; idx < n * n; idx += G) {
-        const int e = idx / n, f = idx - e * n;
-        const double* We = C.ent_w + (e0 + e) * COV_ENT_W;
-        const double* Wf = C.ent_w + (e0 + f) * COV_ENT_W;
-        const double* Sg = C.Sig + (long long)C.ent_col[e0 + e] * C.Np + C.ent_col[e0 + f];
-        double we[18], wf[18], T[18];
-#pragma unroll
-        for (int i = 0; i < 18; i++) { we[i] = We[i]; wf[i] = Wf[i]; T[i] = 0.0; }
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            double s[6];
-#pragma unroll
-            for (int j = 0; j < 6; j++) s[j] = Sg[(long long)k * C.Np + j];
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int j = 0; j < 6; j++) T[6 * i + j] += we[6 * i + k] * s[j];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                double v = 0.0;
-#pragma unroll
-                for (int k = 0; k < 6; k++) v += T[6 * i + k] * wf[6 * j + k];
-                acc[3 * i + j] += v;
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < 9; i++)
-        for (int m = G / 2; m > 0; m >>= 1) acc[i] += __shfl_xor(acc[i], m, G);
-    if (!have || q != 0) return;
+// A long track (CovDev::is_long) is skipped here: its gather is k_cov_lmk_long's (cov_long_kernels.h), its output formulas these.
+
+// The landmark block of landmark l from the gathered sum acc = sum_{e, f} W_e Sigma_pp(c_e, c_f) W_f^T (square-root: C for W), by status
+template <bool SQRT>
+__device__ __forceinline__ void cov_lmk_write(const DevPtrs& P, const CovDev& C, const WinDev& W, int l, int status, const double* acc) {
     double* out = C.lout + 9 * (long long)l;
     if (SQRT && status == COV_LMK_ELIMINATED) {
         const double* R = C.hll + 6 * (long long)l;
@@ -668,6 +632,54 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_lmk(DevPtrs P, CovDev C) {
     } else {
         for (int i = 0; i < 9; i++) out[i] = 0.0;
     }
+}
+
+template <int G, bool SQRT = false>
+__global__ __launch_bounds__(COV_THREADS) void k_cov_lmk(DevPtrs P, CovDev C) {
+    const WinDev W = P.win[C.w];
+    const int l = blockIdx.x * (COV_THREADS / G) + threadIdx.x / G;
+    const int q = threadIdx.x % G;
+    const bool have = l < W.n_lmk;
+    const int status = have ? C.status[l] : COV_LMK_CONST;
+    const bool lng = have && C.is_long && C.is_long[l];   // k_cov_lmk_long's
+    const int n = (have && status == COV_LMK_ELIMINATED && !lng) ? C.ent_n[l] : 0;
+    const long long e0 = have ? P.lmk_ob[W.lmk_base + l] - W.obs_base : 0;
+    double acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc[i] = 0.0;
+    for (int idx = q; idx < n * n; idx += G) {
+        const int e = idx / n, f = idx - e * n;
+        const double* We = C.ent_w + (e0 + e) * COV_ENT_W;
+        const double* Wf = C.ent_w + (e0 + f) * COV_ENT_W;
+        const double* Sg = C.Sig + (long long)C.ent_col[e0 + e] * C.Np + C.ent_col[e0 + f];
+        double we[18], wf[18], T[18];
+#pragma unroll
+        for (int i = 0; i < 18; i++) { we[i] = We[i]; wf[i] = Wf[i]; T[i] = 0.0; }
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            double s[6];
+#pragma unroll
+            for (int j = 0; j < 6; j++) s[j] = Sg[(long long)k * C.Np + j];
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+                for (int j = 0; j < 6; j++) T[6 * i + j] += we[6 * i + k] * s[j];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                double v = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) v += T[6 * i + k] * wf[6 * j + k];
+                acc[3 * i + j] += v;
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+        for (int m = G / 2; m > 0; m >>= 1) acc[i] += __shfl_xor(acc[i], m, G);
+    if (!have || lng || q != 0) return;
+    cov_lmk_write<SQRT>(P, C, W, l, status, acc);
 }
 
 }  // namespace sadvio
