@@ -5,8 +5,9 @@
 // picks for them. Units whose N_p is at most COVB_CAP (route LDS) or zero (route NONE) are processed in groups whose work arrays
 // stay under the scratch budget; a group is one launch sequence on the handle's stream (cov_batch_kernels.h), its results go to
 // pinned host memory with one asynchronous copy, and the call waits once, after the last group. A unit above the cap (route DENSE)
-// goes item by item through cov_driver.h's steps as they are, with the wait that route has; so does a unit on the band route (route
-// BAND, cov_driver.h: cov_band_route), whatever its N_p.
+// goes item by item through cov_driver.h's steps (cov_steps), with the wait that route has; so does a unit on the band route (route
+// BAND, cov_driver.h: cov_band_route), whatever its N_p. What the two calls share on the host is cov_driver.h's and is called from
+// here: cov_check_request (an item's request, under this call's name), cov_wait, cov_pick_blocks and cov_pick_landmarks.
 // The square-root assembly (cov_driver.h: cov_steps, SADVIO_COV_SQRT) exists on the single call's steps only. DENSE and BAND items
 // inherit its choice and its retry. With the variable = 1 the LDS items go down the DENSE route and the NONE items through the same
 // steps; with it unset, an LDS item whose unit failed the pivot test is retried on its own through those steps in square-root form
@@ -39,29 +40,16 @@ struct CovbUnit {
 // landmark status [nl ints] | pivot flag [1 int]
 struct CovbGroup { int u0 = 0, u1 = 0; size_t doubles = 0, ints = 0, r_doubles = 0, r0 = 0; };
 
-// 1. State and arguments, with the codes and the order of sadvio_ba_covariance. Host work only; nothing is written on an error.
+// 1. State and arguments, with the codes and the order of sadvio_ba_covariance (a batch the throughput kernels solved is served: see
+// above). Host work only; nothing is written on an error.
 int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* items) {
-    if (h->world > 1) { h->err = "covariance_batch: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
+    if (h->world > 1) return cov_invalid(h, "covariance_batch", ": the window is sharded over several GPUs (each rank holds a landmark partition only)");
     if (h->defer) { h->err = "covariance_batch between begin_update and commit_update"; return SADVIO_E_STATE; }
     if (!h->solved) { h->err = "covariance_batch before solve"; return SADVIO_E_STATE; }
-    if (n_item < 0) { h->err = "covariance_batch: negative item count"; return SADVIO_E_INVALID_ARG; }
-    if (n_item > 0 && !items) { h->err = "covariance_batch: null items"; return SADVIO_E_INVALID_ARG; }
-    for (int it = 0; it < n_item; it++) {
-        const int w = items[it].w;
-        const sadvio_cov_request* rq = &items[it].rq;
-        if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "covariance_batch: window out of range"; return SADVIO_E_INVALID_ARG; }
-        const WinDev& d = h->plan.wins[w].d;
-        if (d.line_end > d.line_begin) { h->err = "covariance_batch: the window carries line landmarks"; return SADVIO_E_INVALID_ARG; }
-        if (rq->n_kf < 0 || rq->n_pair < 0 || rq->n_lmk < -1 || (rq->n_kf > 0 && !rq->kf) || (rq->n_pair > 0 && (!rq->pair_a || !rq->pair_b)) ||
-            (rq->n_lmk > 0 && !rq->lmk)) { h->err = "covariance_batch: request out of range"; return SADVIO_E_INVALID_ARG; }
-        for (int i = 0; i < rq->n_kf; i++)
-            if (rq->kf[i] < 0 || rq->kf[i] >= d.n_kf) { h->err = "covariance_batch: key-frame index out of range"; return SADVIO_E_INVALID_ARG; }
-        for (int i = 0; i < rq->n_pair; i++)
-            if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) { h->err = "covariance_batch: key-frame index of a pair out of range"; return SADVIO_E_INVALID_ARG; }
-        for (int i = 0; i < rq->n_lmk; i++)
-            if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) { h->err = "covariance_batch: landmark index out of range"; return SADVIO_E_INVALID_ARG; }
-        if (d.Np + 1 > PCH_MAXN && !cov_band_route(h, w)) { h->err = "covariance_batch: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
-    }
+    if (n_item < 0) return cov_invalid(h, "covariance_batch", ": negative item count");
+    if (n_item > 0 && !items) return cov_invalid(h, "covariance_batch", ": null items");
+    for (int it = 0; it < n_item; it++)
+        if (int rc = cov_check_request(h, "covariance_batch", items[it].w, &items[it].rq, true)) return rc;
     return SADVIO_OK;
 }
 
@@ -101,7 +89,7 @@ void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, 
 // An item above the cap: the steps of sadvio_ba_covariance, unchanged, with their choice of assembly and their retry (cov_check's
 // tests were made for every item by covb_check)
 int covb_dense_item(sadvio_ba_handle* h, sadvio_cov_batch_item& I) {
-    const int rc = cov_steps(h, I.w, &I.rq, cov_routes(h, I.w, &I.rq, I.lmk_cov), I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
+    const int rc = cov_steps(h, I.w, cov_routes(h, I.w, &I.rq, I.lmk_cov), cov_read_back_into(h, I.w, &I.rq, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular));
     if (rc == SADVIO_E_NOT_USABLE) { I.status = SADVIO_E_NOT_USABLE; return SADVIO_OK; }
     return rc;
 }
@@ -111,7 +99,7 @@ int covb_dense_item(sadvio_ba_handle* h, sadvio_cov_batch_item& I) {
 int covb_retry_item(sadvio_ba_handle* h, sadvio_cov_batch_item& I) {
     CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
     R.sqrt = true;
-    const int rc = cov_attempt(h, I.w, &I.rq, R, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular);
+    const int rc = cov_attempt(h, I.w, R, cov_read_back_into(h, I.w, &I.rq, I.kf_cov, I.pair_cov, I.lmk_cov, &I.n_lmk_singular));
     if (rc == SADVIO_E_NOT_USABLE) return SADVIO_OK;
     if (rc == SADVIO_OK) I.status = SADVIO_OK;
     return rc;
@@ -241,8 +229,7 @@ int covb_landmarks(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, cons
 // 7. The call's one wait; every item's blocks are picked from its unit's Sigma_pp and landmark table on the host, as cov_read_back
 // picks them. An item whose unit failed the pivot test gets its status and nothing else.
 int covb_read_back(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, const std::vector<CovbUnit>& units, const std::vector<int>& unit_of) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->cfg.profile_kernels) collect_timers(h);
+    if (int rc = cov_wait(h)) return rc;
     for (int it = 0; it < n_item; it++) {
         if (unit_of[it] < 0) continue;
         sadvio_cov_batch_item& I = items[it];
@@ -252,24 +239,8 @@ int covb_read_back(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items
         const int* st = (const int*)(lo + U.r_lout);
         if (st[2 * ((U.nl + 1) / 2)] != 0) { I.status = SADVIO_E_NOT_USABLE; continue; }
         const WinDev& d = h->plan.wins[I.w].d;
-        const sadvio_cov_request* rq = &I.rq;
-        const int n = U.R.Np, dpf = d.dpf;
-        auto block = [&](int ka, int kb, double* out) {
-            const int fa = h->plan.kf_fidx[d.kf_base + ka], fb = h->plan.kf_fidx[d.kf_base + kb];
-            for (int i = 0; i < dpf; i++)
-                for (int j = 0; j < dpf; j++) out[i * dpf + j] = (fa >= 0 && fb >= 0 && n > 0) ? sig[(size_t)(fa * dpf + i) * n + fb * dpf + j] : 0.0;
-        };
-        if (I.kf_cov) for (int i = 0; i < rq->n_kf; i++) block(rq->kf[i], rq->kf[i], I.kf_cov + (size_t)i * dpf * dpf);
-        if (I.pair_cov) for (int i = 0; i < rq->n_pair; i++) block(rq->pair_a[i], rq->pair_b[i], I.pair_cov + (size_t)i * dpf * dpf);
-        const int n_out = rq->n_lmk < 0 ? d.n_lmk : rq->n_lmk;
-        int n_sing = 0;
-        if (I.lmk_cov && rq->n_lmk < 0) memcpy(I.lmk_cov, lo, 72 * (size_t)n_out);
-        for (int i = 0; i < n_out; i++) {
-            const int l = rq->n_lmk < 0 ? i : rq->lmk[i];
-            if (I.lmk_cov && rq->n_lmk >= 0) memcpy(I.lmk_cov + 9 * (size_t)i, lo + 9 * (size_t)l, 72);
-            n_sing += st[l] == COV_LMK_SINGULAR ? 1 : 0;
-        }
-        I.n_lmk_singular = n_sing;
+        cov_pick_blocks(h->plan, d, &I.rq, sig, U.R.Np, I.kf_cov, I.pair_cov);
+        cov_pick_landmarks(&I.rq, d, lo, st, I.lmk_cov, &I.n_lmk_singular);
     }
     return SADVIO_OK;
 }

@@ -3,11 +3,13 @@
 // A "unit" is one window of the call (the items that name it share its assembly and its Sigma_pp). Every kernel below reads its
 // window, delta buffer, N_p and the places of its work arrays from a table of CovUnit on the device, indexed by blockIdx.y (by
 // blockIdx.x in k_cov_inv_lds); the grid's other dimension is sized for the largest unit of the launch and a workgroup beyond its
-// own unit's extent leaves at once. The k_covb_* kernels are cov_kernels.h's bodies behind that indirection: the same __device__
-// helpers, the same order in every sum (thread-strided partial sums, then the fixed tree), no floating-point atomics — a unit's
-// bits depend neither on the other units of the launch nor on its place among them.
+// own unit's extent leaves at once. The k_covb_* kernels are wrappers: each loads its unit's CovDev, applies that guard and calls the
+// __device__ body that its k_cov_* counterpart in cov_kernels.h calls — one body per kernel, so the order in every sum
+// (thread-strided partial sums, then the fixed tree) and the absence of floating-point atomics are those of the single call, and a
+// unit's bits depend neither on the other units of the launch nor on its place among them. k_covb_assemble and k_covb_lmk alone
+// are copies of k_cov_assemble's and k_cov_lmk's text behind the guard (cov_kernels.h says why): a change to one is made to the other.
 //
-// k_cov_inv_lds is new: Sigma_pp = S^-1 of one unit by ONE workgroup with the lower block triangle of S in LDS.
+// k_cov_inv_lds is this file's own: Sigma_pp = S^-1 of one unit by ONE workgroup with the lower block triangle of S in LDS.
 //   cap:      N_p <= COVB_CAP = 176 (11 block rows of 16; the shipped VIO window is 11 x 15 = 165)
 //   layout:   66 tiles of 16 x 16, rows padded to 17 doubles (four row groups of a wave's ds_read_b64 land on four bank pairs) = 140.25 KiB,
 //             + one work tile (the inverse of the current diagonal tile) + S's diagonal and the pivots' roots: 147 328 B of 160 KiB
@@ -45,25 +47,15 @@ struct CovUnit {
     int G;           // lanes per landmark of k_covb_lmk (16 | 64), 0: no landmark block asked of this unit
 };
 
+// ---- the wrappers: the unit's CovDev, the guard of a workgroup beyond the unit's extent, then cov_kernels.h's body ------------------
 __global__ void k_covb_tables(DevPtrs P, const CovUnit* units, double* ptab) {
     const CovDev C = units[blockIdx.y].C;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *units[blockIdx.y].bad = 0;
     const WinDev W = P.win[C.w];
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k == 0) *units[blockIdx.y].bad = 0;
-    if (k < W.n_lmk) {
-        const int lc = P.lmk_const ? P.lmk_const[W.lmk_base + k] : 0;
-        C.status[k] = lc == 1 ? COV_LMK_CONST : (lc == 2 ? COV_LMK_REDUCED : COV_LMK_SINGULAR);
-        C.ent_n[k] = 0;
-    }
-    if (k >= W.n_kf) return;
-    const long long kf = W.kf_base + k;
-    double d6[6], T0[12], tab[POSE_TAB];
-    for (int i = 0; i < 6; i++) d6[i] = P.xp[(long long)C.cur * P.xp_stride + 6 * kf + i];
-    for (int i = 0; i < 12; i++) T0[i] = P.kf_T0[12 * kf + i];
-    pose_table_entry(T0, d6, tab);
-    for (int i = 0; i < POSE_TAB; i++) ptab[kf * POSE_TAB + i] = tab[i];
+    cov_tables_body(P, C, W, ptab);
 }
 
+// (k_cov_assemble's text, which carries the comments)
 template <int FACTOR>
 __global__ __launch_bounds__(COV_THREADS) void k_covb_assemble(DevPtrs P, const CovUnit* units) {
     const CovDev C = units[blockIdx.y].C;
@@ -125,64 +117,9 @@ __global__ __launch_bounds__(COV_SCHUR_THREADS) void k_covb_schur(DevPtrs P, con
     const CovDev C = units[blockIdx.y].C;
     const WinDev W = P.win[C.w];
     if (C.Np == 0 || (int)blockIdx.x >= W.n_free_kf * (W.n_free_kf + 1) / 2) return;
-    int a = 0;
+    int a = 0;   // (a unit of this call is never on the band route: no pair table)
     while ((a + 1) * (a + 2) / 2 <= (int)blockIdx.x) a++;
-    const int b = (int)blockIdx.x - a * (a + 1) / 2;
-    const int ca = a * W.dpf, cb = b * W.dpf;
-    double acc[36];
-#pragma unroll
-    for (int q = 0; q < 36; q++) acc[q] = 0.0;
-    for (int l = threadIdx.x; l < W.n_lmk; l += COV_SCHUR_THREADS) {
-        const int n = C.ent_n[l];
-        if (n == 0) continue;
-        const long long e0 = P.lmk_ob[W.lmk_base + l] - W.obs_base;
-        int ea = -1, eb = -1;
-        for (int e = 0; e < n; e++) {
-            const int col = C.ent_col[e0 + e];
-            if (col == ca) ea = e;
-            if (col == cb) eb = e;
-        }
-        if (ea < 0 || eb < 0) continue;
-        if (a == b) {
-            const double* h21 = C.ent_hpp + (e0 + ea) * COV_ENT_HPP;
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-                for (int j = 0; j < 6; j++) acc[6 * i + j] += i >= j ? h21[i * (i + 1) / 2 + j] : h21[j * (j + 1) / 2 + i];
-        }
-        if (C.status[l] != COV_LMK_ELIMINATED) continue;
-        const double* Wa = C.ent_w + (e0 + ea) * COV_ENT_W;
-        const double* Wb = C.ent_w + (e0 + eb) * COV_ENT_W;
-        const double* H = C.hll + 6 * (long long)l;
-        double HW[18];
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            double y[3];
-            cov_sym3_vec(H, Wb[j], Wb[6 + j], Wb[12 + j], y);
-            HW[j] = y[0]; HW[6 + j] = y[1]; HW[12 + j] = y[2];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = 0; j < 6; j++) acc[6 * i + j] -= Wa[i] * HW[j] + Wa[6 + i] * HW[6 + j] + Wa[12 + i] * HW[12 + j];
-    }
-    __shared__ double sh[COV_SCHUR_THREADS * 36];
-#pragma unroll
-    for (int q = 0; q < 36; q++) sh[threadIdx.x * 36 + q] = acc[q];
-    __syncthreads();
-    for (int s = COV_SCHUR_THREADS / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int q = 0; q < 36; q++) sh[threadIdx.x * 36 + q] += sh[(threadIdx.x + s) * 36 + q];
-        __syncthreads();
-    }
-    if (threadIdx.x < 36) {
-        const int i = threadIdx.x / 6, j = threadIdx.x - 6 * i;
-        if (a == b) C.S[(long long)(ca + i) * C.Np + ca + j] = 0.5 * (sh[6 * i + j] + sh[6 * j + i]);
-        else {
-            C.S[(long long)(ca + i) * C.Np + cb + j] = sh[6 * i + j];
-            C.S[(long long)(cb + j) * C.Np + ca + i] = sh[6 * i + j];
-        }
-    }
+    cov_schur_body(P, C, W, a, (int)blockIdx.x - a * (a + 1) / 2);
 }
 
 template <int FACTOR>
@@ -190,33 +127,7 @@ __global__ __launch_bounds__(64) void k_covb_kept(DevPtrs P, const CovUnit* unit
     const CovDev C = units[blockIdx.x].C;
     const WinDev W = P.win[C.w];
     if (C.Np == 0 || W.kept_end <= W.kept_begin) return;
-    __shared__ double J[2 * 9];
-    __shared__ int col[9];
-    const int t = threadIdx.x;
-    for (int k = W.kept_begin; k < W.kept_end; k++) {
-        const int o = P.kept_obs[3 * k], gl = P.kept_obs[3 * k + 1];
-        if (P.obs_cam[o] < 0) continue;
-        if (t == 0) {
-            const double* xl = P.xl + (long long)C.cur * P.xl_stride + 3 * (long long)gl;
-            const double pw[3] = {P.lmk_p[3 * (long long)gl] + xl[0], P.lmk_p[3 * (long long)gl + 1] + xl[1], P.lmk_p[3 * (long long)gl + 2] + xl[2]};
-            double Jp[12], Jl[6];
-            cov_obs_jacobians<FACTOR>(P, C, o, pw, Jp, Jl);
-            const int fi = P.kf_fidx[P.obs_kf[o]], lr = P.lmk_red[gl];
-            for (int q = 0; q < 2; q++) {
-                for (int c = 0; c < 6; c++) J[9 * q + c] = Jp[6 * q + c];
-                for (int c = 0; c < 3; c++) J[9 * q + 6 + c] = Jl[3 * q + c];
-            }
-            for (int c = 0; c < 6; c++) col[c] = fi >= 0 ? fi * W.dpf + c : -1;
-            for (int c = 0; c < 3; c++) col[6 + c] = lr >= 0 ? lr + c : -1;
-        }
-        __syncthreads();
-        for (int idx = t; idx < 81; idx += 64) {
-            const int a = idx / 9, c = idx - 9 * a;
-            if ((a < 6 && c < 6) || col[a] < 0 || col[c] < 0) continue;
-            C.S[(long long)col[a] * C.Np + col[c]] += J[a] * J[c] + J[9 + a] * J[9 + c];
-        }
-        __syncthreads();
-    }
+    cov_kept_body<FACTOR>(P, C, W);
 }
 
 // ImuDev under a third name: an instantiation of imu_factor_body of this kernel's own (see CovImu in cov_kernels.h)
@@ -224,101 +135,16 @@ struct CovBatchImu : ImuDev {};
 
 __global__ __launch_bounds__(64) void k_covb_factors(DevPtrs P, const CovUnit* units) {
     const CovDev C = units[blockIdx.x].C;
-    const WinDev W = P.win[C.w];
     if (C.Np == 0) return;
-    const int t = threadIdx.x;
-    const double* xp = P.xp + (long long)C.cur * P.xp_stride;
-    const double* xv = P.xv + (long long)C.cur * P.xv_stride;
-    const double* xba = P.xba + (long long)C.cur * P.xv_stride;
-    const double* xbg = P.xbg + (long long)C.cur * P.xv_stride;
-    const double* xl = P.xl + (long long)C.cur * P.xl_stride;
-    __shared__ double sJ[15 * 24];
-    __shared__ int scol[24];
-    for (int k = W.prior_begin; k < W.prior_end; k++) {
-        if (t == 0) {
-            const PriorDev pr = P.priors[k];
-            double T0[12], d6[6], r[6], J[36];
-            for (int i = 0; i < 12; i++) T0[i] = P.kf_T0[12 * (long long)pr.kf + i];
-            for (int i = 0; i < 6; i++) d6[i] = xp[6 * (long long)pr.kf + i];
-            pose_prior_factor(T0, pr.T_prior, pr.inf, d6, r, J);
-            const int fi = P.kf_fidx[pr.kf];
-            for (int i = 0; i < 36; i++) sJ[i] = J[i];
-            for (int a = 0; a < 6; a++) scol[a] = fi >= 0 ? fi * W.dpf + a : -1;
-        }
-        __syncthreads();
-        cov_accumulate(C.S, C.Np, sJ, 6, 6, scol, t, 64);
-        __syncthreads();
-    }
-    for (int k = W.imu_begin; k < W.imu_end; k++) {
-        const CovBatchImu& f = *static_cast<const CovBatchImu*>(P.imus + k);
-        const int i = f.kf_i, j = f.kf_j;
-        const int fi = P.kf_fidx[i], fj = P.kf_fidx[j];
-        if (t == 0) {
-            double r[9];
-            for (int q = 0; q < 9 * 24; q++) sJ[q] = 0.0;
-            imu_factor_body<CovBatchImu, false>(f, P.kf_T0 + 12 * (long long)i, P.kf_T0 + 12 * (long long)j, P.kf_vel + 3 * (long long)i, P.kf_vel + 3 * (long long)j,
-                                                xp + 6 * (long long)i, xp + 6 * (long long)j, xv + 3 * (long long)i, xv + 3 * (long long)j, xba + 3 * (long long)i,
-                                                xbg + 3 * (long long)i, r, sJ);
-            for (int a = 0; a < 24; a++) scol[a] = W.dpf == 15 ? imu_col(a, fi, fj) : -1;
-        }
-        __syncthreads();
-        if (t < 24) {
-            double u[9];
-            for (int q = 0; q < 9; q++) u[q] = sJ[q * 24 + t];
-            for (int q = 0; q < 9; q++) {
-                double v = 0.0;
-                for (int kk = q; kk < 9; kk++) v += f.W[9 * q + kk] * u[kk];
-                sJ[q * 24 + t] = v;
-            }
-        }
-        __syncthreads();
-        cov_accumulate(C.S, C.Np, sJ, 9, 24, scol, t, 64);
-        __syncthreads();
-        if (t == 0) {
-            for (int q = 0; q < 72; q++) sJ[q] = 0.0;
-            for (int a = 0; a < 3; a++) {
-                sJ[a * 12 + a] = -f.sa; sJ[(3 + a) * 12 + 3 + a] = -f.sg; sJ[a * 12 + 6 + a] = f.sa; sJ[(3 + a) * 12 + 9 + a] = f.sg;
-                const bool st = W.dpf == 15;
-                scol[a] = st && fi >= 0 ? fi * 15 + 9 + a : -1; scol[3 + a] = st && fi >= 0 ? fi * 15 + 12 + a : -1;
-                scol[6 + a] = st && fj >= 0 ? fj * 15 + 9 + a : -1; scol[9 + a] = st && fj >= 0 ? fj * 15 + 12 + a : -1;
-            }
-        }
-        __syncthreads();
-        cov_accumulate(C.S, C.Np, sJ, 6, 12, scol, t, 64);
-        __syncthreads();
-    }
-    for (int q = W.spl_begin; q < W.spl_end; q++) {
-        const SparseDev& f = P.sparse[P.sp_list[q]];
-        __shared__ int s_rows;
-        if (t == 0) {
-            double r[15], J[225];
-            for (int a = 0; a < 225; a++) J[a] = 0.0;
-            const bool in = sparse_eval(P, W, f, xp, xv, xba, xbg, xl, nullptr, r, J);
-            s_rows = in ? sparse_rows(f) : 0;
-            for (int a = 0; a < 225; a++) sJ[a] = J[a];
-            const int fi = f.kf >= 0 ? P.kf_fidx[f.kf] : -1;
-            const int lr0 = sparse_lr0(P, W, f);
-            const int lr1 = (f.lmk1 >= 0 && P.lmk_red) ? P.lmk_red[f.lmk1] : -1;
-            for (int a = 0; a < 15; a++) scol[a] = sparse_col(f, a, fi, W.dpf, lr0, lr1);
-        }
-        __syncthreads();
-        cov_accumulate(C.S, C.Np, sJ, s_rows, 15, scol, t, 64);
-        __syncthreads();
-    }
+    const WinDev W = P.win[C.w];
+    cov_factors_body<CovBatchImu>(P, C, W);
 }
 
 __global__ void k_covb_dense(DevPtrs P, const CovUnit* units) {
     const CovDev C = units[blockIdx.y].C;
     const WinDev W = P.win[C.w];
     if (C.Np == 0 || W.dp_n_full <= 0) return;
-    const int n = W.dp_n;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)n * n) return;
-    const int a = (int)(idx / n), c = (int)(idx - (long long)a * n);
-    const int* col = P.dp_ints + W.dp_int_off + 2 * n;
-    if (col[a] < 0 || col[c] < 0) return;
-    const double* H = P.dp_data + W.dp_off + 2LL * W.dp_n_full * n;
-    C.S[(long long)col[a] * C.Np + col[c]] += H[(long long)a * n + c];
+    cov_dense_body(P, C, W);
 }
 
 // ---- Sigma_pp = S^-1 inside one workgroup's LDS --------------------------------------------------------------------------------

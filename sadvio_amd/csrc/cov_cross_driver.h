@@ -1,8 +1,8 @@
 // cov_cross_driver.h — the host side of sadvio_ba_covariance_cross as named steps
-//   covx_check -> cov_routes -> cov_assemble | cov_assemble_sqrt -> cov_invert -> cov_landmarks -> covx_cross (one wait)
-// The steps up to cov_landmarks are cov_driver.h's, called as they are (cov_landmarks for every landmark when innovation outputs are
-// asked for, not at all otherwise); covx_cross takes the place of cov_read_back behind the call's single wait and adds none on the
-// dense route. covx_steps is cov_steps with that last step: the same choice of assembly (SADVIO_COV_SQRT) and the same retry.
+//   covx_check -> cov_routes -> cov_assemble -> cov_invert -> cov_landmarks -> covx_cross (one wait)
+// The steps up to cov_landmarks are cov_driver.h's (cov_landmarks for every landmark when innovation outputs are asked for, not at
+// all otherwise): covx_run hands covx_cross to cov_steps as the last step, in cov_read_back's place behind the call's single wait
+// (it adds none on the dense route), and so takes the single call's choice of assembly (SADVIO_COV_SQRT) and its retry.
 // Dense route: k_cov_cross / k_cov_innov read block rows of Sigma_pp. Band route: k_cov_band_rows first solves the whole block row of
 // every distinct key-frame asked for, and every candidate is served from those rows; no kernel reads Sigma outside its band.
 // Part of the library's single translation unit (ba_capi.hip, which includes it below cov_driver.h); not a public header.
@@ -18,7 +18,7 @@ struct CovCrossOut { double* cross; double* innov; double* maha2; int32_t* statu
 // 1. State and arguments: cov_check's refusals with its texts, then the candidates. Host work only.
 int covx_check(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, const CovCrossOut& O) {
     const sadvio_cov_request none{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
-    if (int rc = cov_check(h, w, rq ? &none : nullptr, nullptr)) return rc;
+    if (int rc = cov_check(h, w, rq ? &none : nullptr)) return rc;
     const WinDev& d = h->plan.wins[w].d;
     if (rq->n < 0 || (rq->n > 0 && (!rq->kf || !rq->lmk)) || ((rq->cam == nullptr) != (rq->meas == nullptr))) { h->err = "covariance: request out of range"; return SADVIO_E_INVALID_ARG; }
     if ((O.innov || O.maha2) && !rq->cam) { h->err = "covariance_cross: innovation outputs without a candidate camera and measurement"; return SADVIO_E_INVALID_ARG; }
@@ -101,43 +101,13 @@ int covx_cross(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, c
     HIP_TRY(hipMemcpyAsync(K.h_status.data(), K.status.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     int flag[2] = {0, 0};
     if (R.band) HIP_TRY(hipMemcpyAsync(flag, V.bflag.p, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->cfg.profile_kernels) collect_timers(h);
-    if (flag[0] != 0) {
-        h->err = "covariance: the reduced information matrix is not positive definite (gauge not fixed: no constant key-frame, no prior)";
-        return SADVIO_E_NOT_USABLE;
-    }
+    if (int rc = cov_wait(h)) return rc;
+    if (flag[0] != 0) return cov_not_usable(h, true);
     if (O.cross) memcpy(O.cross, K.h_out.data(), sizeof(double) * n_cross);
     if (O.innov) memcpy(O.innov, K.h_out.data() + n_cross, sizeof(double) * 4 * (size_t)n);
     if (O.maha2) memcpy(O.maha2, K.h_out.data() + n_cross + 4 * (size_t)n, sizeof(double) * (size_t)n);
     if (O.status) for (int c = 0; c < n; c++) O.status[c] = K.h_status[c];
     return SADVIO_OK;
-}
-
-// Steps 2 to 5 with the assembly R names (cov_attempt with covx_cross as its last step)
-int covx_attempt(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, const CovRoutes& R, const CovCrossOut& O) {
-    if (int rc = R.sqrt ? cov_assemble_sqrt(h, w, R) : cov_assemble(h, w, R)) return rc;
-    bool usable = true;
-    if (int rc = cov_invert(h, R, usable)) return rc;
-    if (!usable) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->cfg.profile_kernels) collect_timers(h);
-        h->err = "covariance: the reduced information matrix is not positive definite (gauge not fixed: no constant key-frame, no prior)";
-        return SADVIO_E_NOT_USABLE;
-    }
-    if (int rc = cov_landmarks(h, w, R)) return rc;
-    return covx_cross(h, w, rq, R, O);
-}
-
-// The assembly of a call and the retry: cov_steps's rule
-int covx_steps(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, CovRoutes R, const CovCrossOut& O) {
-    R.sqrt = h->env.cov_sqrt == 1;
-    int rc = covx_attempt(h, w, rq, R, O);
-    if (rc == SADVIO_E_NOT_USABLE && !R.sqrt && h->env.cov_sqrt != 0) {
-        R.sqrt = true;
-        rc = covx_attempt(h, w, rq, R, O);
-    }
-    return rc;
 }
 
 int covx_run(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, double* cross_cov, double* innov_cov, double* maha2, int32_t* status) {
@@ -148,7 +118,7 @@ int covx_run(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, dou
     // Sigma_ll of every landmark is needed exactly when an innovation is formed
     static const double want_lmk = 0.0;
     const sadvio_cov_request all{0, nullptr, 0, nullptr, nullptr, -1, nullptr};
-    return covx_steps(h, w, rq, cov_routes(h, w, &all, rq->cam ? &want_lmk : nullptr), O);
+    return cov_steps(h, w, cov_routes(h, w, &all, rq->cam ? &want_lmk : nullptr), [=](const CovRoutes& R) { return covx_cross(h, w, rq, R, O); });
 }
 
 }  // namespace

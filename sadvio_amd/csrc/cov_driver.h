@@ -4,8 +4,11 @@
 // BAND route; cov_band_route says when). On the band route k_cov_schur runs over the table of in-band key-frame pairs, no kernel
 // reads an entry of Sigma outside the band, pair blocks outside the band come from band substitution, and the host receives the
 // blocks asked for and nothing else.
-// S and the landmark blocks have two assemblies: the plain one (cov_assemble) and the square-root one (cov_assemble_sqrt), which
-// survives landmarks millimetres from a camera centre; cov_steps says which runs (SADVIO_COV_SQRT) and holds the retry.
+// S and the landmark blocks have two assemblies: the plain one and the square-root one, which survives landmarks millimetres from a
+// camera centre. cov_assemble serves both and branches on CovRoutes::sqrt where they differ; cov_steps says which runs
+// (SADVIO_COV_SQRT) and holds the retry. cov_attempt and cov_steps take the last step as a callable: cov_read_back here, covx_cross
+// in cov_cross_driver.h. What sadvio_ba_covariance_batch shares with this call on the host is here too: cov_check_request (the
+// request's validation under the call's name), cov_wait, cov_not_usable, cov_pick_blocks and cov_pick_landmarks.
 // A window with long tracks (handles created with SADVIO_CFG_LONG_TRACK_COVARIANCE; every other handle is refused in ba_capi.hip) adds
 // cov_assemble_long to either assembly and k_cov_lmk_long to cov_landmarks (cov_long_kernels.h); without long tracks no launch changes.
 // The kernels are cov_kernels.h's; the factorisation of S and the triangular inverse are marg_driver.h's (factor_unpivoted,
@@ -37,7 +40,7 @@ struct CovRoutes {
     int n_lmk_out = 0;      // landmark blocks written
     bool band = false;      // the band route; then hb / bw / nb: block half-bandwidth, (hb + 1) * dpf, block column of the sweeps
     int hb = 0, bw = 0, nb = 0, dpf = 6;
-    bool sqrt = false;      // the square-root assembly (cov_assemble_sqrt) instead of the plain one
+    bool sqrt = false;      // the square-root assembly instead of the plain one (cov_assemble)
     int n_long = 0, long_first = 0, long_max_kf = 0;   // long tracks of the window, its first on the long list, LongArgs::max_kf (k_cov_long, k_cov_lmk_long)
 };
 
@@ -58,27 +61,39 @@ bool cov_band_route(const sadvio_ba_handle* h, int w, int* hb_out = nullptr, int
     return h->env.cov_band > 0 || d.Np + 1 > PCH_MAXN;
 }
 
+// An invalid argument of the call named `call` ("covariance" | "covariance_batch"): its text, its code
+int cov_invalid(sadvio_ba_handle* h, const char* call, const char* what) {
+    h->err = std::string(call) + what;
+    return SADVIO_E_INVALID_ARG;
+}
+
+// 1. Request rq on window w, for sadvio_ba_covariance and for every item of sadvio_ba_covariance_batch: the window, then the
+// request's counts, pointers and indices. through_lm: is a batch solved by the throughput kernels served (cov_batch_driver.h says why
+// the batch call accepts one)?
+int cov_check_request(sadvio_ba_handle* h, const char* call, int w, const sadvio_cov_request* rq, bool through_lm) {
+    if (w < 0 || w >= (int)h->plan.wins.size()) return cov_invalid(h, call, ": window out of range");
+    if (!rq) return cov_invalid(h, call, ": null request");
+    const WinDev& d = h->plan.wins[w].d;
+    if (d.line_end > d.line_begin) return cov_invalid(h, call, ": the window carries line landmarks");
+    if (h->cov_use_lm && !through_lm) return cov_invalid(h, call, ": the batch was solved by the throughput kernels");
+    if (rq->n_kf < 0 || rq->n_pair < 0 || rq->n_lmk < -1 || (rq->n_kf > 0 && !rq->kf) || (rq->n_pair > 0 && (!rq->pair_a || !rq->pair_b)) ||
+        (rq->n_lmk > 0 && !rq->lmk)) return cov_invalid(h, call, ": request out of range");
+    for (int i = 0; i < rq->n_kf; i++)
+        if (rq->kf[i] < 0 || rq->kf[i] >= d.n_kf) return cov_invalid(h, call, ": key-frame index out of range");
+    for (int i = 0; i < rq->n_pair; i++)
+        if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) return cov_invalid(h, call, ": key-frame index of a pair out of range");
+    for (int i = 0; i < rq->n_lmk; i++)
+        if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) return cov_invalid(h, call, ": landmark index out of range");
+    if (d.Np + 1 > PCH_MAXN && !cov_band_route(h, w)) return cov_invalid(h, call, ": the reduced system has 2047 columns or more");
+    return SADVIO_OK;
+}
+
 // 1. State and arguments. Host work only.
-int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov) {
-    if (h->world > 1) { h->err = "covariance: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
+int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq) {
+    if (h->world > 1) return cov_invalid(h, "covariance", ": the window is sharded over several GPUs (each rank holds a landmark partition only)");
     if (h->defer) { h->err = "covariance between begin_update and commit_update"; return SADVIO_E_STATE; }
     if (!h->solved) { h->err = "covariance before solve"; return SADVIO_E_STATE; }
-    if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "covariance: window out of range"; return SADVIO_E_INVALID_ARG; }
-    if (!rq) { h->err = "covariance: null request"; return SADVIO_E_INVALID_ARG; }
-    const WinDev& d = h->plan.wins[w].d;
-    if (d.line_end > d.line_begin) { h->err = "covariance: the window carries line landmarks"; return SADVIO_E_INVALID_ARG; }
-    if (h->cov_use_lm) { h->err = "covariance: the batch was solved by the throughput kernels"; return SADVIO_E_INVALID_ARG; }
-    if (rq->n_kf < 0 || rq->n_pair < 0 || rq->n_lmk < -1 || (rq->n_kf > 0 && !rq->kf) || (rq->n_pair > 0 && (!rq->pair_a || !rq->pair_b)) ||
-        (rq->n_lmk > 0 && !rq->lmk)) { h->err = "covariance: request out of range"; return SADVIO_E_INVALID_ARG; }
-    for (int i = 0; i < rq->n_kf; i++)
-        if (rq->kf[i] < 0 || rq->kf[i] >= d.n_kf) { h->err = "covariance: key-frame index out of range"; return SADVIO_E_INVALID_ARG; }
-    for (int i = 0; i < rq->n_pair; i++)
-        if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) { h->err = "covariance: key-frame index of a pair out of range"; return SADVIO_E_INVALID_ARG; }
-    for (int i = 0; i < rq->n_lmk; i++)
-        if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) { h->err = "covariance: landmark index out of range"; return SADVIO_E_INVALID_ARG; }
-    if (d.Np + 1 > PCH_MAXN && !cov_band_route(h, w)) { h->err = "covariance: the reduced system has 2047 columns or more"; return SADVIO_E_INVALID_ARG; }
-    (void)lmk_cov;
-    return SADVIO_OK;
+    return cov_check_request(h, "covariance", w, rq, false);
 }
 
 CovRoutes cov_routes(const sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov) {
@@ -145,64 +160,36 @@ int cov_assemble_long(sadvio_ba_handle* h, const CovRoutes& R, const DevPtrs& P,
     return SADVIO_OK;
 }
 
-// 2. Allocate; linearise at x*; S = H_pp - sum_l H_pl H_ll^-1 H_lp, full symmetric, in V.S
+// The band route's workgroups of k_cov_schur(_sqrt): the in-band pairs (a, b), a >= b, a - b <= hb, as a table on the device —
+// nothing else of S can be non-zero. n_schur: how many.
+int cov_pair_table(sadvio_ba_handle* h, const WinDev& d, const CovRoutes& R, int& n_schur) {
+    CovScratch& V = h->cv;
+    std::vector<int>& tab = V.h_pair_tab;
+    tab.clear();
+    for (int a = 0; a < d.n_free_kf; a++)
+        for (int b = std::max(0, a - R.hb); b <= a; b++) { tab.push_back(a); tab.push_back(b); }
+    n_schur = (int)tab.size() / 2;
+    HIP_TRY(V.pair_tab.alloc(tab.size()));
+    HIP_TRY(hipMemcpyAsync(V.pair_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
+    return SADVIO_OK;
+}
+
+// 2. Allocate; linearise at x*; S, full symmetric, in V.S. Two assemblies, which differ in the tile kernel, in the pair kernel and in
+// what those keep per observation; everything else is one sequence.
+//   plain (the class cov_assemble):             S = H_pp - sum_l H_pl H_ll^-1 H_lp
+//   square-root (R.sqrt, cov_assemble_sqrt):    the same S in Gram form: per eliminated landmark J_l = Q1 R, C_a = Q1^T J_p,a, and block
+//       (a, b) of S the sum over the landmark's rows of A_a^T A_b, A_a = [row is a's] J_p,a - Q1 C_a (cov_kernels.h) — never a difference
+//       of two large matrices, so a landmark millimetres from a camera centre cannot turn S indefinite. The pair workgroups walk
+//       key-frame -> landmark lists built here from the plan's observation lists and uploaded with the call.
 int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     const WinDev& d = h->plan.wins[w].d;
     CovScratch& V = h->cv;
     const size_t nl = (size_t)std::max(d.n_lmk, 1), no = (size_t)std::max(d.n_obs, 1), nn = (size_t)std::max(R.Np, 1) * std::max(R.Np, 1);
     HIP_TRY(V.ptab.alloc((size_t)h->plan.n_kf_tot * POSE_TAB));
     HIP_TRY(V.hll.alloc(6 * nl)); HIP_TRY(V.hinv.alloc(6 * nl)); HIP_TRY(V.status.alloc(nl)); HIP_TRY(V.ent_n.alloc(nl)); HIP_TRY(V.lout.alloc(9 * nl));
-    HIP_TRY(V.ent_col.alloc(no)); HIP_TRY(V.ent_w.alloc(COV_ENT_W * no)); HIP_TRY(V.ent_hpp.alloc(COV_ENT_HPP * no));
-    HIP_TRY(V.S.alloc(nn)); HIP_TRY(V.Sig.alloc(nn));
-    if (R.n_long > 0) HIP_TRY(V.is_long.alloc(nl));
-    HIP_TRY(hipMemsetAsync(V.S.p, 0, sizeof(double) * nn, h->stream));
-    SolveOpts so{};
-    so.huber_a = h->cov_huber_a;
-    const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
-    int n_schur = d.n_free_kf * (d.n_free_kf + 1) / 2;
-    if (R.band && R.Np > 0) {   // the in-band pairs (a, b), a >= b, a - b <= hb: nothing else of S can be non-zero
-        std::vector<int>& tab = V.h_pair_tab;
-        tab.clear();
-        for (int a = 0; a < d.n_free_kf; a++)
-            for (int b = std::max(0, a - R.hb); b <= a; b++) { tab.push_back(a); tab.push_back(b); }
-        n_schur = (int)tab.size() / 2;
-        HIP_TRY(V.pair_tab.alloc(tab.size()));
-        HIP_TRY(hipMemcpyAsync(V.pair_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
-    }
-    const CovDev C = cov_dev(h, w, R);
-    ScopedTimer t(h, "cov_assemble");
-    const int n_tab = std::max(d.n_kf, d.n_lmk);
-    hipLaunchKernelGGL(k_cov_tables, dim3((n_tab + 255) / 256), dim3(256), 0, h->stream, P, C, V.ptab.p);
-    const int n_tiles = d.tile_end - d.tile_begin;
-    if (n_tiles > 0) hipLaunchKernelGGL(R.pix ? k_cov_assemble<0> : k_cov_assemble<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C);
-    if (int rc = cov_assemble_long(h, R, P, C, CovSqrtDev{})) return rc;
-    if (R.Np == 0) return SADVIO_OK;
-    if (d.n_free_kf > 0) {
-        ScopedTimer ts(h, R.band || R.n_long > 0 ? "k_cov_schur" : nullptr);   // (band route, long tracks: a class of its own inside cov_assemble's span, for the profile)
-        hipLaunchKernelGGL(k_cov_schur, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C);
-    }
-    if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
-    {
-        ScopedTimer tf(h, R.band ? "k_cov_factors" : nullptr);
-        hipLaunchKernelGGL(k_cov_factors, dim3(1), dim3(64), 0, h->stream, P, C);
-    }
-    if (R.dense) hipLaunchKernelGGL(k_cov_dense, dim3((unsigned)(((long long)d.dp_n * d.dp_n + 255) / 256)), dim3(256), 0, h->stream, P, C);
-    HIP_TRY(hipGetLastError());
-    return SADVIO_OK;
-}
-
-// 2 (square-root assembly). The same S in Gram form: per eliminated landmark J_l = Q1 R, C_a = Q1^T J_p,a, and block (a, b) of S the
-// sum over the landmark's rows of A_a^T A_b, A_a = [row is a's] J_p,a - Q1 C_a (cov_kernels.h) — never a difference of two large
-// matrices, so a landmark millimetres from a camera centre cannot turn S indefinite. The pair workgroups walk key-frame -> landmark
-// lists built here from the plan's observation lists and uploaded with the call. Shows as the class cov_assemble_sqrt.
-int cov_assemble_sqrt(sadvio_ba_handle* h, int w, const CovRoutes& R) {
-    const WinDev& d = h->plan.wins[w].d;
-    CovScratch& V = h->cv;
-    const size_t nl = (size_t)std::max(d.n_lmk, 1), no = (size_t)std::max(d.n_obs, 1), nn = (size_t)std::max(R.Np, 1) * std::max(R.Np, 1);
-    HIP_TRY(V.ptab.alloc((size_t)h->plan.n_kf_tot * POSE_TAB));
-    HIP_TRY(V.hll.alloc(6 * nl)); HIP_TRY(V.hinv.alloc(6 * nl)); HIP_TRY(V.status.alloc(nl)); HIP_TRY(V.ent_n.alloc(nl)); HIP_TRY(V.lout.alloc(9 * nl));
     HIP_TRY(V.ent_col.alloc(no)); HIP_TRY(V.ent_w.alloc(COV_ENT_W * no));
-    HIP_TRY(V.sq_jp.alloc(12 * no)); HIP_TRY(V.sq_q.alloc(6 * no)); HIP_TRY(V.sq_ent.alloc(no));
+    if (!R.sqrt) HIP_TRY(V.ent_hpp.alloc(COV_ENT_HPP * no));
+    else { HIP_TRY(V.sq_jp.alloc(12 * no)); HIP_TRY(V.sq_q.alloc(6 * no)); HIP_TRY(V.sq_ent.alloc(no)); }
     HIP_TRY(V.S.alloc(nn)); HIP_TRY(V.Sig.alloc(nn));
     if (R.n_long > 0) HIP_TRY(V.is_long.alloc(nl));
     HIP_TRY(hipMemsetAsync(V.S.p, 0, sizeof(double) * nn, h->stream));
@@ -210,32 +197,32 @@ int cov_assemble_sqrt(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     so.huber_a = h->cov_huber_a;
     const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
     int n_schur = d.n_free_kf * (d.n_free_kf + 1) / 2;
-    if (R.band && R.Np > 0) {
-        std::vector<int>& tab = V.h_pair_tab;
-        tab.clear();
-        for (int a = 0; a < d.n_free_kf; a++)
-            for (int b = std::max(0, a - R.hb); b <= a; b++) { tab.push_back(a); tab.push_back(b); }
-        n_schur = (int)tab.size() / 2;
-        HIP_TRY(V.pair_tab.alloc(tab.size()));
-        HIP_TRY(hipMemcpyAsync(V.pair_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
+    if (R.band && R.Np > 0)
+        if (int rc = cov_pair_table(h, d, R, n_schur)) return rc;
+    CovSqrtDev Q{};
+    if (R.sqrt) {
+        cov_kf_lmk_lists(d.n_free_kf, d.n_lmk, h->plan.lmk_ob.data() + d.lmk_base, h->plan.lmk_oe.data() + d.lmk_base, h->plan.obs_kf.data(),
+                         h->plan.kf_fidx.data(), V.h_kf_ptr, V.h_kf_lmk);
+        HIP_TRY(V.kf_ptr.alloc(V.h_kf_ptr.size())); HIP_TRY(V.kf_lmk.alloc(V.h_kf_lmk.size()));
+        HIP_TRY(hipMemcpyAsync(V.kf_ptr.p, V.h_kf_ptr.data(), sizeof(int) * V.h_kf_ptr.size(), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(V.kf_lmk.p, V.h_kf_lmk.data(), sizeof(int) * V.h_kf_lmk.size(), hipMemcpyHostToDevice, h->stream));
+        Q = CovSqrtDev{V.sq_jp.p, V.sq_q.p, V.sq_ent.p, V.kf_ptr.p, V.kf_lmk.p};
     }
-    cov_kf_lmk_lists(d.n_free_kf, d.n_lmk, h->plan.lmk_ob.data() + d.lmk_base, h->plan.lmk_oe.data() + d.lmk_base, h->plan.obs_kf.data(),
-                     h->plan.kf_fidx.data(), V.h_kf_ptr, V.h_kf_lmk);
-    HIP_TRY(V.kf_ptr.alloc(V.h_kf_ptr.size())); HIP_TRY(V.kf_lmk.alloc(V.h_kf_lmk.size()));
-    HIP_TRY(hipMemcpyAsync(V.kf_ptr.p, V.h_kf_ptr.data(), sizeof(int) * V.h_kf_ptr.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(V.kf_lmk.p, V.h_kf_lmk.data(), sizeof(int) * V.h_kf_lmk.size(), hipMemcpyHostToDevice, h->stream));
     const CovDev C = cov_dev(h, w, R);
-    const CovSqrtDev Q{V.sq_jp.p, V.sq_q.p, V.sq_ent.p, V.kf_ptr.p, V.kf_lmk.p};
-    ScopedTimer t(h, "cov_assemble_sqrt");
+    ScopedTimer t(h, R.sqrt ? "cov_assemble_sqrt" : "cov_assemble");
     const int n_tab = std::max(d.n_kf, d.n_lmk);
     hipLaunchKernelGGL(k_cov_tables, dim3((n_tab + 255) / 256), dim3(256), 0, h->stream, P, C, V.ptab.p);
     const int n_tiles = d.tile_end - d.tile_begin;
-    if (n_tiles > 0) hipLaunchKernelGGL(R.pix ? k_cov_assemble_sqrt<0> : k_cov_assemble_sqrt<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C, Q);
+    if (n_tiles > 0) {
+        if (R.sqrt) hipLaunchKernelGGL(R.pix ? k_cov_assemble_sqrt<0> : k_cov_assemble_sqrt<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C, Q);
+        else hipLaunchKernelGGL(R.pix ? k_cov_assemble<0> : k_cov_assemble<1>, dim3(n_tiles), dim3(COV_THREADS), 0, h->stream, P, C);
+    }
     if (int rc = cov_assemble_long(h, R, P, C, Q)) return rc;
     if (R.Np == 0) { HIP_TRY(hipGetLastError()); return SADVIO_OK; }
-    if (d.n_free_kf > 0) {
-        ScopedTimer ts(h, R.band || R.n_long > 0 ? "k_cov_schur_sqrt" : nullptr);
-        hipLaunchKernelGGL(k_cov_schur_sqrt, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C, Q);
+    if (d.n_free_kf > 0) {   // (band route, long tracks: a class of its own inside the assembly's span, for the profile)
+        ScopedTimer ts(h, R.band || R.n_long > 0 ? (R.sqrt ? "k_cov_schur_sqrt" : "k_cov_schur") : nullptr);
+        if (R.sqrt) hipLaunchKernelGGL(k_cov_schur_sqrt, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C, Q);
+        else hipLaunchKernelGGL(k_cov_schur, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C);
     }
     if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
     {
@@ -322,6 +309,49 @@ int cov_landmarks(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     return SADVIO_OK;
 }
 
+// The call's wait, and the kernel timers behind it
+int cov_wait(sadvio_ba_handle* h) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->cfg.profile_kernels) collect_timers(h);
+    return SADVIO_OK;
+}
+
+// The refusal of a window whose S failed a pivot test, behind the call's wait (waited: the caller has waited already)
+const char* const COV_NOT_USABLE = "covariance: the reduced information matrix is not positive definite (gauge not fixed: no constant key-frame, no prior)";
+int cov_not_usable(sadvio_ba_handle* h, bool waited = false) {
+    if (!waited)
+        if (int rc = cov_wait(h)) return rc;
+    h->err = COV_NOT_USABLE;
+    return SADVIO_E_NOT_USABLE;
+}
+
+// The key-frame and pair blocks asked for (null: not wanted), dpf x dpf each, out of Sigma_pp = sig [n][n] by free index; zero where
+// a key-frame is constant
+void cov_pick_blocks(const LayoutPlan& plan, const WinDev& d, const sadvio_cov_request* rq, const double* sig, int n, double* kf_cov, double* pair_cov) {
+    const int dpf = d.dpf;
+    auto block = [&](int ka, int kb, double* out) {
+        const int fa = plan.kf_fidx[d.kf_base + ka], fb = plan.kf_fidx[d.kf_base + kb];
+        for (int i = 0; i < dpf; i++)
+            for (int j = 0; j < dpf; j++) out[i * dpf + j] = (fa >= 0 && fb >= 0 && n > 0) ? sig[(size_t)(fa * dpf + i) * n + fb * dpf + j] : 0.0;
+    };
+    if (kf_cov) for (int i = 0; i < rq->n_kf; i++) block(rq->kf[i], rq->kf[i], kf_cov + (size_t)i * dpf * dpf);
+    if (pair_cov) for (int i = 0; i < rq->n_pair; i++) block(rq->pair_a[i], rq->pair_b[i], pair_cov + (size_t)i * dpf * dpf);
+}
+
+// The landmark blocks asked for out of the window's table lout [n_lmk][9], and how many of the landmarks asked for are singular by
+// status [n_lmk] (either output null: not wanted, and its table is not read)
+void cov_pick_landmarks(const sadvio_cov_request* rq, const WinDev& d, const double* lout, const int* status, double* lmk_cov, int32_t* n_lmk_singular) {
+    const int n_out = rq->n_lmk < 0 ? d.n_lmk : rq->n_lmk;
+    if (lmk_cov && rq->n_lmk < 0 && n_out > 0) memcpy(lmk_cov, lout, 72 * (size_t)n_out);
+    int n_sing = 0;
+    for (int i = 0; i < n_out; i++) {
+        const int l = rq->n_lmk < 0 ? i : rq->lmk[i];
+        if (lmk_cov && rq->n_lmk >= 0) memcpy(lmk_cov + 9 * (size_t)i, lout + 9 * (size_t)l, 72);
+        if (n_lmk_singular) n_sing += status[l] == COV_LMK_SINGULAR ? 1 : 0;
+    }
+    if (n_lmk_singular) *n_lmk_singular = n_sing;
+}
+
 // 5 (band route). The columns of the pair blocks outside the band by substitution with L's band, one workgroup per distinct column
 // key-frame: the canonical block is (a, b), a > b in free index, and (b, a) is read as its transpose, so pair(a, b) and
 // pair(b, a)^T agree to the bit and a pair's bits do not depend on what else was asked for. The blocks asked for are gathered on the
@@ -375,21 +405,11 @@ int cov_read_back_band(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq,
     }
     int flag[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(flag, V.bflag.p, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->cfg.profile_kernels) collect_timers(h);
-    if (flag[0] != 0) {
-        h->err = "covariance: the reduced information matrix is not positive definite (gauge not fixed: no constant key-frame, no prior)";
-        return SADVIO_E_NOT_USABLE;
-    }
+    if (int rc = cov_wait(h)) return rc;
+    if (flag[0] != 0) return cov_not_usable(h, true);
     if (nk > 0) memcpy(kf_cov, out.data(), sizeof(double) * (size_t)nk * bs);
     if (np > 0) memcpy(pair_cov, out.data() + (size_t)nk * bs, sizeof(double) * (size_t)np * bs);
-    if (R.want_lmk)
-        for (int i = 0; i < R.n_lmk_out; i++) memcpy(lmk_cov + 9 * (size_t)i, &lo[9 * (size_t)(rq->n_lmk < 0 ? i : rq->lmk[i])], 72);
-    if (n_lmk_singular) {
-        int n_sing = 0;
-        for (int i = 0; i < R.n_lmk_out; i++) n_sing += st[rq->n_lmk < 0 ? i : rq->lmk[i]] == COV_LMK_SINGULAR ? 1 : 0;
-        *n_lmk_singular = n_sing;
-    }
+    cov_pick_landmarks(rq, d, lo.data(), st.data(), lmk_cov, n_lmk_singular);
     return SADVIO_OK;
 }
 
@@ -402,7 +422,6 @@ int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, cons
     if (R.band) return cov_read_back_band(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
     std::vector<double>& sig = V.h_sig; std::vector<double>& lo = V.h_lout;
     const bool want_pp = n > 0 && ((kf_cov && rq->n_kf > 0) || (pair_cov && rq->n_pair > 0));
-    int n_sing = 0;
     if (want_pp) { sig.resize((size_t)n * n); HIP_TRY(hipMemcpyAsync(sig.data(), V.Sig.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, h->stream)); }
     if (R.want_lmk) {
         lo.resize(9 * (size_t)d.n_lmk);
@@ -413,59 +432,48 @@ int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, cons
         st.resize(d.n_lmk);
         HIP_TRY(hipMemcpyAsync(st.data(), V.status.p, sizeof(int) * (size_t)d.n_lmk, hipMemcpyDeviceToHost, h->stream));
     }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->cfg.profile_kernels) collect_timers(h);
-    auto block = [&](int ka, int kb, double* out) {
-        const int fa = h->plan.kf_fidx[d.kf_base + ka], fb = h->plan.kf_fidx[d.kf_base + kb];
-        for (int i = 0; i < dpf; i++)
-            for (int j = 0; j < dpf; j++) out[i * dpf + j] = (fa >= 0 && fb >= 0 && n > 0) ? sig[(size_t)(fa * dpf + i) * n + fb * dpf + j] : 0.0;
-    };
-    if (kf_cov) for (int i = 0; i < rq->n_kf; i++) block(rq->kf[i], rq->kf[i], kf_cov + (size_t)i * dpf * dpf);
-    if (pair_cov) for (int i = 0; i < rq->n_pair; i++) block(rq->pair_a[i], rq->pair_b[i], pair_cov + (size_t)i * dpf * dpf);
-    if (R.want_lmk)
-        for (int i = 0; i < R.n_lmk_out; i++) memcpy(lmk_cov + 9 * (size_t)i, &lo[9 * (size_t)(rq->n_lmk < 0 ? i : rq->lmk[i])], 72);
-    if (n_lmk_singular) {   // among the landmarks asked for
-        for (int i = 0; i < R.n_lmk_out; i++) n_sing += st[rq->n_lmk < 0 ? i : rq->lmk[i]] == COV_LMK_SINGULAR ? 1 : 0;
-        *n_lmk_singular = n_sing;
-    }
+    if (int rc = cov_wait(h)) return rc;
+    cov_pick_blocks(h->plan, d, rq, sig.data(), n, kf_cov, pair_cov);
+    cov_pick_landmarks(rq, d, lo.data(), st.data(), lmk_cov, n_lmk_singular);
     return SADVIO_OK;
 }
 
-// Steps 2 to 5 with the assembly R names. SADVIO_E_NOT_USABLE: a pivot of S failed its test; the outputs are untouched.
-int cov_attempt(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const CovRoutes& R, double* kf_cov, double* pair_cov, double* lmk_cov,
-                int32_t* n_lmk_singular) {
-    if (int rc = R.sqrt ? cov_assemble_sqrt(h, w, R) : cov_assemble(h, w, R)) return rc;
+// Steps 2 to 5 with the assembly R names; last(R) is step 5, the call's wait and its outputs (cov_read_back for sadvio_ba_covariance,
+// covx_cross for sadvio_ba_covariance_cross). SADVIO_E_NOT_USABLE: a pivot of S failed its test; the outputs are untouched.
+template <class Last>
+int cov_attempt(sadvio_ba_handle* h, int w, const CovRoutes& R, const Last& last) {
+    if (int rc = cov_assemble(h, w, R)) return rc;
     bool usable = true;
     if (int rc = cov_invert(h, R, usable)) return rc;
-    if (!usable) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->cfg.profile_kernels) collect_timers(h);
-        h->err = "covariance: the reduced information matrix is not positive definite (gauge not fixed: no constant key-frame, no prior)";
-        return SADVIO_E_NOT_USABLE;
-    }
+    if (!usable) return cov_not_usable(h);
     if (int rc = cov_landmarks(h, w, R)) return rc;
-    return cov_read_back(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+    return last(R);
 }
 
 // The assembly of a call (SADVIO_COV_SQRT, read once in EnvCfg). Unset: the plain one, and only when the pivot tests refuse its S
 // (behind the call's wait on either route) the square-root one, with a second inversion, a second test and one further wait; a window
 // the plain form serves keeps its bits, a refused one pays one more assembly before the same refusal. 1: square-root from the
 // start. 0: plain only.
-int cov_steps(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, CovRoutes R, double* kf_cov, double* pair_cov, double* lmk_cov,
-              int32_t* n_lmk_singular) {
+template <class Last>
+int cov_steps(sadvio_ba_handle* h, int w, CovRoutes R, const Last& last) {
     R.sqrt = h->env.cov_sqrt == 1;
-    int rc = cov_attempt(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+    int rc = cov_attempt(h, w, R, last);
     if (rc == SADVIO_E_NOT_USABLE && !R.sqrt && h->env.cov_sqrt != 0) {
         R.sqrt = true;
-        rc = cov_attempt(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+        rc = cov_attempt(h, w, R, last);
     }
     return rc;
 }
 
+// cov_read_back as the last step of cov_attempt / cov_steps
+auto cov_read_back_into(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov, int32_t* n_lmk_singular) {
+    return [=](const CovRoutes& R) { return cov_read_back(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular); };
+}
+
 int cov_run(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, double* kf_cov, double* pair_cov, double* lmk_cov, int32_t* n_lmk_singular) {
-    if (int rc = cov_check(h, w, rq, lmk_cov)) return rc;
+    if (int rc = cov_check(h, w, rq)) return rc;
     HIP_TRY(hipSetDevice(h->device));
-    return cov_steps(h, w, rq, cov_routes(h, w, rq, lmk_cov), kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+    return cov_steps(h, w, cov_routes(h, w, rq, lmk_cov), cov_read_back_into(h, w, rq, kf_cov, pair_cov, lmk_cov, n_lmk_singular));
 }
 
 }  // namespace

@@ -22,7 +22,17 @@
 //   k_cov_lmk       the landmark blocks: one landmark per group of G lanes (below)
 // S and the landmark blocks have a second assembly, the square-root one (k_cov_assemble_sqrt, k_cov_schur_sqrt, k_cov_lmk<G, true>,
 // further down): the same quantities without the difference above, for windows with landmarks millimetres from a camera centre.
-// cov_driver.h (cov_steps) says which runs. The kernels of the plain assembly are untouched by it.
+// cov_driver.h (cov_steps) says which runs.
+// Bodies and wrappers: the work of k_cov_tables, k_cov_schur, k_cov_kept, k_cov_factors and k_cov_dense is written once, in a
+// __device__ __forceinline__ body (cov_tables_body ... cov_dense_body) that takes DevPtrs, CovDev and WinDev by reference. The
+// __global__ k_cov_* below each body is the wrapper of sadvio_ba_covariance (CovDev is a kernel argument, WinDev a local copy);
+// cov_batch_kernels.h holds the second wrapper, k_covb_*, which loads CovDev from the call's unit table. What says how a sum is
+// ordered or why a step is there stands on the body.
+// Two kernels are exceptions and stay two copies of one text each, here and in cov_batch_kernels.h; a change to one copy is made to
+// the other. k_cov_assemble: behind a shared body the compiler contracts other products into its fused multiply-adds, and every
+// block of both calls moves in the last place (measured on the MI355X with scripts/cov_same_results.py); the copies give the bits
+// they always gave. k_cov_lmk: the batch call's copy has no long-track test, and behind the shared body k_covb_lmk ran 0.3 - 0.4 %
+// longer on 64 config-2 windows (profiles/r24_cov_shared_bodies.txt).
 // Long tracks (landmarks the planner keeps out of the tiles) get their rows of the same tables from k_cov_long and their landmark
 // blocks from k_cov_lmk_long (cov_long_kernels.h); every other kernel here reads them like any landmark.
 // A landmark whose H_ll is not positive definite (one observation; a pivot within 64 ulps of its diagonal entry) is left out of H
@@ -59,8 +69,7 @@ struct CovDev {
     int* is_long;            // [n_lmk] 1: a long track, filled by k_cov_long and left to k_cov_lmk_long (cov_long_kernels.h); null: the window has none
 };
 
-__global__ void k_cov_tables(DevPtrs P, CovDev C, double* ptab) {
-    const WinDev W = P.win[C.w];
+__device__ __forceinline__ void cov_tables_body(const DevPtrs& P, const CovDev& C, const WinDev& W, double* ptab) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < W.n_lmk) {   // a landmark no tile lists (no observation) has no information of its own
         const int lc = P.lmk_const ? P.lmk_const[W.lmk_base + k] : 0;
@@ -74,6 +83,11 @@ __global__ void k_cov_tables(DevPtrs P, CovDev C, double* ptab) {
     for (int i = 0; i < 12; i++) T0[i] = P.kf_T0[12 * kf + i];
     pose_table_entry(T0, d6, tab);
     for (int i = 0; i < POSE_TAB; i++) ptab[kf * POSE_TAB + i] = tab[i];
+}
+
+__global__ void k_cov_tables(DevPtrs P, CovDev C, double* ptab) {
+    const WinDev W = P.win[C.w];
+    cov_tables_body(P, C, W, ptab);
 }
 
 // Jacobians of observation o of landmark position pw at x*, corrected as the solve corrects them (lane_linearize, k_build_kept)
@@ -193,15 +207,7 @@ __global__ __launch_bounds__(COV_THREADS) void k_cov_assemble(DevPtrs P, CovDev 
 }
 
 // The 6 x 6 pose block (a, b), a >= b, of S over the visual factors: sum_l [a == b] sum Jp^T Jp - W_a^T H_ll W_b.
-__global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur(DevPtrs P, CovDev C) {
-    const WinDev W = P.win[C.w];
-    int a = 0, b;
-    if (C.pair_tab) {   // band route: the pair comes from the table of in-band pairs
-        a = C.pair_tab[2 * blockIdx.x]; b = C.pair_tab[2 * blockIdx.x + 1];
-    } else {
-        while ((a + 1) * (a + 2) / 2 <= (int)blockIdx.x) a++;
-        b = (int)blockIdx.x - a * (a + 1) / 2;
-    }
+__device__ __forceinline__ void cov_schur_body(const DevPtrs& P, const CovDev& C, const WinDev& W, int a, int b) {
     const int ca = a * W.dpf, cb = b * W.dpf;
     double acc[36];
 #pragma unroll
@@ -259,6 +265,18 @@ __global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur(DevPtrs P, CovD
     }
 }
 
+__global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur(DevPtrs P, CovDev C) {
+    int a = 0, b;
+    if (C.pair_tab) {   // band route: the pair comes from the table of in-band pairs
+        a = C.pair_tab[2 * blockIdx.x]; b = C.pair_tab[2 * blockIdx.x + 1];
+    } else {
+        while ((a + 1) * (a + 2) / 2 <= (int)blockIdx.x) a++;
+        b = (int)blockIdx.x - a * (a + 1) / 2;
+    }
+    const WinDev W = P.win[C.w];
+    cov_schur_body(P, C, W, a, b);
+}
+
 // ---- the square-root assembly ----------------------------------------------------------------------------------------------------
 // The same S and landmark blocks without the difference H_pp - W^T H_ll W: a landmark millimetres from a camera centre puts 1e12
 // and more into H_pp beside entries of S of 1e10, and the plain form then loses S to rounding ("Near-camera landmarks").
@@ -272,8 +290,7 @@ __global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur(DevPtrs P, CovD
 // with a second orthogonalisation pass (orthonormal to a few ulps while cond(J_l) eps < 1; R = chol(H_ll) would lose it with
 // cond(H_ll)), in place on the landmark's rows of CovSqrtDev::q. Singular: fewer than two observations, or r_ii^2 <= 64 eps |column i|^2 —
 // cov_sym3_inverse's pivot rule stated through R.
-// What the square-root assembly keeps beside CovDev (a kernel argument of its own: CovDev and with it the plain assembly's kernels stay
-// as they are). On this route CovDev::hll holds R (upper: 00 01 02 11 12 22) and CovDev::ent_w the couplings C_a (3 x 6).
+// What the square-root assembly keeps beside CovDev (a kernel argument of its own). On this route CovDev::hll holds R (upper: 00 01 02 11 12 22) and CovDev::ent_w the couplings C_a (3 x 6).
 struct CovSqrtDev {
     double* jp;              // [n_obs][12] the two J_p rows of every observation
     double* q;               // [n_obs][6] the two rows of Q1 (zero for a landmark that is not eliminated)
@@ -435,8 +452,7 @@ __global__ __launch_bounds__(COV_SCHUR_THREADS) void k_cov_schur_sqrt(DevPtrs P,
 
 // Landmarks kept in the reduced system: Jl^T Jl and Jl^T Jp of their observations (Jp^T Jp went through k_cov_schur).
 template <int FACTOR>
-__global__ __launch_bounds__(64) void k_cov_kept(DevPtrs P, CovDev C) {
-    const WinDev W = P.win[C.w];
+__device__ __forceinline__ void cov_kept_body(const DevPtrs& P, const CovDev& C, const WinDev& W) {
     __shared__ double J[2 * 9];   // rows: [Jp 6 | Jl 3]
     __shared__ int col[9];
     const int t = threadIdx.x;
@@ -466,6 +482,12 @@ __global__ __launch_bounds__(64) void k_cov_kept(DevPtrs P, CovDev C) {
     }
 }
 
+template <int FACTOR>
+__global__ __launch_bounds__(64) void k_cov_kept(DevPtrs P, CovDev C) {
+    const WinDev W = P.win[C.w];
+    cov_kept_body<FACTOR>(P, C, W);
+}
+
 // S[col a][col c] += sum_q J[q][a] J[q][c]: every (a, c) by one lane, factor after factor behind workgroup barriers
 __device__ __forceinline__ void cov_accumulate(double* S, int Np, const double* J, int rows, int ncols, const int* col, int t, int nthr) {
     for (int idx = t; idx < ncols * ncols; idx += nthr) {
@@ -479,11 +501,12 @@ __device__ __forceinline__ void cov_accumulate(double* S, int Np, const double* 
 
 // ImuDev under a name of its own: imu_factor_body<CovImu, ..> is then an instantiation of its own, and the one k_marg_small calls
 // keeps its single caller (with a second caller the compiler no longer specialises it on k_marg_small's constant arguments, and
-// that kernel's code changes)
+// that kernel's code changes). For the same reason cov_factors_body takes the name as its template parameter IMU: every kernel
+// that calls the body brings a name of its own (CovBatchImu in cov_batch_kernels.h), and each instantiation has one caller.
 struct CovImu : ImuDev {};
 
-__global__ __launch_bounds__(64) void k_cov_factors(DevPtrs P, CovDev C) {
-    const WinDev W = P.win[C.w];
+template <class IMU>
+__device__ __forceinline__ void cov_factors_body(const DevPtrs& P, const CovDev& C, const WinDev& W) {
     const int t = threadIdx.x;
     const double* xp = P.xp + (long long)C.cur * P.xp_stride;
     const double* xv = P.xv + (long long)C.cur * P.xv_stride;
@@ -510,15 +533,15 @@ __global__ __launch_bounds__(64) void k_cov_factors(DevPtrs P, CovDev C) {
     }
     // IMUFactor + IMUBiasFactor (as k_marg_small evaluates them: lane 0 the un-whitened Jacobian, 24 lanes the whitening)
     for (int k = W.imu_begin; k < W.imu_end; k++) {
-        const CovImu& f = *static_cast<const CovImu*>(P.imus + k);
+        const IMU& f = *static_cast<const IMU*>(P.imus + k);
         const int i = f.kf_i, j = f.kf_j;
         const int fi = P.kf_fidx[i], fj = P.kf_fidx[j];
         if (t == 0) {
             double r[9];
             for (int q = 0; q < 9 * 24; q++) sJ[q] = 0.0;
-            imu_factor_body<CovImu, false>(f, P.kf_T0 + 12 * (long long)i, P.kf_T0 + 12 * (long long)j, P.kf_vel + 3 * (long long)i, P.kf_vel + 3 * (long long)j,
-                                           xp + 6 * (long long)i, xp + 6 * (long long)j, xv + 3 * (long long)i, xv + 3 * (long long)j, xba + 3 * (long long)i,
-                                           xbg + 3 * (long long)i, r, sJ);
+            imu_factor_body<IMU, false>(f, P.kf_T0 + 12 * (long long)i, P.kf_T0 + 12 * (long long)j, P.kf_vel + 3 * (long long)i, P.kf_vel + 3 * (long long)j,
+                                        xp + 6 * (long long)i, xp + 6 * (long long)j, xv + 3 * (long long)i, xv + 3 * (long long)j, xba + 3 * (long long)i,
+                                        xbg + 3 * (long long)i, r, sJ);
             for (int a = 0; a < 24; a++) scol[a] = W.dpf == 15 ? imu_col(a, fi, fj) : -1;
         }
         __syncthreads();
@@ -568,9 +591,13 @@ __global__ __launch_bounds__(64) void k_cov_factors(DevPtrs P, CovDev C) {
     }
 }
 
-// dense prior r0 + J dx: its J^T J (formed at upload) through the column map kind[n] | index[n] | col[n]
-__global__ void k_cov_dense(DevPtrs P, CovDev C) {
+__global__ __launch_bounds__(64) void k_cov_factors(DevPtrs P, CovDev C) {
     const WinDev W = P.win[C.w];
+    cov_factors_body<CovImu>(P, C, W);
+}
+
+// dense prior r0 + J dx: its J^T J (formed at upload) through the column map kind[n] | index[n] | col[n]
+__device__ __forceinline__ void cov_dense_body(const DevPtrs& P, const CovDev& C, const WinDev& W) {
     const int n = W.dp_n;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)n * n) return;
@@ -579,6 +606,11 @@ __global__ void k_cov_dense(DevPtrs P, CovDev C) {
     if (col[a] < 0 || col[c] < 0) return;
     const double* H = P.dp_data + W.dp_off + 2LL * W.dp_n_full * n;
     C.S[(long long)col[a] * C.Np + col[c]] += H[(long long)a * n + c];
+}
+
+__global__ void k_cov_dense(DevPtrs P, CovDev C) {
+    const WinDev W = P.win[C.w];
+    cov_dense_body(P, C, W);
 }
 
 // ---- the landmark blocks -----------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// cov_kf_lists.h — the key-frame -> landmark lists of the square-root covariance assembly (cov_driver.h: cov_assemble_sqrt;
+// cov_kf_lists.h — the key-frame -> landmark lists of the square-root covariance assembly (cov_driver.h: cov_assemble;
 // cov_kernels.h: k_cov_schur_sqrt walks them). Host only, no HIP: tests/cpp/test_cov_kf_lists.cpp compiles it on its own.
 #pragma once
 #include <vector>
