@@ -66,6 +66,7 @@ typedef struct sadvio_ba_config {
 #define SADVIO_CFG_LONG_TRACKS 1
 #define SADVIO_CFG_LONG_TRACK_PRIORS 2 /* with SADVIO_CFG_LONG_TRACKS: marginalize, sparsify and the prior setters serve long tracks */
 #define SADVIO_CFG_LONG_TRACK_COVARIANCE 4 /* with SADVIO_CFG_LONG_TRACKS: sadvio_ba_covariance and _covariance_cross serve windows with long tracks */
+#define SADVIO_CFG_LONG_TRACK_BATCH 8 /* with SADVIO_CFG_LONG_TRACKS: sadvio_ba_marginalize_relative and _relative_batch serve windows with long tracks; with SADVIO_CFG_LONG_TRACK_COVARIANCE as well, sadvio_ba_covariance_batch */
 
 /*
  * One sliding window, flattened (SoA, index based). Replaces the object-graph walk of
@@ -100,7 +101,7 @@ typedef struct sadvio_ba_config {
  *   A held long track costs what any held landmark costs: 3 more columns of the reduced system in every LM step, and one thread
  *   per observation of it adding its rows (k_build_kept); its pose-pose part is still summed by the long kernels.
  *   sadvio_ba_covariance, _covariance_batch, _covariance_cross, sadvio_ba_marginalize_relative and _relative_batch refuse a window
- *   with long tracks as before, with this flag or without it.
+ *   with long tracks as before, with this flag or without it (the two flags below lift those refusals).
  *
  * Covariances of windows with long tracks. A handle created with SADVIO_CFG_LONG_TRACKS | SADVIO_CFG_LONG_TRACK_COVARIANCE (without
  * SADVIO_CFG_LONG_TRACKS: sadvio_ba_create fails with SADVIO_E_INVALID_ARG, the text through sadvio_ba_last_error(NULL)) serves
@@ -108,10 +109,22 @@ typedef struct sadvio_ba_config {
  * routes (dense, band) and the retry, with the bit guarantees of those calls. A long track's landmark block, its cross blocks and the
  * innovation of a candidate observation of it are what they are for any landmark: eliminated, constant (zeros), or — together with
  * SADVIO_CFG_LONG_TRACK_PRIORS — kept in the reduced system by a prior. The flag is independent of SADVIO_CFG_LONG_TRACK_PRIORS
- * (reserved = 1 | 4 and 1 | 2 | 4 are both valid). A handle without it keeps every refusal above with the same text. With it,
- * sadvio_ba_covariance_batch (its kernels hold S in LDS and walk the landmark tiles only), sadvio_ba_marginalize_relative and
- * sadvio_ba_marginalize_relative_batch still refuse a window with long tracks, with the same text. On any handle a window without
- * long tracks takes the launches it always took and returns the same bits. DESIGN.md "Covariances of windows with long tracks".
+ * (reserved = 1 | 4 and 1 | 2 | 4 are both valid). A handle without it keeps every refusal above with the same text. With it alone,
+ * sadvio_ba_covariance_batch, sadvio_ba_marginalize_relative and sadvio_ba_marginalize_relative_batch still refuse a window with
+ * long tracks, with the same text. On any handle a window without long tracks takes the launches it always took and returns the
+ * same bits. DESIGN.md "Covariances of windows with long tracks".
+ *
+ * Batch calls on windows with long tracks. A handle created with SADVIO_CFG_LONG_TRACKS | SADVIO_CFG_LONG_TRACK_BATCH (without
+ * SADVIO_CFG_LONG_TRACKS: sadvio_ba_create fails with SADVIO_E_INVALID_ARG, the text through sadvio_ba_last_error(NULL)) serves
+ * sadvio_ba_marginalize_relative and sadvio_ba_marginalize_relative_batch on a window that holds long tracks: a long track shared by
+ * the two key-frames is an item like any landmark, with the multiplicity, the cuts and the bits a walk over all its observations
+ * would give (its observations in the two key-frames are found by bisection). With SADVIO_CFG_LONG_TRACK_COVARIANCE as well
+ * (reserved = 1 | 4 | 8, or 1 | 2 | 4 | 8) sadvio_ba_covariance_batch serves such windows on every route, with the guarantees stated
+ * at that call; with SADVIO_CFG_LONG_TRACK_BATCH but without SADVIO_CFG_LONG_TRACK_COVARIANCE it keeps refusing, with the same text
+ * (its DENSE and BAND items, its retry and its SADVIO_COV_SQRT=1 items go through the steps of sadvio_ba_covariance, which that flag
+ * gates). A handle without SADVIO_CFG_LONG_TRACK_BATCH keeps all three refusals, text unchanged. After this, no call on a window
+ * held by one GPU refuses it for a long track on a handle with reserved = 1 | 2 | 4 | 8. DESIGN.md "Batch calls on windows with
+ * long tracks".
  * A window sharded over several GPUs has no long path: it is refused at 65 observations whatever the flags. On a handle with the flag, SADVIO_LONG_MIN in the environment (read by sadvio_ba_create; an
  * integer in [2, 65], default 65; tests and A/B timing) sends every landmark with at least that many observations down the long path.
  */
@@ -789,8 +802,11 @@ int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_reques
  * n_item = 0 returns SADVIO_OK and touches nothing.
  * No floating-point atomics: two calls return the same bits, and an item's bits depend neither on the other items of the call nor
  * on its position among them. The solve's deltas, summaries, trace and the handle's prior are left untouched.
- * A window with long tracks is refused (SADVIO_E_INVALID_ARG, a text that names them) on every handle, one created with
- * SADVIO_CFG_LONG_TRACK_COVARIANCE included: call sadvio_ba_covariance per window there. */
+ * A window with long tracks is served on a handle created with SADVIO_CFG_LONG_TRACKS | SADVIO_CFG_LONG_TRACK_COVARIANCE |
+ * SADVIO_CFG_LONG_TRACK_BATCH, on every route and with every guarantee above: on the LDS and NONE routes a long track's rows of the
+ * unit's tables and its landmark block come from one workgroup per track (kernel classes k_covb_long and k_covb_lmk_long, which
+ * appear only when a group holds a long track), the other routes are the single call's. On every other handle an item that names
+ * such a window fails the whole call (SADVIO_E_INVALID_ARG, a text that names long tracks) before anything is written. */
 #define SADVIO_COV_ROUTE_NONE  0
 #define SADVIO_COV_ROUTE_LDS   1
 #define SADVIO_COV_ROUTE_DENSE 2

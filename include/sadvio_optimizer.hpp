@@ -300,11 +300,14 @@ class HipOptimizer {
     // long_tracks: landmarks with more than 64 observations are accepted (SADVIO_CFG_LONG_TRACKS, sadvio_ba.h); such a window is
     // marginalised, sparsified and given priors on its long tracks only with long_track_priors (SADVIO_CFG_LONG_TRACK_PRIORS), and asked
     // for covariances (covariance(), covarianceCross(); not the batch call) only with long_track_covariance
-    // (SADVIO_CFG_LONG_TRACK_COVARIANCE). Both need long_tracks and are independent of each other
+    // (SADVIO_CFG_LONG_TRACK_COVARIANCE). Both need long_tracks and are independent of each other. long_track_batch
+    // (SADVIO_CFG_LONG_TRACK_BATCH, needs long_tracks): marginalizeRelative() and marginalizeRelativeBatch() serve such a window, and
+    // with long_track_covariance the batch covariance call does
     explicit HipOptimizer(int device = 0, bool angular = false, bool long_tracks = false, bool long_track_priors = false,
-                          bool long_track_covariance = false) : _angular(angular) {
+                          bool long_track_covariance = false, bool long_track_batch = false) : _angular(angular) {
         sadvio_ba_config cfg{device, 0, 1, (long_tracks ? SADVIO_CFG_LONG_TRACKS : 0) | (long_track_priors ? SADVIO_CFG_LONG_TRACK_PRIORS : 0) |
-                                               (long_track_covariance ? SADVIO_CFG_LONG_TRACK_COVARIANCE : 0)};
+                                               (long_track_covariance ? SADVIO_CFG_LONG_TRACK_COVARIANCE : 0) |
+                                               (long_track_batch ? SADVIO_CFG_LONG_TRACK_BATCH : 0)};
         const int rc = sadvio_ba_create(&cfg, &_h);
         if (rc == SADVIO_E_INVALID_ARG) throw std::runtime_error(std::string("sadvio: ") + sadvio_ba_last_error(nullptr));
         if (rc != SADVIO_OK) throw std::runtime_error("sadvio: no usable gfx950 device");

@@ -21,6 +21,7 @@ SADVIO_OK = 0
 CFG_LONG_TRACKS = 1   # sadvio_ba_config.reserved: SADVIO_CFG_LONG_TRACKS
 CFG_LONG_TRACK_PRIORS = 2   # ... SADVIO_CFG_LONG_TRACK_PRIORS (with CFG_LONG_TRACKS)
 CFG_LONG_TRACK_COVARIANCE = 4   # ... SADVIO_CFG_LONG_TRACK_COVARIANCE (with CFG_LONG_TRACKS)
+CFG_LONG_TRACK_BATCH = 8   # ... SADVIO_CFG_LONG_TRACK_BATCH (with CFG_LONG_TRACKS)
 E_INVALID_ARG, E_NOT_USABLE, E_HIP, E_RCCL, E_NO_DEVICE, E_STATE, E_REFUSED = -1, -2, -3, -4, -5, -6, -7
 FACTOR_PIXEL, FACTOR_ANGULAR = 0, 1
 TERM_NAMES = {0: "NO_CONVERGENCE", 1: "FUNCTION_TOL", 2: "PARAMETER_TOL", 3: "GRADIENT_TOL", 4: "MIN_RADIUS",
@@ -478,14 +479,16 @@ class Backend:
     """Thin OO wrapper of one `sadvio_ba_handle` (one HIP stream, device-resident windows)."""
 
     def __init__(self, device: int = 0, profile_kernels: bool = False, use_graph: bool = False, long_tracks: bool = False,
-                 long_track_priors: bool = False, long_track_covariance: bool = False):
+                 long_track_priors: bool = False, long_track_covariance: bool = False, long_track_batch: bool = False):
         """long_tracks: SADVIO_CFG_LONG_TRACKS, the handle accepts landmarks with more than 64 observations.
         long_track_priors: SADVIO_CFG_LONG_TRACK_PRIORS (needs long_tracks), marginalize, sparsify and the prior setters serve them.
         long_track_covariance: SADVIO_CFG_LONG_TRACK_COVARIANCE (needs long_tracks), covariance and covariance_cross serve windows
-        that hold them."""
+        that hold them.
+        long_track_batch: SADVIO_CFG_LONG_TRACK_BATCH (needs long_tracks), marginalize_relative and marginalize_relative_batch serve
+        such windows, and covariance_batch does with long_track_covariance as well."""
         self.lib = load_library()
         flags = ((CFG_LONG_TRACKS if long_tracks else 0) | (CFG_LONG_TRACK_PRIORS if long_track_priors else 0)
-                 | (CFG_LONG_TRACK_COVARIANCE if long_track_covariance else 0))
+                 | (CFG_LONG_TRACK_COVARIANCE if long_track_covariance else 0) | (CFG_LONG_TRACK_BATCH if long_track_batch else 0))
         cfg = Config(device=device, profile_kernels=int(profile_kernels), use_graph=int(use_graph), reserved=flags)
         self.h = C.c_void_p()
         rc = self.lib.sadvio_ba_create(C.byref(cfg), C.byref(self.h))

@@ -57,6 +57,10 @@ int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
         create_err = "create: SADVIO_CFG_LONG_TRACK_COVARIANCE needs SADVIO_CFG_LONG_TRACKS (a handle without the long path has no long track to form a covariance of)";
         return SADVIO_E_INVALID_ARG;
     }
+    if (cfg && (cfg->reserved & SADVIO_CFG_LONG_TRACK_BATCH) && !(cfg->reserved & SADVIO_CFG_LONG_TRACKS)) {
+        create_err = "create: SADVIO_CFG_LONG_TRACK_BATCH needs SADVIO_CFG_LONG_TRACKS (a handle without the long path has no long track for a batch call to serve)";
+        return SADVIO_E_INVALID_ARG;
+    }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return SADVIO_E_NO_DEVICE;
     int dev = cfg ? cfg->device : 0;
@@ -75,6 +79,8 @@ int sadvio_ba_create(const sadvio_ba_config* cfg, sadvio_ba_handle** out) {
     h->env.long_priors = (h->cfg.reserved & SADVIO_CFG_LONG_TRACK_PRIORS) != 0;
     // ... and asked for covariances (the single call and the cross call) on handles that ask for that: independent of the priors' flag
     h->env.long_cov = (h->cfg.reserved & SADVIO_CFG_LONG_TRACK_COVARIANCE) != 0;
+    // ... and the relative marginalisations, and with the covariance flag covariance_batch, on handles that ask for that
+    h->env.long_batch = (h->cfg.reserved & SADVIO_CFG_LONG_TRACK_BATCH) != 0;
     h->device = dev;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return SADVIO_E_HIP; }
     if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) h->side = nullptr;   // optional: without it everything is serial
@@ -516,7 +522,8 @@ int sadvio_ba_marginalize_relative(sadvio_ba_handle* h, int32_t w, int32_t kf_a,
     if (h->world > 1) { h->err = "marginalize_relative: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }
     const WinDev& d = h->plan.wins[w].d;
     if (kf_a < 0 || kf_a >= d.n_kf || kf_b < 0 || kf_b >= d.n_kf || kf_a == kf_b) { h->err = "marginalize_relative: bad key-frame index"; return SADVIO_E_INVALID_ARG; }
-    if (int rc = refuse_long(h, w, "marginalize_relative")) return rc;
+    if (!h->env.long_batch)   // (SADVIO_CFG_LONG_TRACK_BATCH: served; a long track's observations are found by bisection, rel_runs.h)
+        if (int rc = refuse_long(h, w, "marginalize_relative")) return rc;
     if (d.has_imu) { h->err = "marginalize_relative: frames with IMU states are not supported (the reference's own column layout for them is inconsistent, BundleAdjustmentCERESAnalytic.cpp:705-737)"; return SADVIO_E_INVALID_ARG; }
     return marginalize_relative(h, w, kf_a, kf_b, eig_cut_mode, inf36, Ak144);
 }
@@ -1037,7 +1044,9 @@ extern "C" {
 // ---- the covariances of many windows of the solved batch in one call ----
 int sadvio_ba_covariance_batch(sadvio_ba_handle* h, int32_t n_item, sadvio_cov_batch_item* items) {
     if (!h) return SADVIO_E_INVALID_ARG;
-    for (int i = 0; items && i < n_item; i++)
+    // (SADVIO_CFG_LONG_TRACK_BATCH with SADVIO_CFG_LONG_TRACK_COVARIANCE: served — k_covb_long / k_covb_lmk_long on the group path, and
+    // the single call's steps, which the covariance flag gates, for DENSE, BAND, square-root and retried items)
+    for (int i = 0; items && i < n_item && !(h->env.long_batch && h->env.long_cov); i++)
         if (int rc = refuse_long(h, items[i].w, "covariance_batch")) return rc;
     return covb_run(h, n_item, items);
 }
@@ -1068,7 +1077,8 @@ extern "C" {
 int sadvio_ba_marginalize_relative_batch(sadvio_ba_handle* h, int32_t w, int32_t n_pair, const int32_t* kf_a, const int32_t* kf_b, int32_t eig_cut_mode,
                                          double* inf36, double* Ak144, double* T_a_b, int32_t* n_shared, int32_t* status) {
     if (!h) return SADVIO_E_INVALID_ARG;
-    if (int rc = refuse_long(h, w, "marginalize_relative_batch")) return rc;
+    if (!h->env.long_batch)
+        if (int rc = refuse_long(h, w, "marginalize_relative_batch")) return rc;
     return rel_run(h, w, n_pair, kf_a, kf_b, eig_cut_mode, inf36, Ak144, T_a_b, n_shared, status);
 }
 

@@ -229,6 +229,7 @@ struct CovBatchScratch {
     DevBuf<int> ipool;
     DevBuf<char> units;
     char* pinned = nullptr; size_t pinned_cap = 0;
+    size_t tab_bytes = 0;   // of the current call's tables (units and long-track rows) in `units` and at the head of `pinned`
     hipError_t pin(size_t bytes) {
         if (bytes <= pinned_cap) return hipSuccess;
         if (pinned) (void)hipHostFree(pinned);
@@ -268,6 +269,7 @@ struct EnvCfg {
     int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range)
     bool long_priors = false;   // SADVIO_CFG_LONG_TRACK_PRIORS: marginalize, sparsify and the prior setters serve long tracks. Set by sadvio_ba_create
     bool long_cov = false;      // SADVIO_CFG_LONG_TRACK_COVARIANCE: covariance and covariance_cross serve a window with long tracks. Set by sadvio_ba_create
+    bool long_batch = false;    // SADVIO_CFG_LONG_TRACK_BATCH: marginalize_relative(_batch) serve a window with long tracks, and with long_cov covariance_batch. Set by sadvio_ba_create
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {

@@ -12,6 +12,11 @@
 // inherit its choice and its retry. With the variable = 1 the LDS items go down the DENSE route and the NONE items through the same
 // steps; with it unset, an LDS item whose unit failed the pivot test is retried on its own through those steps in square-root form
 // behind the call's wait (covb_retry_item), and items that were served keep their bits.
+// Long tracks (ba_capi.hip refuses them unless the handle has SADVIO_CFG_LONG_TRACK_COVARIANCE | SADVIO_CFG_LONG_TRACK_BATCH): a group
+// whose units hold some uploads a work table behind its unit table (covb_long_plan.h: unit | index on the long list, units and tracks
+// ascending) and launches k_covb_long behind k_covb_assemble and k_covb_lmk_long behind k_covb_lmk, one workgroup per row; such a unit
+// gets a zeroed is_long array from the int pool. A group without long tracks takes the launches it always took. Items on the single
+// call's steps are served by cov_driver.h's long kernels.
 //
 // After a solve by the throughput kernels (lm_kernels.h). sadvio_ba_covariance refuses such a batch; this call accepts it, on these
 // grounds. (i) Both solve paths keep two delta buffers per array and LmState::cur names the one holding the accepted state x: k_solve
@@ -25,6 +30,7 @@
 #pragma once
 #include "cov_batch_kernels.h"
 #include "cov_driver.h"
+#include "covb_long_plan.h"
 
 namespace {
 
@@ -38,7 +44,10 @@ struct CovbUnit {
 };
 // A unit's result block, one piece of device memory copied to the host in one go with its group's: Sigma_pp [nn] | lout [r_lout] |
 // landmark status [nl ints] | pivot flag [1 int]
-struct CovbGroup { int u0 = 0, u1 = 0; size_t doubles = 0, ints = 0, r_doubles = 0, r0 = 0; };
+// l0 / n_long: the long tracks of the call's units in front of the group | of the group's units (rows of its work table)
+struct CovbGroup { int u0 = 0, u1 = 0; size_t doubles = 0, ints = 0, r_doubles = 0, r0 = 0; int l0 = 0, n_long = 0; };
+// The group's work table of long tracks on the device (covb_long_plan.h), from covb_assemble to covb_landmarks; n_rows = 0: none
+struct CovbLong { const int* d_rows = nullptr; int n_rows = 0, max_kf = 0; };
 
 // 1. State and arguments, with the codes and the order of sadvio_ba_covariance (a batch the throughput kernels solved is served: see
 // above). Host work only; nothing is written on an error.
@@ -78,6 +87,7 @@ void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, 
             U.w = I.w; U.R = R; U.R.want_lmk = false; U.route = I.route;
             U.nl = (size_t)std::max(d.n_lmk, 1); U.no = (size_t)std::max(d.n_obs, 1); U.nn = (size_t)std::max(d.Np, 1) * std::max(d.Np, 1);
             U.bytes = sizeof(double) * (21 * U.nl + (COV_ENT_W + COV_ENT_HPP) * U.no + 2 * U.nn) + sizeof(int) * (2 * U.nl + U.no + 1);
+            if (R.n_long > 0) U.bytes += sizeof(int) * U.nl;   // CovDev::is_long
             units.push_back(U);
         }
         CovbUnit& U = units[of_win[I.w]];
@@ -111,37 +121,50 @@ int covb_groups(sadvio_ba_handle* h, std::vector<CovbUnit>& units, std::vector<C
     CovBatchScratch& B = h->cvb;
     const size_t budget = (size_t)std::max(h->env.cov_batch_scratch_mb, 0) << 20;
     size_t used = 0, max_d = 1, max_i = 1, max_r = 1, r_tot = 0;
+    int l_tot = 0;
     for (int u = 0; u < (int)units.size(); u++) {
         CovbUnit& U = units[u];
-        if (groups.empty() || used + U.bytes > budget) { groups.push_back(CovbGroup{u, u, 0, 0, 0, r_tot}); used = 0; }
+        if (groups.empty() || used + U.bytes > budget) { groups.push_back(CovbGroup{u, u, 0, 0, 0, r_tot, l_tot, 0}); used = 0; }
         CovbGroup& g = groups.back();
         U.r_lout = U.R.want_lmk ? 9 * U.nl : 0;
         U.r_size = U.nn + U.r_lout + (U.nl + 1) / 2 + 1;
         U.r_off = r_tot; r_tot += U.r_size;
         g.u1 = u + 1; g.doubles += 12 * U.nl + (COV_ENT_W + COV_ENT_HPP) * U.no + U.nn; g.ints += U.nl + U.no; g.r_doubles += U.r_size;
+        if (U.R.n_long > 0) { g.ints += U.nl; g.n_long += U.R.n_long; l_tot += U.R.n_long; }
         used += U.bytes;
         max_d = std::max(max_d, g.doubles); max_i = std::max(max_i, g.ints); max_r = std::max(max_r, g.r_doubles);
     }
     HIP_TRY(B.pool.alloc(max_d)); HIP_TRY(B.ipool.alloc(max_i)); HIP_TRY(B.rpool.alloc(max_r));
     HIP_TRY(B.ptab.alloc((size_t)h->plan.n_kf_tot * POSE_TAB));
-    HIP_TRY(B.units.alloc(sizeof(CovUnit) * units.size()));
-    HIP_TRY(B.pin(sizeof(CovUnit) * units.size() + sizeof(double) * r_tot));
+    // the tables, group after group: a group's units, then its long tracks' rows (8 bytes each: what follows stays aligned)
+    static_assert(sizeof(int) * COVB_LONG_ROW == 8 && sizeof(CovUnit) % 8 == 0, "the tables are laid out back to back");
+    B.tab_bytes = sizeof(CovUnit) * units.size() + sizeof(int) * COVB_LONG_ROW * (size_t)l_tot;
+    HIP_TRY(B.units.alloc(B.tab_bytes));
+    HIP_TRY(B.pin(B.tab_bytes + sizeof(double) * r_tot));
     return SADVIO_OK;
 }
 
-// the call's result blocks in the pinned block, behind the unit tables
-double* covb_host_results(sadvio_ba_handle* h, const std::vector<CovbUnit>& units) { return (double*)(h->cvb.pinned + sizeof(CovUnit) * units.size()); }
+// where group g's tables start in the pinned block and in CovBatchScratch::units
+size_t covb_tab_offset(const CovbGroup& g) { return sizeof(CovUnit) * (size_t)g.u0 + sizeof(int) * COVB_LONG_ROW * (size_t)g.l0; }
 
-// 4. One group: the unit table; linearise every unit at its x*; every S, full symmetric
-int covb_assemble(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const CovbGroup& g, const DevPtrs& P, const CovUnit*& d_units) {
+// the call's result blocks in the pinned block, behind the tables
+double* covb_host_results(sadvio_ba_handle* h, const std::vector<CovbUnit>&) { return (double*)(h->cvb.pinned + h->cvb.tab_bytes); }
+
+// 4. One group: the unit table and the work table of its long tracks; linearise every unit at its x*; every S, full symmetric
+int covb_assemble(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const CovbGroup& g, const DevPtrs& P, const CovUnit*& d_units, CovbLong& L) {
     CovBatchScratch& B = h->cvb;
     const int nu = g.u1 - g.u0;
-    CovUnit* tab = (CovUnit*)B.pinned + g.u0;
+    CovUnit* tab = (CovUnit*)(B.pinned + covb_tab_offset(g));
     // the work pool: every S of the group first (one memset), then unit after unit; the result pool: block after block
     size_t s_tot = 0;
     for (int u = g.u0; u < g.u1; u++) s_tot += units[u].nn;
     double* pd = B.pool.p + s_tot; double* ps = B.pool.p;
     int* pi = B.ipool.p;
+    size_t i_tot = 0;   // (the is_long arrays of the units with long tracks lie behind every other int array: one memset)
+    for (int u = g.u0; u < g.u1; u++) i_tot += units[u].nl + units[u].no;
+    int* const pl0 = B.ipool.p + i_tot;
+    int* pl = pl0;
+    std::vector<int> lb((size_t)nu), le((size_t)nu);
     int mx_tab = 1, mx_tiles = 0, mx_schur = 0, mx_dense = 0;
     bool any_kept = false, any_np = false;
     for (int u = g.u0; u < g.u1; u++) {
@@ -157,6 +180,8 @@ int covb_assemble(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const
         C.hll = pd; pd += 6 * nl; C.hinv = pd; pd += 6 * nl;
         C.ent_w = pd; pd += COV_ENT_W * no; C.ent_hpp = pd; pd += COV_ENT_HPP * no;
         C.ent_n = pi; pi += nl; C.ent_col = pi; pi += no;
+        if (U.R.n_long > 0) { C.is_long = pl; pl += nl; }
+        lb[u - g.u0] = U.R.long_first; le[u - g.u0] = U.R.long_first + U.R.n_long;
         double* pr = B.rpool.p + (U.r_off - g.r0);
         T.sig = pr; C.Sig = pr; C.lout = pr + nn;
         C.status = (int*)(pr + nn + U.r_lout);
@@ -172,13 +197,25 @@ int covb_assemble(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const
             if (U.R.dense) mx_dense = std::max(mx_dense, (int)(((long long)d.dp_n * d.dp_n + 255) / 256));
         }
     }
-    d_units = (const CovUnit*)B.units.p + g.u0;
-    HIP_TRY(hipMemcpyAsync((void*)d_units, tab, sizeof(CovUnit) * nu, hipMemcpyHostToDevice, h->stream));
+    CovbLongPlan lp;
+    covb_long_plan(nu, lb.data(), le.data(), h->plan.long_rec.data(), LONG_REC, lp);
+    assert(lp.n_rows() == g.n_long);
+    if (lp.n_rows() > 0) memcpy(tab + nu, lp.rows.data(), sizeof(int) * lp.rows.size());
+    d_units = (const CovUnit*)(B.units.p + covb_tab_offset(g));
+    L = CovbLong{(const int*)(d_units + nu), lp.n_rows(), lp.max_kf};
+    HIP_TRY(hipMemcpyAsync((void*)d_units, tab, sizeof(CovUnit) * nu + sizeof(int) * lp.rows.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(B.pool.p, 0, sizeof(double) * s_tot, h->stream));
+    if (pl > pl0) HIP_TRY(hipMemsetAsync(pl0, 0, sizeof(int) * (size_t)(pl - pl0), h->stream));
     const bool pix = h->plan.factor_type == SADVIO_FACTOR_PIXEL;
     ScopedTimer t(h, "covb_assemble");
     hipLaunchKernelGGL(k_covb_tables, dim3(mx_tab, nu), dim3(256), 0, h->stream, P, d_units, B.ptab.p);
     if (mx_tiles > 0) hipLaunchKernelGGL(pix ? k_covb_assemble<0> : k_covb_assemble<1>, dim3(mx_tiles, nu), dim3(COV_THREADS), 0, h->stream, P, d_units);
+    if (L.n_rows > 0) {   // the long tracks into the tables the tile walk just filled, in front of k_covb_schur
+        LongArgs A = cov_long_args(h);
+        A.max_kf = L.max_kf;
+        ScopedTimer tl(h, "k_covb_long");
+        hipLaunchKernelGGL(pix ? k_covb_long<0> : k_covb_long<1>, dim3(L.n_rows), dim3(LONG_THREADS), cov_long_lds_bytes(L.max_kf), h->stream, P, d_units, L.d_rows, A);
+    }
     if (any_np) {
         if (mx_schur > 0) hipLaunchKernelGGL(k_covb_schur, dim3(mx_schur, nu), dim3(COV_SCHUR_THREADS), 0, h->stream, P, d_units);
         if (any_kept) hipLaunchKernelGGL(pix ? k_covb_kept<0> : k_covb_kept<1>, dim3(nu), dim3(64), 0, h->stream, P, d_units);
@@ -204,7 +241,7 @@ int covb_invert(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const C
 }
 
 // 6. Sigma_ll of every landmark of the units that were asked for landmark blocks; then the group's results on their way to the host
-int covb_landmarks(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const CovbGroup& g, const DevPtrs& P, const CovUnit* d_units) {
+int covb_landmarks(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, const CovbGroup& g, const DevPtrs& P, const CovUnit* d_units, const CovbLong& L) {
     CovBatchScratch& B = h->cvb;
     const int nu = g.u1 - g.u0;
     int blocks[2] = {0, 0};   // G = 16 | 64
@@ -220,6 +257,12 @@ int covb_landmarks(sadvio_ba_handle* h, const std::vector<CovbUnit>& units, cons
         ScopedTimer t(h, "k_covb_lmk");
         if (blocks[0]) hipLaunchKernelGGL(k_covb_lmk<16>, dim3(blocks[0], nu), dim3(COV_THREADS), 0, h->stream, P, d_units);
         if (blocks[1]) hipLaunchKernelGGL(k_covb_lmk<64>, dim3(blocks[1], nu), dim3(COV_THREADS), 0, h->stream, P, d_units);
+    }
+    if (L.n_rows > 0 && (blocks[0] || blocks[1])) {   // the long tracks' blocks, which k_covb_lmk skipped (CovDev::is_long)
+        LongArgs A = cov_long_args(h);
+        A.max_kf = L.max_kf;
+        ScopedTimer tl(h, "k_covb_lmk_long");
+        hipLaunchKernelGGL(k_covb_lmk_long, dim3(L.n_rows), dim3(LONG_THREADS), 0, h->stream, P, d_units, L.d_rows, A);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(covb_host_results(h, units) + g.r0, B.rpool.p, sizeof(double) * g.r_doubles, hipMemcpyDeviceToHost, h->stream));
@@ -263,9 +306,10 @@ int covb_run(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items) {
     const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
     for (const CovbGroup& g : groups) {
         const CovUnit* d_units = nullptr;
-        if (int rc = covb_assemble(h, units, g, P, d_units)) return rc;
+        CovbLong L;
+        if (int rc = covb_assemble(h, units, g, P, d_units, L)) return rc;
         if (int rc = covb_invert(h, units, g, d_units)) return rc;
-        if (int rc = covb_landmarks(h, units, g, P, d_units)) return rc;
+        if (int rc = covb_landmarks(h, units, g, P, d_units, L)) return rc;
     }
     if (int rc = covb_read_back(h, n_item, items, units, unit_of)) return rc;
     if (h->env.cov_sqrt != 0)

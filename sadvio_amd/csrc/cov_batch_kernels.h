@@ -8,6 +8,8 @@
 // (thread-strided partial sums, then the fixed tree) and the absence of floating-point atomics are those of the single call, and a
 // unit's bits depend neither on the other units of the launch nor on its place among them. k_covb_assemble and k_covb_lmk alone
 // are copies of k_cov_assemble's and k_cov_lmk's text behind the guard (cov_kernels.h says why): a change to one is made to the other.
+// A unit with long tracks (handles created with SADVIO_CFG_LONG_TRACK_COVARIANCE | SADVIO_CFG_LONG_TRACK_BATCH): k_covb_long and
+// k_covb_lmk_long, one workgroup per row of the group's work table (covb_long_plan.h), wrap cov_long_kernels.h's bodies the same way.
 //
 // k_cov_inv_lds is this file's own: Sigma_pp = S^-1 of one unit by ONE workgroup with the lower block triangle of S in LDS.
 //   cap:      N_p <= COVB_CAP = 176 (11 block rows of 16; the shipped VIO window is 11 x 15 = 165)
@@ -26,6 +28,7 @@
 // Part of the library's single translation unit; not a public header.
 #pragma once
 #include "cov_kernels.h"
+#include "cov_long_kernels.h"
 
 namespace sadvio {
 
@@ -111,6 +114,27 @@ __global__ __launch_bounds__(COV_THREADS) void k_covb_assemble(DevPtrs P, const 
         C.status[l] = status;
         C.ent_n[l] = n;
     }
+}
+
+// The long tracks of the group's units (handles created with SADVIO_CFG_LONG_TRACK_COVARIANCE | SADVIO_CFG_LONG_TRACK_BATCH): the tile
+// walk above never meets one. One workgroup of LONG_THREADS per row of the group's work table (covb_long_plan.h: unit inside the
+// group | index on the long list), behind k_covb_assemble and in front of k_covb_schur: cov_long_kernels.h's plain body with the
+// unit's CovDev, which fills the track's rows of the unit's tables and marks CovDev::is_long. A.max_kf is the table's (the LDS layout).
+template <int FACTOR>
+__global__ __launch_bounds__(LONG_THREADS) void k_covb_long(DevPtrs P, const CovUnit* units, const int* rows, LongArgs A) {
+    extern __shared__ __attribute__((aligned(16))) char covb_long_smem[];
+    const int* row = rows + 2 * (long long)blockIdx.x;
+    const CovDev C = units[row[0]].C;
+    cov_long_body<FACTOR, false>(P, C, CovSqrtDev{}, A, long_track(A, row[1]), covb_long_smem);
+}
+
+// ... and their landmark blocks, behind k_covb_lmk, which skips them: cov_long_kernels.h's body under k_covb_lmk's guard
+__global__ __launch_bounds__(LONG_THREADS) void k_covb_lmk_long(DevPtrs P, const CovUnit* units, const int* rows, LongArgs A) {
+    __shared__ double red[(LONG_THREADS / 64) * LONG_RED];
+    const int* row = rows + 2 * (long long)blockIdx.x;
+    const CovUnit U = units[row[0]];
+    if (U.G == 0 || *U.bad) return;
+    cov_lmk_long_body<false>(P, U.C, long_track(A, row[1]), red);
 }
 
 __global__ __launch_bounds__(COV_SCHUR_THREADS) void k_covb_schur(DevPtrs P, const CovUnit* units) {
@@ -336,7 +360,8 @@ __global__ __launch_bounds__(COV_THREADS) void k_covb_lmk(DevPtrs P, const CovUn
     const int q = threadIdx.x % G;
     const bool have = l < W.n_lmk;
     const int status = have ? C.status[l] : COV_LMK_CONST;
-    const int n = (have && status == COV_LMK_ELIMINATED) ? C.ent_n[l] : 0;
+    const bool lng = have && C.is_long && C.is_long[l];   // k_covb_lmk_long's
+    const int n = (have && status == COV_LMK_ELIMINATED && !lng) ? C.ent_n[l] : 0;
     const long long e0 = have ? P.lmk_ob[W.lmk_base + l] - W.obs_base : 0;
     double acc[9];
 #pragma unroll
@@ -372,7 +397,7 @@ __global__ __launch_bounds__(COV_THREADS) void k_covb_lmk(DevPtrs P, const CovUn
 #pragma unroll
     for (int i = 0; i < 9; i++)
         for (int m = G / 2; m > 0; m >>= 1) acc[i] += __shfl_xor(acc[i], m, G);
-    if (!have || q != 0) return;
+    if (!have || lng || q != 0) return;
     double* out = C.lout + 9 * (long long)l;
     if (status == COV_LMK_ELIMINATED) {
         const double* Hi = C.hinv + 6 * (long long)l;

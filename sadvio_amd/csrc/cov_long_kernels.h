@@ -20,6 +20,8 @@
 // a failed projection). Nothing per observation lives in registers beyond the one in hand: the plain form linearises a second time in
 // the owner pass, the square-root form keeps J_p and Q1 in CovSqrtDev::jp / q (global memory, each row written and rewritten by the
 // thread that owns its observation). Not tuned: a key-frame that holds very many of a track's observations serialises on its owner.
+// Both kernels are wrappers of a __device__ body (cov_long_body, cov_lmk_long_body) that takes the track; the unit kernels of
+// sadvio_ba_covariance_batch (cov_batch_kernels.h: k_covb_long, k_covb_lmk_long) call the plain forms of the same bodies.
 // Part of the library's single translation unit; not a public header.
 #pragma once
 #include "cov_kernels.h"
@@ -35,10 +37,10 @@ __host__ __device__ inline size_t cov_long_lds_bytes(int n_kf) {
 static_assert(sizeof(double) * (LONG_THREADS / 64) * LONG_RED + sizeof(int) * (2 * (size_t)MAX_LONG_KF + 2) <= 64 * 1024,
               "k_cov_long is launched without raising the dynamic LDS limit");
 
+// The body of k_cov_long for track T of the long list, by its workgroup of LONG_THREADS; smem: cov_long_lds_bytes(A.max_kf) of LDS.
+// k_covb_long (cov_batch_kernels.h) calls the plain form with its unit's CovDev: one body, so a track's bits are the single call's.
 template <int FACTOR, bool SQRT>
-__global__ __launch_bounds__(LONG_THREADS) void k_cov_long(DevPtrs P, CovDev C, CovSqrtDev Q1, LongArgs A, int first) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const LongTrack T = long_track(A, first + blockIdx.x);
+__device__ __forceinline__ void cov_long_body(const DevPtrs& P, const CovDev& C, const CovSqrtDev& Q1, const LongArgs& A, const LongTrack& T, char* smem) {
     const WinDev W = P.win[C.w];
     const int tid = threadIdx.x;
     double* red = (double*)smem;
@@ -178,10 +180,15 @@ __global__ __launch_bounds__(LONG_THREADS) void k_cov_long(DevPtrs P, CovDev C, 
     }
 }
 
+template <int FACTOR, bool SQRT>
+__global__ __launch_bounds__(LONG_THREADS) void k_cov_long(DevPtrs P, CovDev C, CovSqrtDev Q1, LongArgs A, int first) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    cov_long_body<FACTOR, SQRT>(P, C, Q1, A, long_track(A, first + blockIdx.x), smem);
+}
+
+// The body of k_cov_lmk_long for track T; red: the workgroup-sum exchange in LDS. k_covb_lmk_long calls the plain form.
 template <bool SQRT>
-__global__ __launch_bounds__(LONG_THREADS) void k_cov_lmk_long(DevPtrs P, CovDev C, LongArgs A, int first) {
-    __shared__ double red[(LONG_THREADS / 64) * LONG_RED];
-    const LongTrack T = long_track(A, first + blockIdx.x);
+__device__ __forceinline__ void cov_lmk_long_body(const DevPtrs& P, const CovDev& C, const LongTrack& T, double* red) {
     const WinDev W = P.win[C.w];
     const int l = T.gl - W.lmk_base;
     const int status = C.status[l];
@@ -228,6 +235,12 @@ __global__ __launch_bounds__(LONG_THREADS) void k_cov_lmk_long(DevPtrs P, CovDev
     }
     long_block_sum(acc, red);
     if (threadIdx.x == 0) cov_lmk_write<SQRT>(P, C, W, l, status, acc);
+}
+
+template <bool SQRT>
+__global__ __launch_bounds__(LONG_THREADS) void k_cov_lmk_long(DevPtrs P, CovDev C, LongArgs A, int first) {
+    __shared__ double red[(LONG_THREADS / 64) * LONG_RED];
+    cov_lmk_long_body<SQRT>(P, C, long_track(A, first + blockIdx.x), red);
 }
 
 }  // namespace sadvio

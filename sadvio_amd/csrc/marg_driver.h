@@ -812,10 +812,17 @@ int marginalize_relative(sadvio_ba_handle* h, int w, int kf_a, int kf_b, int eig
     for (int l = 0; l < d.n_lmk; l++) {
         const int gl = d.lmk_base + l;
         int ca = 0, cb = 0;
-        for (int o = h->plan.lmk_ob[gl]; o < h->plan.lmk_oe[gl]; o++) {
-            if (h->plan.obs_perm[o] < 0) continue;      // pseudo-observation of a sparse prior factor
-            ca += h->plan.obs_kf[o] == ga; cb += h->plan.obs_kf[o] == gb;
-        }
+        const int ob = h->plan.lmk_ob[gl], oe = h->plan.lmk_oe[gl];
+        auto count = [&](int lo, int hi) {
+            for (int o = lo; o < hi; o++) {
+                if (h->plan.obs_perm[o] < 0) continue;      // pseudo-observation of a sparse prior factor
+                ca += h->plan.obs_kf[o] == ga; cb += h->plan.obs_kf[o] == gb;
+            }
+        };
+        if (oe - ob > MAX_LMK_OBS) {   // a long track: the runs of the two key-frames alone (rel_runs.h)
+            const RelRuns rr = rel_runs(h->plan.obs_kf.data(), ob, oe, ga, gb);
+            count(rr.lo[0], rr.hi[0]); count(rr.lo[1], rr.hi[1]);
+        } else count(ob, oe);
         if (ca > 0 && cb > 0) { items.push_back(gl); items.push_back(cb); m += 3 * cb; }
     }
     const int n_items = (int)items.size() / 2;

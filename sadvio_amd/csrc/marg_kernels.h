@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "rel_runs.h"
 
 namespace sadvio {
 
@@ -1466,7 +1467,16 @@ __global__ __launch_bounds__(64) void k_relmarg_lmk(DevPtrs P, const int* items 
     for (int i = 0; i < 9; i++) Hll[i] = 0.0;
     for (int i = 0; i < 36; i++) { E[i] = 0.0; Hp[0][i] = 0.0; Hp[1][i] = 0.0; }
     const double d6[6] = {0, 0, 0, 0, 0, 0};
-    for (int o = P.lmk_ob[gl]; o < P.lmk_oe[gl]; o++) {
+    // (a long track: the two runs of rel_runs.h, the observations this walk stops at in its order; every other landmark: one segment)
+    const int ob = P.lmk_ob[gl], oe = P.lmk_oe[gl];
+    int o = ob, hi0 = oe, lo1 = oe, hi1 = oe;
+    if (oe - ob > MAX_LMK_OBS) {
+        const RelRuns rr = rel_runs(P.obs_kf, ob, oe, ga, gb);
+        o = rr.lo[0]; hi0 = rr.hi[0]; lo1 = rr.lo[1]; hi1 = rr.hi[1];
+    }
+#pragma unroll 1
+    for (int seg = 0; seg < 2; seg++, o = lo1, hi0 = hi1)
+    for (; o < hi0; o++) {
         const int kf = P.obs_kf[o], cam = P.obs_cam[o];
         if (cam < 0 || (kf != ga && kf != gb)) continue;
         const int side = kf == ga ? 0 : 1;
