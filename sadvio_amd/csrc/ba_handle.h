@@ -1,5 +1,6 @@
 // ba_handle.h — the handle behind the C ABI (sadvio_ba_handle) and its helper structs: device buffers, the staged upload batch,
-// the host copies of the caller's windows, the environment switches and the kernel-class timers.
+// the host copies of the caller's windows, the environment switches, the long-track switches, the state guard of the entry points
+// (entry_state) and the kernel-class timers.
 // Part of the library's single translation unit (ba_capi.hip); not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -264,12 +265,7 @@ struct EnvCfg {
     int cov_band = -1;   // covariance, the band route (cov_band_kernels.h): -1 not set: only where the call was refused before (N_p >= 2047) | 1: every bandable window | 0: never
     int cov_sqrt = -1;   // covariance, the square-root assembly (cov_kernels.h): -1 not set: only after the pivot tests refused the plain form | 1: from the start | 0: never
     int cov_cross_stage = -1;   // covariance_cross: doubles of a block row k_cov_cross stages in LDS (tests: both sides of the limit); -1 not set: COVX_STAGE_MAX
-    int long_min = 0;   // 0: the handle was created without SADVIO_CFG_LONG_TRACKS (no long path); else 65, or SADVIO_LONG_MIN in [2, 65] (tests, A/B timing): a landmark
-                        // with at least this many observations takes the long path (long_kernels.h). Set by sadvio_ba_create, behind read()
-    int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range)
-    bool long_priors = false;   // SADVIO_CFG_LONG_TRACK_PRIORS: marginalize, sparsify and the prior setters serve long tracks. Set by sadvio_ba_create
-    bool long_cov = false;      // SADVIO_CFG_LONG_TRACK_COVARIANCE: covariance and covariance_cross serve a window with long tracks. Set by sadvio_ba_create
-    bool long_batch = false;    // SADVIO_CFG_LONG_TRACK_BATCH: marginalize_relative(_batch) serve a window with long tracks, and with long_cov covariance_batch. Set by sadvio_ba_create
+    int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range): LongCfg::from_create applies it
     double jacobi_tol = 1e-14;
     bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
     void read() {
@@ -292,8 +288,34 @@ struct EnvCfg {
     }
 };
 
+// What sadvio_ba_create's long-track flags (sadvio_ba_config::reserved) ask of the handle.
+struct LongCfg {
+    int min = 0;   // 0: created without SADVIO_CFG_LONG_TRACKS (no long path: a 65th observation is refused as it always was); else 65, or SADVIO_LONG_MIN in
+                   // [2, 65] (tests, A/B timing): a landmark with at least this many observations takes the long path (long_kernels.h)
+    bool priors = false;   // SADVIO_CFG_LONG_TRACK_PRIORS: marginalize, sparsify and the prior setters serve long tracks
+    bool cov = false;      // SADVIO_CFG_LONG_TRACK_COVARIANCE: covariance and covariance_cross serve a window with long tracks (independent of `priors`)
+    bool batch = false;    // SADVIO_CFG_LONG_TRACK_BATCH: marginalize_relative(_batch) serve a window with long tracks, and with `cov` covariance_batch
+    // Fills the struct; false with the refusal in `err`: a flag that needs SADVIO_CFG_LONG_TRACKS and came without it
+    bool from_create(unsigned reserved, int long_min_env, std::string& err) {
+        static const struct { unsigned flag; const char* name; const char* reason; } needs[] = {
+            {SADVIO_CFG_LONG_TRACK_PRIORS, "SADVIO_CFG_LONG_TRACK_PRIORS", "to carry a prior on"},
+            {SADVIO_CFG_LONG_TRACK_COVARIANCE, "SADVIO_CFG_LONG_TRACK_COVARIANCE", "to form a covariance of"},
+            {SADVIO_CFG_LONG_TRACK_BATCH, "SADVIO_CFG_LONG_TRACK_BATCH", "for a batch call to serve"}};
+        for (const auto& n : needs)
+            if ((reserved & n.flag) && !(reserved & SADVIO_CFG_LONG_TRACKS)) {
+                err = std::string("create: ") + n.name + " needs SADVIO_CFG_LONG_TRACKS (a handle without the long path has no long track " + n.reason + ")";
+                return false;
+            }
+        min = (reserved & SADVIO_CFG_LONG_TRACKS) ? (long_min_env ? long_min_env : MAX_LMK_OBS + 1) : 0;
+        priors = (reserved & SADVIO_CFG_LONG_TRACK_PRIORS) != 0; cov = (reserved & SADVIO_CFG_LONG_TRACK_COVARIANCE) != 0;
+        batch = (reserved & SADVIO_CFG_LONG_TRACK_BATCH) != 0;
+        return true;
+    }
+};
+
 struct sadvio_ba_handle {
     EnvCfg env;
+    LongCfg lt;
     sadvio_ba_config cfg{};
     LayoutPlan plan;   // the current layout as host tables (layout_plan.h); layout_driver.h puts it on the device
     int device = 0;
@@ -407,6 +429,15 @@ int kclass_id(sadvio_ba_handle* h, const char* name) {
     return (int)h->kclasses.size() - 1;
 }
 
+// The state an entry point needs of its handle, checked in this order; `what` opens the refusal's text
+enum { NEED_UPLOADED = 1, NOT_DEFERRED = 2, NEED_SOLVED = 4 };
+int entry_state(sadvio_ba_handle* h, const char* what, int need) {
+    if ((need & NEED_UPLOADED) && !h->uploaded) { h->err = std::string(what) + " before set_windows"; return SADVIO_E_STATE; }
+    if ((need & NOT_DEFERRED) && h->defer) { h->err = std::string(what) + " between begin_update and commit_update"; return SADVIO_E_STATE; }
+    if ((need & NEED_SOLVED) && !h->solved) { h->err = std::string(what) + " before solve"; return SADVIO_E_STATE; }
+    return SADVIO_OK;
+}
+
 // Long tracks (long_kernels.h) are served by the window solve and the per-landmark probes; the entry points that walk a landmark's
 // observations in lane groups of their own refuse a window that has one (DESIGN.md "Long tracks": follow-ups).
 bool window_has_long(const sadvio_ba_handle* h, int w) {
@@ -419,11 +450,11 @@ int refuse_long(sadvio_ba_handle* h, int w, const char* what) {
 }
 // landmark l of window w as the NEXT layout will see it (the caller's copy: valid between begin_update and commit_update too)
 bool lmk_is_long(const sadvio_ba_handle* h, int w, int l) {
-    return w >= 0 && w < (int)h->src.size() && src_lmk_is_long(h->src[w], l, h->env.long_min, h->world, h->coll_fn != nullptr);
+    return w >= 0 && w < (int)h->src.size() && src_lmk_is_long(h->src[w], l, h->lt.min, h->world, h->coll_fn != nullptr);
 }
 // ... and is it one that this handle's back-end calls (marginalize, sparsify, the prior setters) refuse: every long track, unless the
 // handle was created with SADVIO_CFG_LONG_TRACK_PRIORS
-bool lmk_is_refused_long(const sadvio_ba_handle* h, int w, int l) { return !h->env.long_priors && lmk_is_long(h, w, l); }
+bool lmk_is_refused_long(const sadvio_ba_handle* h, int w, int l) { return !h->lt.priors && lmk_is_long(h, w, l); }
 
 struct ScopedTimer {
     sadvio_ba_handle* h;

@@ -53,8 +53,7 @@ struct CovbLong { const int* d_rows = nullptr; int n_rows = 0, max_kf = 0; };
 // above). Host work only; nothing is written on an error.
 int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* items) {
     if (h->world > 1) return cov_invalid(h, "covariance_batch", ": the window is sharded over several GPUs (each rank holds a landmark partition only)");
-    if (h->defer) { h->err = "covariance_batch between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (!h->solved) { h->err = "covariance_batch before solve"; return SADVIO_E_STATE; }
+    if (int rc = entry_state(h, "covariance_batch", NOT_DEFERRED | NEED_SOLVED)) return rc;
     if (n_item < 0) return cov_invalid(h, "covariance_batch", ": negative item count");
     if (n_item > 0 && !items) return cov_invalid(h, "covariance_batch", ": null items");
     for (int it = 0; it < n_item; it++)

@@ -5,7 +5,7 @@
 // (it adds none on the dense route), and so takes the single call's choice of assembly (SADVIO_COV_SQRT) and its retry.
 // Dense route: k_cov_cross / k_cov_innov read block rows of Sigma_pp. Band route: k_cov_band_rows first solves the whole block row of
 // every distinct key-frame asked for, and every candidate is served from those rows; no kernel reads Sigma outside its band.
-// Part of the library's single translation unit (ba_capi.hip, which includes it below cov_driver.h); not a public header.
+// Part of the library's single translation unit (ba_capi.hip); not a public header.
 #pragma once
 #include "cov_cross_kernels.h"
 #include "cov_cross_plan.h"

@@ -15,7 +15,7 @@
 // prior_build_Z: the route sadvio_ba_sparsify takes to Sigma_k = Ak^-1), called as they are. Nothing of the solve is touched: the
 // delta buffers, the final records, the trace and the handle's prior are read only; the work buffers are the handle's CovScratch
 // and, inside the two borrowed routines, MargScratch.
-// Part of the library's single translation unit (ba_capi.hip, which includes it below marg_driver.h); not a public header.
+// Part of the library's single translation unit (ba_capi.hip); not a public header.
 #pragma once
 #include <cassert>
 #include <climits>
@@ -91,8 +91,7 @@ int cov_check_request(sadvio_ba_handle* h, const char* call, int w, const sadvio
 // 1. State and arguments. Host work only.
 int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq) {
     if (h->world > 1) return cov_invalid(h, "covariance", ": the window is sharded over several GPUs (each rank holds a landmark partition only)");
-    if (h->defer) { h->err = "covariance between begin_update and commit_update"; return SADVIO_E_STATE; }
-    if (!h->solved) { h->err = "covariance before solve"; return SADVIO_E_STATE; }
+    if (int rc = entry_state(h, "covariance", NOT_DEFERRED | NEED_SOLVED)) return rc;
     return cov_check_request(h, "covariance", w, rq, false);
 }
 

@@ -32,7 +32,7 @@ LayoutIn layout_inputs(sadvio_ba_handle* h) {
     in.world = h->world; in.has_coll = h->coll_fn != nullptr;
     in.tile_rounds = h->env.tile_rounds; in.lm = h->env.lm; in.lm_subs = h->env.lm_subs;
     in.contig_tiles = h->env.contig_tiles; in.no_lpt = h->env.no_lpt; in.no_pre = h->env.no_pre;
-    in.long_min = h->env.long_min; in.long_priors = h->env.long_priors;
+    in.long_min = h->lt.min; in.long_priors = h->lt.priors;
     return in;
 }
 

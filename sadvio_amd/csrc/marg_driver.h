@@ -1,10 +1,11 @@
 // marg_driver.h — the host side of marginalisation: the dense factorisations it is built from (pivoted / unpivoted Cholesky, the
 // Jacobi eigen-solvers, the triangular inverse), sadvio_ba_marginalize as named steps
 //   marg_layout -> marg_routes -> marg_assemble -> marg_invert_mm -> marg_schur -> marg_factor_cholesky | marg_factor_eigen -> marg_install
-// and the bodies of sadvio_ba_marginalize_relative and sadvio_ba_sparsify. The kernels are marg_kernels.h's and dense_chol.h's.
-// Part of the library's single translation unit (ba_capi.hip, which includes it below make_imu_dev); not a public header.
+// and the bodies of sadvio_ba_marginalize_relative, sadvio_ba_sparsify, sadvio_ba_get_prior and sadvio_ba_set_prior. The kernels are marg_kernels.h's and dense_chol.h's.
+// Part of the library's single translation unit (ba_capi.hip); not a public header.
 #pragma once
 #include "ba_handle.h"
+#include "imu_host.h"
 #include "solve_driver.h"
 
 namespace {
@@ -1041,6 +1042,36 @@ int sparsify(sadvio_ba_handle* h, int w, int vio, int nf, int n, const double* J
         }
     }
     *n_out = cnt;
+    return SADVIO_OK;
+}
+
+// sadvio_ba_get_prior: the handle's prior as it stands (J, r0: null = not asked for)
+int read_prior(sadvio_ba_handle* h, sadvio_prior_info* info, double* J, double* r0) {
+    const PriorState& PR = h->prior;
+    if (info) { info->valid = PR.valid ? 1 : 0; info->n_full = PR.valid ? PR.n_full : 0; info->n = PR.valid ? PR.n : 0; info->form = PR.form; }
+    if (!PR.valid) { if (J || r0) { h->err = "get_prior: the handle holds no prior"; return SADVIO_E_STATE; } return SADVIO_OK; }
+    HIP_TRY(hipSetDevice(h->device));
+    if (J) HIP_TRY(hipMemcpyAsync(J, PR.J.p, sizeof(double) * (size_t)PR.n_full * PR.n, hipMemcpyDeviceToHost, h->stream));
+    if (r0) HIP_TRY(hipMemcpyAsync(r0, PR.r0.p, sizeof(double) * PR.n_full, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return SADVIO_OK;
+}
+
+// sadvio_ba_set_prior: the caller's prior in place of the handle's (n_full <= 0: none)
+int write_prior(sadvio_ba_handle* h, int32_t n_full, int32_t n, int32_t form, const double* J, const double* r0) {
+    PriorState& PR = h->prior;
+    PR.serial++;
+    PR.hg_valid = false;
+    if (n_full <= 0) { PR.valid = false; PR.z_valid = false; return SADVIO_OK; }
+    if (n <= 0 || !J || !r0 || form != SADVIO_PRIOR_FORM_EIGEN) {   // a Cholesky-form prior carries its pivot order: only the device produces one
+        h->err = "set_prior: needs J, r0 in the eigen form (orthogonal rows)"; return SADVIO_E_INVALID_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(PR.J.alloc((size_t)n_full * n)); HIP_TRY(PR.r0.alloc(n_full));
+    HIP_TRY(hipMemcpyAsync(PR.J.p, J, sizeof(double) * (size_t)n_full * n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(PR.r0.p, r0, sizeof(double) * n_full, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    PR.valid = true; PR.z_valid = false; PR.n_full = n_full; PR.n = n; PR.form = form; PR.cut_mode = SADVIO_EIG_CUT_REFERENCE;
     return SADVIO_OK;
 }
 

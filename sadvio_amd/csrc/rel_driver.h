@@ -14,8 +14,7 @@ namespace {
 
 // 1. State and arguments, in the order and wording of sadvio_ba_marginalize_relative. Host work only; nothing is written on an error.
 int rel_check(sadvio_ba_handle* h, int w, int n_pair, const int32_t* kf_a, const int32_t* kf_b, int eig_cut_mode, const double* inf36, const int32_t* status) {
-    if (!h->uploaded) { h->err = "marginalize_relative_batch before set_windows"; return SADVIO_E_STATE; }
-    if (h->defer) { h->err = "marginalize_relative_batch between begin_update and commit_update"; return SADVIO_E_STATE; }
+    if (int rc = entry_state(h, "marginalize_relative_batch", NEED_UPLOADED | NOT_DEFERRED)) return rc;
     if (w < 0 || w >= (int)h->plan.wins.size()) { h->err = "marginalize_relative_batch: window out of range"; return SADVIO_E_INVALID_ARG; }
     if (eig_cut_mode != SADVIO_EIG_CUT_REFERENCE && eig_cut_mode != SADVIO_EIG_CUT_NOISE_FLOOR) { h->err = "marginalize_relative_batch: bad eig_cut_mode"; return SADVIO_E_INVALID_ARG; }
     if (h->world > 1) { h->err = "marginalize_relative_batch: the window is sharded over several GPUs (each rank holds a landmark partition only)"; return SADVIO_E_INVALID_ARG; }

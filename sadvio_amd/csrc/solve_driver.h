@@ -3,12 +3,15 @@
 //                  workspace pointers), allocates what it needs and may synchronise the stream; nothing is launched from it
 //   enqueue_solve  launches, reading only the plan: it may run under stream capture, so it neither allocates nor synchronises
 // The bytes of the plan are the key of the captured graph: what enqueue_solve reads and what decides a re-capture are one thing.
+// Beside them the other steps of sadvio_ba_solve (convert_options, launch_solve with the graph capture, solve_summaries) and the
+// read-backs of a solved batch (read_deltas, read_line_deltas, read_trace).
 // Part of the library's single translation unit (ba_capi.hip); not a public header.
 #pragma once
 #include <cstddef>
 #include <type_traits>
 
 #include "ba_handle.h"
+#include "solve_opts.h"
 
 namespace {
 
@@ -611,6 +614,130 @@ void print_debug_stamps(sadvio_ba_handle* h, int n_tiles) {
         fprintf(stderr, "[sadvio dbg] k_build tile sums: %lld uniform waves in %zu workgroups; most head lanes in a wave %lld (mean of the workgroups' fullest waves %.1f), workgroups with a wave above 32 heads %lld\n",
                 uni, wg.size() / 4, hmax, (double)hsum / (double)(wg.size() / 4), over32);
 #endif
+}
+
+// sadvio_ba_solve, step 1. The caller's options as the kernels take them; null: the defaults
+int convert_options(sadvio_ba_handle* h, const sadvio_solve_options* opts, SolveOpts& o) {
+    sadvio_solve_options defo;
+    if (!opts) { sadvio_ba_default_options(&defo); opts = &defo; }
+    if (opts->max_num_iterations < 0 || opts->max_num_iterations > 1000) { h->err = "solve: max_num_iterations out of range"; return SADVIO_E_INVALID_ARG; }
+    memset(&o, 0, sizeof(o));   // it travels in DevPtrs, whose bytes are part of the graph key
+    solve_opts_from(*opts, o);
+    o.huber_a = opts->huber_a;
+    // wall_clock64: 100 MHz. Not applied to a window sharded over several GPUs: the ranks' clocks would disagree on the slot
+    o.max_time_ticks = (opts->max_solver_time_in_seconds > 0.0 && h->world == 1) ? opts->max_solver_time_in_seconds * 1e8 : 0.0;
+    if (!(o.huber_a >= 0.0)) { h->err = "solve: huber_a must be >= 0"; return SADVIO_E_INVALID_ARG; }
+    return SADVIO_OK;
+}
+
+// sadvio_ba_solve, step 3. Launch, as one graph where the handle asks for it
+int launch_solve(sadvio_ba_handle* h, const SolvePlan& plan, const std::vector<BigPlan>& big) {
+    bool coll_ok = true;
+    if (h->cfg.use_graph && !h->cfg.profile_kernels && !h->coll_fn) {
+        // the whole <= 20-iteration solve is one graph launch, re-captured whenever the plan differs from the captured one in any byte
+        const unsigned char* pb = (const unsigned char*)&plan;
+        const unsigned char* bb = (const unsigned char*)big.data();
+        std::vector<unsigned char> key(pb, pb + sizeof(plan));
+        key.insert(key.end(), bb, bb + big.size() * sizeof(BigPlan));
+        if (!h->graph_exec || key != h->graph_key) {
+            if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+            hipGraph_t g = nullptr;
+            HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+            enqueue_solve(h, plan, big);
+            HIP_TRY(hipStreamEndCapture(h->stream, &g));
+            HIP_TRY(hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(g);
+            h->graph_key.swap(key);
+        }
+        HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
+    } else {
+        coll_ok = enqueue_solve(h, plan, big);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!coll_ok) { h->err = "solve: the all-reduce of the reduced system failed"; return SADVIO_E_RCCL; }
+    return SADVIO_OK;
+}
+
+// sadvio_ba_solve, step 6. The final records as the handle's solved state and the caller's summaries (null: none asked for)
+int solve_summaries(sadvio_ba_handle* h, const SolveOpts& o, const SolvePlan& plan, sadvio_solve_summary* summaries) {
+    const int n_win = plan.P.n_win;
+    h->fin.assign(h->h_final, h->h_final + n_win);
+    h->deltas_cached = false;
+    h->last_slots = plan.slots;
+    h->cov_huber_a = o.huber_a; h->cov_use_lm = plan.use_lm;
+    h->solved = true;
+    int rc = SADVIO_OK;
+    for (int w = 0; w < n_win; w++) {
+        const LmState& s = h->fin[w].s;
+        if (summaries) {
+            sadvio_solve_summary& S = summaries[w];
+            S.iterations = s.iter; S.num_successful_steps = s.n_success; S.num_unsuccessful_steps = s.n_unsuccess;
+            S.termination = s.termination; S.initial_cost = s.initial_cost; S.final_cost = s.x_cost;
+            S.fixed_cost = 0.5 * h->fin[w].fixed_cost; S.final_radius = s.radius;
+        }
+        if (s.termination == SADVIO_TERM_FAILURE) rc = SADVIO_E_NOT_USABLE;
+    }
+    return rc;
+}
+
+// sadvio_ba_get_deltas: window w's share of the solved deltas (any output may be null)
+int read_deltas(sadvio_ba_handle* h, int32_t w, double* pose, double* lmk, double* dv, double* dba, double* dbg) {
+    HIP_TRY(hipSetDevice(h->device));
+    const WinDev& d = h->plan.wins[w].d;
+    const int cur = h->fin[w].s.cur;
+    // One read-back per solve: both buffers of every delta array go to a pinned host buffer with asynchronous copies and ONE
+    // synchronisation (a pageable hipMemcpy per array and window costs 30 - 80 us each); every get_deltas of this solve is then
+    // a host memcpy. Layout: xp [2][6 n_kf] | xl [2][3 n_lmk] | xv | xba | xbg [2][3 n_kf] each.
+    const size_t nk = (size_t)h->plan.n_kf_tot, nl = (size_t)h->plan.n_lmk_tot;
+    const size_t o_xp = 0, o_xl = o_xp + 12 * nk, o_xv = o_xl + 6 * nl, o_xba = o_xv + 6 * nk, o_xbg = o_xba + 6 * nk, total = o_xbg + 6 * nk;
+    if (!h->deltas_cached) {
+        if (h->h_deltas_cap < total) {
+            if (h->h_deltas) (void)hipHostFree(h->h_deltas);
+            h->h_deltas = nullptr; h->h_deltas_cap = 0;
+            HIP_TRY(hipHostMalloc((void**)&h->h_deltas, sizeof(double) * (total + total / 2), hipHostMallocDefault));
+            h->h_deltas_cap = total + total / 2;
+        }
+        bool any_imu = false;
+        for (const auto& hw : h->plan.wins) any_imu |= hw.d.has_imu != 0;
+        HIP_TRY(hipMemcpyAsync(h->h_deltas + o_xp, h->d_xp.p, sizeof(double) * 12 * nk, hipMemcpyDeviceToHost, h->stream));
+        if (nl) HIP_TRY(hipMemcpyAsync(h->h_deltas + o_xl, h->d_xl.p, sizeof(double) * 6 * nl, hipMemcpyDeviceToHost, h->stream));
+        if (any_imu) {
+            HIP_TRY(hipMemcpyAsync(h->h_deltas + o_xv, h->d_xv.p, sizeof(double) * 6 * nk, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->h_deltas + o_xba, h->d_xba.p, sizeof(double) * 6 * nk, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->h_deltas + o_xbg, h->d_xbg.p, sizeof(double) * 6 * nk, hipMemcpyDeviceToHost, h->stream));
+        } else {
+            memset(h->h_deltas + o_xv, 0, sizeof(double) * 18 * nk);   // windows without IMU states: their deltas are never touched (zero)
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->deltas_cached = true;
+    }
+    if (pose) memcpy(pose, h->h_deltas + o_xp + (size_t)cur * 6 * nk + 6 * (size_t)d.kf_base, sizeof(double) * 6 * d.n_kf);
+    if (lmk && d.n_lmk) memcpy(lmk, h->h_deltas + o_xl + (size_t)cur * 3 * nl + 3 * (size_t)d.lmk_base, sizeof(double) * 3 * d.n_lmk);
+    double* outs[3] = {dv, dba, dbg};
+    const size_t offs[3] = {o_xv, o_xba, o_xbg};
+    for (int q = 0; q < 3; q++)
+        if (outs[q]) memcpy(outs[q], h->h_deltas + offs[q] + (size_t)cur * 3 * nk + 3 * (size_t)d.kf_base, sizeof(double) * 3 * d.n_kf);
+    return SADVIO_OK;
+}
+
+// sadvio_ba_get_line_deltas
+int read_line_deltas(sadvio_ba_handle* h, int32_t w, double* line_delta6) {
+    HIP_TRY(hipSetDevice(h->device));
+    const WinDev& d = h->plan.wins[w].d;
+    const int n = d.line_end - d.line_begin;
+    if (n > 0) HIP_TRY(hipMemcpy(line_delta6, h->d_xline.p + (size_t)h->fin[w].s.cur * 6 * h->n_line_tot + 6 * (size_t)d.line_begin, sizeof(double) * 6 * n, hipMemcpyDeviceToHost));
+    return SADVIO_OK;
+}
+
+// sadvio_ba_get_trace
+int read_trace(sadvio_ba_handle* h, int32_t w, int32_t cap_rows, double* rows8, int32_t* n_rows) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int stride = h->last_slots + 2;
+    const int n = std::min(h->fin[w].s.iter + 1, stride);
+    if (n_rows) *n_rows = n;
+    const int m = std::min(n, cap_rows);
+    if (m > 0) HIP_TRY(hipMemcpy(rows8, h->d_trace.p + (size_t)w * stride * 8, sizeof(double) * 8 * (size_t)m, hipMemcpyDeviceToHost));
+    return SADVIO_OK;
 }
 
 }  // namespace
