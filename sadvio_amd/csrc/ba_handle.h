@@ -377,7 +377,7 @@ struct sadvio_ba_handle {
     DevBuf<unsigned char> d_lmk_const;
     DevBuf<int> d_lmk_ob, d_lmk_oe, d_obs_kf, d_obs_cam, d_tile_kf, d_tile_row, d_tile_lmk;
     DevBuf<int> d_long_rec, d_long_kf, d_long_slot;   // tables of the long tracks (long_kernels.h, LayoutPlan::long_rec)
-    DevBuf<int> d_pre_lane, d_pre_kf;     // first-round packets of the latency kernels (kernels.h: DevPtrs::pre_lane), few-tile submissions only
+    DevBuf<int> d_pre_lane, d_pre_kf;     // first-round packets of the latency kernels (step_args.h: DevPtrs::pre_lane), few-tile submissions only
     bool pre_dirty = false;
     DevBuf<int> d_rank_col; DevBuf<double> d_rank_x;       // refine_rank_by_eigenvalue (guarded calls only): pivot column per step, the solved vectors
     DevBuf<unsigned char> d_obs_slot, d_obs_lslot;

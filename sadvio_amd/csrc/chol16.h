@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "ba_types.h"
+#include "wave_ops.h"
 
 // SADVIO_C16_PARENT_ORDER (compile time; tests/cpp/chol16_order_check.hip and A/B measurements): the back-substitution with the H
 // column of a step requested in front of that step's barrier, as it was before the column was requested one step ahead — the same
@@ -56,44 +57,6 @@ __host__ __device__ constexpr int c16_tile(int I, int J) { return ((I * (I + 1))
 // element (i, j), i >= j, of the tile-packed lower triangle (diagonal tiles: the lower half; see c16_symmetrize)
 __host__ __device__ constexpr int c16_index(int i, int j) { return (c16_tile(i >> 4, j >> 4) << 8) + ((j & 15) << 4) + (i & 15); }
 // c16_blocks, c16_size: ba_types.h (the host's layout sizes the image with them)
-
-__device__ __forceinline__ double c16_readlane(double v, int lane) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, lane);
-    hi = __builtin_amdgcn_readlane(hi, lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double c16_rsqrt(double d) {   // v_rsq_f64 (2^-24) + ONE third-order (Halley) step: e = 1 - d y^2,
-    double y = __builtin_amdgcn_rsq(d);                    // y <- y (1 + e / 2 + 3 e^2 / 8): error O(e^3) ~ 1e-22 before rounding;
-    const double t = d * y;                                // five dependent operations instead of the six of two Newton steps
-    const double e = __builtin_fma(-t, y, 1.0);
-    const double p = __builtin_fma(0.375, e, 0.5);
-    const double q = e * p;
-    return __builtin_fma(y, q, y);
-}
-// (even-row member, odd-row member) of the lane pair {l, l ^ 16} in both lanes; likewise (lower, upper) of {l, l ^ 32}
-__device__ __forceinline__ void c16_pair16(double v, double& e, double& o) {
-    const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    e = __hiloint2double(b[0], a[0]); o = __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ void c16_pair32(double v, double& l, double& u) {
-    const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    l = __hiloint2double(b[0], a[0]); u = __hiloint2double(b[1], a[1]);
-}
-
-// value of the lane (i - 1) % 16 of the same 16-lane row: DPP row_ror:1 (a lane receives from the lane 1 below, cyclically),
-// i.e. after d applications lane i holds the value lane (i - d) % 16 started with. The back-substitution wants (i + d) % 16:
-// it applies row_ror:15 = one step the other way.
-__device__ __forceinline__ double c16_row_ror1(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x12F, 0xF, 0xF, true);   // row_ror:15
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x12F, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
 
 __device__ __forceinline__ c16_d4 c16_load(const double* t, int ln) {
     c16_d4 v;
@@ -177,11 +140,11 @@ template <int S, int GATHER>
 __device__ __forceinline__ void c16_gather(double u, double* gbuf, int ln, double (&a)[10]) {
     if (GATHER == 0) {
         // D[4S + r][4S + c] (r >= c) = D[4S + c][4S + r] sits in lane 16 r + 4 S + c
-        a[0] = c16_readlane(u, 4 * S);
-        a[1] = c16_readlane(u, 16 + 4 * S); a[2] = c16_readlane(u, 16 + 4 * S + 1);
-        a[3] = c16_readlane(u, 32 + 4 * S); a[4] = c16_readlane(u, 32 + 4 * S + 1); a[5] = c16_readlane(u, 32 + 4 * S + 2);
-        a[6] = c16_readlane(u, 48 + 4 * S); a[7] = c16_readlane(u, 48 + 4 * S + 1); a[8] = c16_readlane(u, 48 + 4 * S + 2);
-        a[9] = c16_readlane(u, 48 + 4 * S + 3);
+        a[0] = readlane_f64(u, 4 * S);
+        a[1] = readlane_f64(u, 16 + 4 * S); a[2] = readlane_f64(u, 16 + 4 * S + 1);
+        a[3] = readlane_f64(u, 32 + 4 * S); a[4] = readlane_f64(u, 32 + 4 * S + 1); a[5] = readlane_f64(u, 32 + 4 * S + 2);
+        a[6] = readlane_f64(u, 48 + 4 * S); a[7] = readlane_f64(u, 48 + 4 * S + 1); a[8] = readlane_f64(u, 48 + 4 * S + 2);
+        a[9] = readlane_f64(u, 48 + 4 * S + 3);
     } else {
         gbuf[ln] = u;      // wave-private 64 doubles; same-wave LDS accesses complete in order
         const double2 r1 = *(const double2*)(gbuf + 16 + 4 * S), r2 = *(const double2*)(gbuf + 32 + 4 * S);
@@ -200,9 +163,9 @@ __device__ __forceinline__ void c16_pivot_step(c16_d4& D, c16_d4& E, c16_d4& W, 
     c16_d4 zw = {0.0, 0.0, 0.0, 0.0};
     if (GATHER == 0) {
         double ev, od;
-        c16_pair16(u, ev, od);
-        c16_pair32(ev, a0, a2);
-        c16_pair32(od, a1, a3);
+        swap16_pair_f64(u, ev, od);
+        swap32_pair_f64(ev, a0, a2);
+        swap32_pair_f64(od, a1, a3);
         c16_stamp(lc, 8 * S + 1, a3);
         c16_gather<S, 0>(u, gbuf, ln, a);
     } else {
@@ -217,13 +180,13 @@ __device__ __forceinline__ void c16_pivot_step(c16_d4& D, c16_d4& E, c16_d4& W, 
         c16_stamp(lc, 8 * S + 1, a3);
     }
     c16_stamp(lc, 8 * S + 2, a[9]);
-    const double i0 = nreal > 0 ? c16_rsqrt(a[0]) : 0.0;
+    const double i0 = nreal > 0 ? rsqrt_nr(a[0]) : 0.0;
     const double l10 = a[1] * i0, l20 = a[3] * i0, l30 = a[6] * i0;
-    const double i1 = nreal > 1 ? c16_rsqrt(__builtin_fma(-l10, l10, a[2])) : 0.0;
+    const double i1 = nreal > 1 ? rsqrt_nr(__builtin_fma(-l10, l10, a[2])) : 0.0;
     const double l21 = __builtin_fma(-l20, l10, a[4]) * i1, l31 = __builtin_fma(-l30, l10, a[7]) * i1;
-    const double i2 = nreal > 2 ? c16_rsqrt(__builtin_fma(-l21, l21, __builtin_fma(-l20, l20, a[5]))) : 0.0;
+    const double i2 = nreal > 2 ? rsqrt_nr(__builtin_fma(-l21, l21, __builtin_fma(-l20, l20, a[5]))) : 0.0;
     const double l32 = __builtin_fma(-l31, l21, __builtin_fma(-l30, l20, a[8])) * i2;
-    double i3 = nreal > 3 ? c16_rsqrt(__builtin_fma(-l32, l32, __builtin_fma(-l31, l31, __builtin_fma(-l30, l30, a[9])))) : 0.0;
+    double i3 = nreal > 3 ? rsqrt_nr(__builtin_fma(-l32, l32, __builtin_fma(-l31, l31, __builtin_fma(-l30, l30, a[9])))) : 0.0;
     c16_stamp(lc, 8 * S + 3, i3);
     if (GATHER == 1 && S > 0) {   // the matrix pipe finished zw during the factor chain
         W[S - 1] = zw[0];

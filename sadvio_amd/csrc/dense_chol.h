@@ -16,7 +16,6 @@
 // the co-visibility structure; = N for a dense system): the work per step is O(bw^2), not O(N^2), for the
 // block-banded systems of long trajectories (configs 4 / 5).
 #pragma once
-#include "chol16.h"
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -27,13 +26,6 @@ constexpr int CH_NB = 32;
 constexpr int CH_TS = 64;
 constexpr int CH_THREADS = 256;
 
-__device__ __forceinline__ double ch_readlane(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // In-register Cholesky of an nb x nb (nb <= 32) block held one ROW per lane (lane r: a[c] = D[r][c], c <= r).
 // Returns false in all lanes if a pivot is not positive. On return a[] holds row r of L.
 __device__ __forceinline__ bool ch_factor_rows(double (&a)[CH_NB], int nb, int ln) {
@@ -41,14 +33,14 @@ __device__ __forceinline__ bool ch_factor_rows(double (&a)[CH_NB], int nb, int l
 #pragma unroll
     for (int c = 0; c < CH_NB; c++) {
         if (c < nb) {
-            const double d = ch_readlane(a[c], c);  // pivot (row c, column c), wave-uniform
+            const double d = readlane_f64(a[c], c);  // pivot (row c, column c), wave-uniform
             if (!(d > 0.0)) ok = false;
-            const double inv = rsqrt_nr(d);  // v_rsq_f64 + 2 Newton steps (kernels.h): ~4x shorter chain than sqrt + divide
+            const double inv = rsqrt_nr(d);  // v_rsq_f64 + one third-order step (wave_ops.h): ~4x shorter chain than sqrt + divide
             a[c] = (ln == c) ? d * inv : a[c] * inv;  // column c of L (rows >= c)
 #pragma unroll
             for (int j = c + 1; j < CH_NB; j++) {
                 if (j < nb) {
-                    const double ljc = ch_readlane(a[c], j);  // L[j][c], wave-uniform
+                    const double ljc = readlane_f64(a[c], j);  // L[j][c], wave-uniform
                     a[j] -= a[c] * ljc;                       // rows r >= j matter; others hold garbage never read
                 }
             }
@@ -237,8 +229,8 @@ __global__ __launch_bounds__(CH_THREADS) void k_chol_backsolve(const double* __r
 #pragma unroll
             for (int j = CH_NB - 1; j >= 0; j--) {
                 if (j < nb) {
-                    const double tj = ch_readlane(t, j);
-                    const double ljj = ch_readlane(l[j], j);
+                    const double tj = readlane_f64(t, j);
+                    const double ljj = readlane_f64(l[j], j);
                     const double xj = tj / ljj;
                     if (ln == j) t = xj;
                     else if (ln < j) t -= l[j] * xj;  // L[k0 + j][k0 + ln]

@@ -16,119 +16,11 @@
 #include "ba_types.h"
 #include "device_math.h"
 #include "chol16.h"
+#include "step_args.h"
+#include "wave_ops.h"
+#include "tile_common.h"
 
 namespace sadvio {
-
-struct DevPtrs {
-    const WinDev* win;
-    const Tile* tiles;
-    const double* kf_T0;
-    const int* kf_fidx;
-    double* xp; double* xv; double* xba; double* xbg;  // [2][...]
-    long long xp_stride, xv_stride, xl_stride;
-    const double* kf_vel; const double* kf_ba; const double* kf_bg;
-    const double* cam_K; const double* cam_T; const double* cam_isig;
-    const double* lmk_p; double* xl; double* s_lmk;
-    const unsigned char* lmk_const;
-    const int* lmk_ob; const int* lmk_oe;
-    const int* obs_kf; const int* obs_cam; const double* obs_meas;
-    const unsigned char* obs_slot;  // index of the observation's key-frame in its tile's list
-    const int* tile_kf;             // per-tile key-frame lists (global indices)
-    const int* tile_lmk;            // landmark lists of the packed tiles (Tile::lmk_off)
-    const int* tile_row;            // matching row in the tile's LDS system (6 * rank among free) or -1
-    // first-round packets (k_pre_packets; null for submissions of more than PRE_MAX_TILES tiles): per (tile, 8 consecutive lanes — a landmark's
-    // lane group is 8 .. 64 wide) | landmark | its first observation | its observation count + (1 << 16 if the landmark exists) | position of the
-    // 8 lanes' first one inside the group |,
-    // per (tile, k < PRE_KF) | global key-frame or -1 | its free index |: the opening loads of k_build / k_backsub hang on blockIdx alone
-    const int4* pre_lane;
-    const int2* pre_kf;
-    double* ptab;                   // [2][n_kf_tot][POSE_TAB] pose tables of the two delta buffers
-    long long ptab_stride;
-    const PriorDev* priors;
-    double* prior_lin;              // [2][n_prior_tot][PRIOR_LIN] g = J^T r (6) | H = J^T J lower (21) | |r|^2 of every pose prior at the x of
-    long long prior_lin_stride;     // each delta buffer: written at x = 0 by k_init_tables, at the candidate by k_solve's back half
-    int n_prior_tot;
-    const ImuDev* imus;
-    double* imu_scratch;  // [2][n_imu_tot][IMU_ROW], see ba_types.h: the linearisation of every IMU factor pair at the deltas of buffer 0 | 1
-    long long imu_scratch_stride;
-    double* S; double* gred; double* gfull; double* hdiag; double* delta; double* s_pose;
-    LmState* states;  // [n_win][slots+2]
-    IterAcc* acc;     // [n_win][slots+1] window totals (written by single workgroups only)
-    TileAcc* tacc;    // [2][n_tiles] per-tile partials, double-buffered by slot parity (no atomics)
-    FinalRec* final_out;  // [n_win]
-    int* big_info;        // [n_win] potrf info of the windows solved out of LDS
-    // a window sharded over `world` GPUs (landmark partition): per-rank partial sums, exchanged with the reduced
-    // system by one all-reduce per phase; rank r writes slot r and zeroes the others (sum == gather)
-    int imu_direct;       // 1: imu_pair_lin_wg adds the IMU pairs' entries to the reduced system itself (one device); 0: k_solve's item loop
-    int decide_kernel;    // 1: the LM decision of a slot is taken by k_decide (many tiles); 0: by every k_build workgroup
-    int world, rank;
-    double* rank_b;       // [n_win][world][4] lin_cost, fixed_cost, gmax, -      (after k_build)
-    double* rank_s;       // [n_win][world][4] cand_cost, mcc, step_norm2, cand_norm2 (after k_backsub)
-    const int* lmk_red;   // [n_lmk_tot] offset of a prior-kept landmark in its window's reduced vector, else -1 (may be null)
-    const int* kept_obs;  // [n_kept][3] (device observation index, global landmark, window)
-    int n_kept;
-    double* dp_data;      // dense priors, see WinDev::dp_off
-    const SparseDev* sparse;  // sparse prior factors
-    const int* sp_list;       // indices (into sparse) of the factors the solve evaluates itself, per window slice
-    double* sp_scratch;       // [2][n_sparse][SPARSE_J] r, J of the listed factors at the deltas of buffer 0 | 1 (as imu_scratch)
-    long long sp_scratch_stride;
-    int n_imu_tot, n_sp_list;  // extra workgroups of k_build / k_backsub: IMU factor pairs, then the listed sparse-prior factors
-    const int* dp_ints;
-    const int* chunk_ob;      // [n_chunks + 1] first observation of each chunk (lm_kernels.h)
-    const int* chunk_lm;      // [n_chunks + 1] first landmark of each chunk
-    const int* tile_perm;     // [n_tiles] launch order of the throughput kernels: tiles by decreasing chunk count
-    const unsigned char* obs_lslot;  // [n_obs_tot] index of the observation's landmark inside its chunk
-    double* lm_hg;            // [2][n_lmk_tot][9] H_ll | g_l of every landmark at the point of each delta buffer (k_lm_pass)
-    double* lm_dt;            // [2][n_tiles][LM_DT] per tile: key-frame sums (sum Jp^T Jp, sum Jp^T r) + cost totals at each buffer's point
-    long long lm_hg_stride, lm_dt_stride;
-    const int* lm_sub;        // [n_sub][2] work list of k_lm_pass: tile | sub-block (LM_PASS_THREADS landmarks) of the tile, largest tiles first
-    int lm_sub_per_item;      // sub-blocks one work item (workgroup) of k_lm_pass runs through
-    int lm_ksub;              // record slots per tile (= the largest tile's sub-block count): lm_dt / lm_sacc are indexed tile * lm_ksub + sub-block
-    double* lm_sacc;          // [2][n_tiles * lm_ksub][4] per sub-block and slot parity: cand_cost | mcc | step_norm2 | cand_norm2 (unused slots stay zero)
-    const LineDev* lines;     // linexd landmarks: few, kept in the reduced system
-    const LineObsDev* lobs;
-    double* xline;            // [2][n_line_tot][6] line deltas, double-buffered like xp
-    double* line_scratch;     // [n_lobs_tot][LINE_ROW]
-    long long xline_stride;
-    long long n_xp, n_xv, n_xl;  // doubles in the (double-buffered) delta arrays, zeroed by k_reset
-    int n_tiles;
-    int state_stride;
-    int n_win;
-    long long* t_start; // wall_clock64 at the first kernel of the solve (k_reset)
-    double* trace;      // [n_win][state_stride][8] per-iteration log (sadvio_ba_get_trace), written by the slot's single decider
-    long long* dbg_ts;  // [DBG_SLOTS] phase timestamps (wall_clock64, 100 MHz) of workgroup 0 when debug & 4096
-    int debug;  // SADVIO_DEBUG env: bit 12 (4096) = in-kernel phase timestamps of workgroup 0 into dbg_ts (results unaffected)
-    int c16_old_tail;   // 1 (SADVIO_C16_OLD_TAIL, A/B): chol16.h's last block column with both of its barriers
-    SolveOpts o;
-};
-
-// In-kernel phase timestamps (SADVIO_DEBUG & 4096) exist only in a build with -DSADVIO_KERNEL_TS: even as not-taken
-// branches they cost the latency-bound kernels ~1-2 us per launch (measured A/B on k_solve).
-#ifdef SADVIO_KERNEL_TS
-#define SADVIO_TS(slot_, idx_) do { if ((P.debug & 4096) && blockIdx.x == 0 && threadIdx.x == 0 && slot == (slot_)) P.dbg_ts[idx_] = wall_clock64(); } while (0)
-#define SADVIO_TS_PTR(cond_) ((cond_) ? P.dbg_ts : nullptr)
-// Per-workgroup record of one k_build launch (slot 3): | start | end | XCC id << 32 | HW_ID (gfx9 layout: SIMD 5:4, CU 11:8, SH 12,
-// SE 15:13) | waves whose 8 landmarks list the same key-frames in the same lanes (`uniform`) << 32, most head lanes in a wave | behind the 128 phase slots. Shows which workgroups share a CU and when each of them ends (scripts/gpu_time_tiles.py).
-constexpr int DBG_WG_MAX = 1024, DBG_WG_BASE = 128, DBG_SLOTS = DBG_WG_BASE + 4 * DBG_WG_MAX;
-#define SADVIO_WG_TS(slot_, which_) do { if ((P.debug & 4096) && blockIdx.x < DBG_WG_MAX && threadIdx.x == 0 && slot == (slot_)) { \
-        P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + (which_)] = wall_clock64(); \
-        if ((which_) == 0) P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + 3] = 0; \
-        if ((which_) == 0) P.dbg_ts[DBG_WG_BASE + 4 * blockIdx.x + 2] = ((long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)); } } while (0)
-#else
-#define SADVIO_TS(slot_, idx_) do { } while (0)
-#define SADVIO_TS_PTR(cond_) nullptr
-#define SADVIO_WG_TS(slot_, which_) do { } while (0)
-constexpr int DBG_SLOTS = 128;
-#endif
-
-__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // i >= j
-// element (i >= j) of a window's reduced matrix in HBM: packed lower triangle (ld == 0) or full row-major
-// ld == 0: the 16 x 16 tile-packed lower triangle of chol16.h (= the LDS image of k_solve<0>, so that its gather is a linear copy)
-__device__ __forceinline__ long long s_index(int ld, int i, int j) { return ld ? (long long)i * ld + j : (long long)c16_index(i, j); }
-
-__device__ __forceinline__ void atomic_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
-
-__device__ __forceinline__ void atomic_max_u64(unsigned long long* p, unsigned long long v) { atomicMax(p, v); }
 
 // Ceres 2.2 TrustRegionMinimizer iteration bookkeeping, restated (see oracle/solver.c for the
 // line-by-line CPU restatement this must agree with).
@@ -191,52 +83,6 @@ __device__ __forceinline__ void trace_write(const DevPtrs& P, int w, int slot, c
     N[4] = judged ? cc / a.mcc : 0.0; N[5] = next.n_success > prev.n_success ? 1.0 : 0.0; N[6] = -1.0; N[7] = a.mcc;
 }
 
-// Wave-wide sum / max with DPP + the gfx950 v_permlane{16,32}_swap (plain VALU): every lane receives the result. The
-// __shfl_down forms go through ds_bpermute, ~100 cycles per step on the LDS pipe: six steps per value were ~1 us of every
-// kernel tail that reduces a handful of partials.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64_(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// v_permlane16_swap / v_permlane32_swap of a register with itself return (own value, value of lane ^ 16 / ^ 32) in an order
-// that depends on the half: symmetric combinations (sum, max) need not know which is which
-__device__ __forceinline__ void swap16_pair_f64(double v, double& x0, double& x1) {
-    unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    x0 = __hiloint2double(b[0], a[0]); x1 = __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ void swap32_pair_f64(double v, double& x0, double& x1) {
-    unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    x0 = __hiloint2double(b[0], a[0]); x1 = __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    v += dpp_f64_<0xB1>(v);   // xor 1
-    v += dpp_f64_<0x4E>(v);   // xor 2
-    v += dpp_f64_<0x141>(v);  // row_half_mirror
-    v += dpp_f64_<0x140>(v);  // row_mirror
-    double x0, x1;
-    swap16_pair_f64(v, x0, x1); v = x0 + x1;
-    swap32_pair_f64(v, x0, x1); v = x0 + x1;
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    v = fmax(v, dpp_f64_<0xB1>(v));
-    v = fmax(v, dpp_f64_<0x4E>(v));
-    v = fmax(v, dpp_f64_<0x141>(v));
-    v = fmax(v, dpp_f64_<0x140>(v));
-    double x0, x1;
-    swap16_pair_f64(v, x0, x1); v = fmax(x0, x1);
-    swap32_pair_f64(v, x0, x1); v = fmax(x0, x1);
-    return v;
-}
-
-
 // Sum the k_backsub partials of a window's tiles (slot parity `par`): executed by one wave. Every kernel that re-derives
 // the LM decision of a slot must get the SAME BITS, so the order is canonical for windows of at most 4 * BUILD_THREADS tiles
 // (the only ones whose decision is taken by more than one kernel): tile t belongs to virtual thread t % 256, which adds its
@@ -276,232 +122,6 @@ __device__ __forceinline__ void wave_sum_backsub_partials(const DevPtrs& P, int 
     }
     if (ln == 0) { out4[0] = c; out4[1] = m; out4[2] = sn; out4[3] = cn; }
 }
-
-// ---- landmark-group machinery shared by k_build and k_backsub ------------------------------------
-// ---- cross-lane primitives without the LDS pipe -------------------------------------------------------
-// ds_bpermute / ds_swizzle shuffles and ds_add_f64 cost ~100-170 cycles per wave-instruction here (measured),
-// DPP modifiers and the gfx950 v_permlane{16,32}_swap are plain VALU. dpp_ctrl: quad_perm 0x00-0xFF,
-// row_shl:n 0x100+n, row_shr:n 0x110+n, row_ror:n 0x120+n, row_mirror 0x140, row_half_mirror 0x141.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-// v[lane] + v[lane ^ 16] / v[lane ^ 32] in every lane
-__device__ __forceinline__ double xor16_sum(double v) {
-    unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ double xor32_sum(double v) {
-    unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ int xor16_other(int v) {  // the value held by lane ^ 16 (SADVIO_KERNEL_TS builds: the tile-sum counters of k_build)
-    auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)((threadIdx.x & 16) ? a[0] : a[1]);
-}
-__device__ __forceinline__ int xor32_other(int v) {
-    auto a = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)((threadIdx.x & 32) ? a[0] : a[1]);
-}
-
-// Sum over the G lanes of a landmark group (G = power of two, 8 <= G <= 64, groups aligned to G lanes);
-// every lane of the group receives the total.
-__device__ __forceinline__ double group_sum(double v, int G) {
-    v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]  (xor 1)
-    v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]  (xor 2)
-    v += dpp_f64<0x141>(v);  // row_half_mirror: the other quad of the 8-lane group
-    if (G >= 16) v += dpp_f64<0x140>(v);  // row_mirror: the other half of the 16-lane row
-    if (G >= 32) v = xor16_sum(v);
-    if (G >= 64) v = xor32_sum(v);
-    return v;
-}
-// ceres::HuberLoss(a) + Corrector (rho'' <= 0 branch): returns rho(|r|^2) and the scale sqrt(rho') for r and J.
-__device__ __forceinline__ double huber_rho(double a, double s, double& scale) {
-    scale = 1.0;
-    if (a > 0.0 && s > a * a) {
-        const double rr = sqrt(s);
-        scale = sqrt(fmax(2.2250738585072014e-308, a / rr));
-        return 2.0 * a * rr - a * a;
-    }
-    return s;
-}
-
-struct ObsLin {
-    double r[2], Jp[12], Jl[6];
-    double rho;   // loss-corrected cost of the block (= |r|^2 without a loss function)
-    int row;      // row of the observing key-frame in the tile's LDS system, -1 if constant
-    int slot;     // index into the tile's key-frame list
-    bool valid;   // this lane owns an observation
-    bool counted; // the residual block belongs to the reduced program (some parameter block is free)
-};
-
-// Lane-local linearisation of observation `o` of landmark `gl` from LDS tables.
-// RARE = false compiles the robust loss out (plain window BA: huber_a = 0, no prior-kept landmarks).
-// The constants of one observation, loaded ahead of use (k_build fetches its first landmark round while the LM decision of
-// the previous slot is still being summed).
-struct ObsPre {
-    int slot, craw;
-    double m[3];
-};
-template <int FACTOR>
-__device__ __forceinline__ ObsPre obs_prefetch(const DevPtrs& P, int o) {
-    ObsPre q;
-    q.slot = P.obs_slot[o];
-    q.craw = P.obs_cam[o];
-    if (FACTOR == 0) { const double* m = P.obs_meas + 2 * (long long)o; q.m[0] = m[0]; q.m[1] = m[1]; q.m[2] = 0.0; }
-    else { const double* m = P.obs_meas + 3 * (long long)o; q.m[0] = m[0]; q.m[1] = m[1]; q.m[2] = m[2]; }
-    return q;
-}
-
-template <int FACTOR, bool RARE>
-__device__ __forceinline__ void lane_linearize(const DevPtrs& P, const double* poseTab, const double* camTab,
-                                               const int* rowTab, int cam_base, const ObsPre& ob, const double* pw, bool keep_jl,
-                                               bool lcounted, ObsLin& L) {
-    const int slot = ob.slot;
-    const int craw = ob.craw;
-    const int cam = craw < 0 ? 0 : craw - cam_base;
-    const double* tab = poseTab + slot * POSE_TAB;
-    const double* ct = camTab + cam * 17;  // K[4] Tsf[12] isig
-    L.slot = slot;
-    L.row = rowTab[slot];
-    if (RARE && craw < 0) {
-        // pseudo-observation: one half of a PoseToLandmarkFactor of the sparsified prior (no loss function on it)
-        const int code = -1 - craw;
-        const SparseDev& f = P.sparse[code >> 1];
-        p2l_pseudo_obs<true>(tab, pw, f.delta, f.W, code & 1, L.r, L.Jp, L.Jl);
-        L.rho = L.r[0] * L.r[0] + L.r[1] * L.r[1];
-        if (L.row < 0) {
-#pragma unroll
-            for (int i = 0; i < 12; i++) L.Jp[i] = 0.0;
-        }
-        if (!keep_jl) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) L.Jl[i] = 0.0;
-        }
-        L.counted = (L.row >= 0) || lcounted;
-        return;
-    }
-    if (FACTOR == 0) {
-        pixel_factor<true>(tab, ct, ct + 4, pw, ob.m[0], ob.m[1], ct[16], L.r, L.Jp, L.Jl);
-    } else {
-        double b[3] = {ob.m[0], ob.m[1], ob.m[2]};
-        angular_factor<true>(tab, ct + 4, pw, b, ct[16], L.r, L.Jp, L.Jl);
-    }
-    L.rho = L.r[0] * L.r[0] + L.r[1] * L.r[1];
-    if (RARE) {
-        double sc;
-        L.rho = huber_rho(P.o.huber_a, L.rho, sc);
-        if (sc != 1.0) {
-            L.r[0] *= sc; L.r[1] *= sc;
-#pragma unroll
-            for (int i = 0; i < 12; i++) L.Jp[i] *= sc;
-#pragma unroll
-            for (int i = 0; i < 6; i++) L.Jl[i] *= sc;
-        }
-    }
-    if (L.row < 0) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) L.Jp[i] = 0.0;
-    }
-    if (!keep_jl) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) L.Jl[i] = 0.0;
-    }
-    L.counted = (L.row >= 0) || lcounted;
-    if (!L.counted) { /* fixed cost: caller accounts r, then it leaves the program */ }
-}
-
-// Per-landmark elimination, every lane of the group redundantly: H_ll, g_l (group sums), LM damping, the inverse Cholesky
-// factor Li of the damped block (sym3_chol_inverse: packed lower 6-vector; named Mi below). Returns whether the landmark has a
-// parameter block in the program. s_pre: the landmark's three Jacobi scales (DevPtrs::s_lmk) where the caller fetched them with
-// the round's other inputs (k_build), or null: they are loaded here, behind the group sums. Unused with write_scale.
-__device__ __forceinline__ bool group_eliminate(const DevPtrs& P, const ObsLin& L, int G, int gl, bool lmk_valid,
-                                                bool lfree, int nobs, double radius, bool write_scale, bool leader,
-                                                double* Mi, double* g, const double* s_pre) {
-    double H[6];
-    H[0] = L.Jl[0] * L.Jl[0] + L.Jl[3] * L.Jl[3];
-    H[1] = L.Jl[0] * L.Jl[1] + L.Jl[3] * L.Jl[4];
-    H[2] = L.Jl[0] * L.Jl[2] + L.Jl[3] * L.Jl[5];
-    H[3] = L.Jl[1] * L.Jl[1] + L.Jl[4] * L.Jl[4];
-    H[4] = L.Jl[1] * L.Jl[2] + L.Jl[4] * L.Jl[5];
-    H[5] = L.Jl[2] * L.Jl[2] + L.Jl[5] * L.Jl[5];
-    g[0] = L.Jl[0] * L.r[0] + L.Jl[3] * L.r[1];
-    g[1] = L.Jl[1] * L.r[0] + L.Jl[4] * L.r[1];
-    g[2] = L.Jl[2] * L.r[0] + L.Jl[5] * L.r[1];
-#pragma unroll
-    for (int i = 0; i < 6; i++) H[i] = group_sum(H[i], G);
-#pragma unroll
-    for (int i = 0; i < 3; i++) g[i] = group_sum(g[i], G);
-    const bool active = lmk_valid && lfree && nobs > 0;
-    if (!active) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) Mi[i] = 0.0;
-        return false;
-    }
-    double s[3];
-    if (write_scale) {
-        s[0] = P.o.jacobi_scaling ? 1.0 / (1.0 + sqrt(H[0])) : 1.0;
-        s[1] = P.o.jacobi_scaling ? 1.0 / (1.0 + sqrt(H[3])) : 1.0;
-        s[2] = P.o.jacobi_scaling ? 1.0 / (1.0 + sqrt(H[5])) : 1.0;
-        if (leader) {
-            P.s_lmk[3 * (long long)gl] = s[0]; P.s_lmk[3 * (long long)gl + 1] = s[1]; P.s_lmk[3 * (long long)gl + 2] = s[2];
-        }
-    } else if (s_pre) {
-        s[0] = s_pre[0]; s[1] = s_pre[1]; s[2] = s_pre[2];
-    } else {
-        s[0] = P.s_lmk[3 * (long long)gl]; s[1] = P.s_lmk[3 * (long long)gl + 1]; s[2] = P.s_lmk[3 * (long long)gl + 2];
-    }
-    const double ir = 1.0 / radius;
-    const double s0 = s[0] * s[0], s1 = s[1] * s[1], s2 = s[2] * s[2];
-    double M[6] = {H[0], H[1], H[2], H[3], H[4], H[5]};
-    M[0] += fmin(fmax(s0 * H[0], P.o.min_lm_diagonal), P.o.max_lm_diagonal) * ir / s0;
-    M[3] += fmin(fmax(s1 * H[3], P.o.min_lm_diagonal), P.o.max_lm_diagonal) * ir / s1;
-    M[5] += fmin(fmax(s2 * H[5], P.o.min_lm_diagonal), P.o.max_lm_diagonal) * ir / s2;
-    sym3_chol_inverse(M, Mi);
-    return true;
-}
-
-// Stage the tile's key-frame pose tables (buffer `buf`) and the window's cameras into LDS.
-__device__ __forceinline__ void stage_tables(const DevPtrs& P, const Tile& T, int buf, double* poseTab, double* camTab,
-                                             int* rowTab) {
-    const int tid = threadIdx.x;
-    const double* src = P.ptab + (long long)buf * P.ptab_stride;
-    for (int i = tid; i < T.n_kf * POSE_TAB; i += blockDim.x) {
-        const int k = i / POSE_TAB, e = i - k * POSE_TAB;
-        poseTab[i] = src[(long long)P.tile_kf[T.kf_off + k] * POSE_TAB + e];
-    }
-    for (int i = tid; i < T.n_cam * 17; i += blockDim.x) {
-        const int c = i / 17, e = i - 17 * c;
-        const int gc = T.cam_base + c;
-        camTab[i] = e < 4 ? P.cam_K[4 * (long long)gc + e] : (e < 16 ? P.cam_T[12 * (long long)gc + e - 4] : P.cam_isig[gc]);
-    }
-    for (int i = tid; i < T.n_kf; i += blockDim.x) rowTab[i] = P.tile_row[T.kf_off + i];
-}
-
-__device__ __forceinline__ void wave_lds_fence() {
-    // LDS traffic between lanes of ONE wave: order this wave's stores before its later loads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__host__ __device__ inline size_t tile_tables_bytes(int n_kf) {
-    // pose tables + camera tables + row table; a global-atomics tile may list up to 64 key-frames (> MAX_TILE_KF)
-    size_t b = sizeof(double) * ((size_t)n_kf * POSE_TAB + MAX_WIN_CAM * 17) + sizeof(int) * (size_t)(n_kf > MAX_TILE_KF ? n_kf : MAX_TILE_KF);
-    return (b + 15) & ~(size_t)15;
-}
-
-// global landmark in slot i of a tile: listed (packed tiles) or consecutive
-__device__ __forceinline__ int tile_landmark(const Tile& T, const int* __restrict__ tile_lmk, int i) { return T.lmk_off >= 0 ? tile_lmk[T.lmk_off + i] : T.lmk0 + i; }
 
 // First-round packets (DevPtrs::pre_lane / pre_kf): one launch per layout, behind its upload. What a lane of k_build / k_backsub needs
 // to address the inputs of its tile's FIRST landmark round, laid out by (tile, 8-lane granule) so that those loads hang on blockIdx alone
@@ -638,12 +258,8 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         const long long src = (long long)P.tile_kf[T.kf_off + k] * POSE_TAB + e;
         pre_t0 = P.ptab[src]; pre_t1 = P.ptab[P.ptab_stride + src];
     }
-    for (int i = tid; i < T.n_cam * 17; i += blockDim.x) {
-        const int c = i / 17, e = i - 17 * c;
-        const int gc = T.cam_base + c;
-        camTab[i] = e < 4 ? P.cam_K[4 * (long long)gc + e] : (e < 16 ? P.cam_T[12 * (long long)gc + e - 4] : P.cam_isig[gc]);
-    }
-    for (int i = tid; i < T.n_kf; i += blockDim.x) rowTab[i] = P.tile_row[T.kf_off + i];
+    stage_cams(P, T.cam_base, T.n_cam, camTab);
+    for (int i = tid; i < T.n_kf; i += blockDim.x) rowTab[i] = P.tile_row[T.kf_off + i];   // (stage_rows' text: the call makes the RARE variants 4 bytes shorter)
     ObsPre pre_obs;
     pre_obs.slot = 0; pre_obs.craw = 0; pre_obs.m[0] = pre_obs.m[1] = pre_obs.m[2] = 0.0;
     if (pre_o >= 0) pre_obs = obs_prefetch<FACTOR>(P, pre_o);
@@ -1016,23 +632,6 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
 //     update reads with unit stride; 4x2 register micro-tiles;
 //   * two workgroup barriers per block column, one per back-substitution step.
 // On return xs = S^-1 rhs. Returns false if a pivot is not positive.
-__device__ __forceinline__ double rsqrt_nr(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    // one third-order step (see c16_rsqrt, chol16.h): e = 1 - d y^2, y <- y (1 + e / 2 + 3 e^2 / 8); five dependent operations
-    const double t = d * y;
-    const double e = __builtin_fma(-t, y, 1.0);
-    const double p = __builtin_fma(0.375, e, 0.5);
-    const double q = e * p;
-    return __builtin_fma(y, q, y);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, lane);
-    hi = __builtin_amdgcn_readlane(hi, lane);
-    return __hiloint2double(hi, lo);
-}
-
 constexpr int NBP = 6;  // rows of the transposed panel strip (max NB)
 
 template <int NB>
@@ -1421,20 +1020,13 @@ __device__ __forceinline__ double prior_lin_record(const double* T0, const doubl
 // acos, Jr^-1) as CALLS: inlined into the 512-thread kernel they lengthened live ranges across the factorisation and cost it 42
 // spilled VGPRs; a handful of lanes run them, off the critical path of the other waves.
 // (arguments in registers: six scalars + pointers; a by-value struct of 18 doubles travels through scratch)
-__device__ __noinline__ void pose_table_store(const double* T0, double d0, double d1, double d2, double d3, double d4, double d5, double* dst) {
-    double T0r[12], tab[POSE_TAB];
-#pragma unroll
-    for (int i = 0; i < 12; i++) T0r[i] = T0[i];
-    const double d6[6] = {d0, d1, d2, d3, d4, d5};
-    pose_table_entry(T0r, d6, tab);
-#pragma unroll
-    for (int i = 0; i < POSE_TAB; i++) dst[i] = tab[i];
-}
-// The same between two places in LDS (k_solve<0>'s parked key-frames): ds_read / ds_write, no flat access. The call ABI waits for
-// every outstanding memory operation of the wave at entry and at return; with nothing but LDS traffic in flight around the call
-// neither wait meets a round trip to HBM. The caller's workgroup copies the tables to DevPtrs::ptab afterwards.
+// One template over the pointer type, two instantiations: `double` (generic pointers: T0 from LDS or HBM, the table into DevPtrs::ptab)
+// and `lds_double`, between two places in LDS (k_solve<0>'s parked key-frames): ds_read / ds_write, no flat access. The call ABI
+// waits for every outstanding memory operation of the wave at entry and at return; with nothing but LDS traffic in flight around
+// the call neither wait meets a round trip to HBM. The caller's workgroup copies the tables to DevPtrs::ptab afterwards.
 typedef __attribute__((address_space(3))) double lds_double;
-__device__ __noinline__ void pose_table_lds(const lds_double* T0, double d0, double d1, double d2, double d3, double d4, double d5, lds_double* dst) {
+template <typename D>
+__device__ __noinline__ void pose_table_store(const D* T0, double d0, double d1, double d2, double d3, double d4, double d5, D* dst) {
     double T0r[12], tab[POSE_TAB];
 #pragma unroll
     for (int i = 0; i < 12; i++) T0r[i] = T0[i];
@@ -1988,7 +1580,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(DevPtrs P, int slot) {
             if (fi >= 0) cn = fma(d6[i], d6[i], cn);    // (spelled out: a sum of bare products may be contracted from either end)
         }
         // pose table of the candidate buffer (k_backsub reads it now, k_build reads it if the step is accepted)
-        if (tab_lds) pose_table_lds(kc + 7, d6[0], d6[1], d6[2], d6[3], d6[4], d6[5], (lds_double*)A + k * POSE_TAB);
+        if (tab_lds) pose_table_store(kc + 7, d6[0], d6[1], d6[2], d6[3], d6[4], d6[5], (lds_double*)A + k * POSE_TAB);
         else pose_table_store(kfc + k * SOLVE_KFC_STRIDE + 7, d6[0], d6[1], d6[2], d6[3], d6[4], d6[5], P.ptab + (long long)(1 - cur) * P.ptab_stride + (long long)g * POSE_TAB);
 #pragma unroll
         for (int i = 0; i < 6; i++) xpc[6 * (long long)g + i] = d6[i];
@@ -2275,12 +1867,8 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, 
             poseTab[i] = src[o];
             if (e < 12) candTab[k * 12 + e] = srcc[o];
         }
-        for (int i = tid; i < T.n_cam * 17; i += blockDim.x) {
-            const int c = i / 17, e = i - 17 * c;
-            const int gc = T.cam_base + c;
-            camTab[i] = e < 4 ? P.cam_K[4 * (long long)gc + e] : (e < 16 ? P.cam_T[12 * (long long)gc + e - 4] : P.cam_isig[gc]);
-        }
-        for (int i = tid; i < T.n_kf; i += blockDim.x) rowTab[i] = P.tile_row[T.kf_off + i];
+        stage_cams(P, T.cam_base, T.n_cam, camTab);
+        stage_rows(P, T, rowTab);
         const double* dp = P.delta + T.red_off;
         for (int i = tid; i < T.n_kf * 6; i += blockDim.x) {
             const int k = i / 6, e = i - 6 * k;

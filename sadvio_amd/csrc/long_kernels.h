@@ -45,14 +45,6 @@ __device__ __forceinline__ LongTrack long_track(const LongArgs& A, int i) {
     return LongTrack{r[0], r[1], r[2], r[3], r[4], r[5]};
 }
 
-__device__ __forceinline__ void long_stage_cams(const DevPtrs& P, const WinDev& W, double* camTab) {
-    for (int i = threadIdx.x; i < W.n_cam * 17; i += blockDim.x) {
-        const int c = i / 17, e = i - 17 * c;
-        const int gc = W.cam_base + c;
-        camTab[i] = e < 4 ? P.cam_K[4 * (long long)gc + e] : (e < 16 ? P.cam_T[12 * (long long)gc + e - 4] : P.cam_isig[gc]);
-    }
-}
-
 // Sum of n <= LONG_RED values per thread over the workgroup; every thread receives the totals (waves added in index order)
 template <int N>
 __device__ __forceinline__ void long_block_sum(double (&v)[N], double* red) {
@@ -84,17 +76,6 @@ __device__ __forceinline__ void long_linearize(const DevPtrs& P, const double* p
     L.valid = true;
 }
 
-// Inverse Cholesky factor of the damped H_ll, the formula of group_eliminate
-__device__ __forceinline__ void long_damped_inverse(const DevPtrs& P, const double* H, const double* s, double radius, double* Mi) {
-    const double ir = 1.0 / radius;
-    const double s0 = s[0] * s[0], s1 = s[1] * s[1], s2 = s[2] * s[2];
-    double M[6] = {H[0], H[1], H[2], H[3], H[4], H[5]};
-    M[0] += fmin(fmax(s0 * H[0], P.o.min_lm_diagonal), P.o.max_lm_diagonal) * ir / s0;
-    M[3] += fmin(fmax(s1 * H[3], P.o.min_lm_diagonal), P.o.max_lm_diagonal) * ir / s1;
-    M[5] += fmin(fmax(s2 * H[5], P.o.min_lm_diagonal), P.o.max_lm_diagonal) * ir / s2;
-    sym3_chol_inverse(M, Mi);
-}
-
 // ---- linearise and eliminate one long track per workgroup ------------------------------------------------------------------
 template <int FACTOR>
 __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A, int slot) {
@@ -107,7 +88,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A
     double* Y = (double*)smem;                       // [n_kf][6][3]
     double* camTab = Y + 18 * (size_t)A.max_kf;
     double* red = camTab + MAX_WIN_CAM * 17;
-    long_stage_cams(P, W, camTab);
+    stage_cams(P, W.cam_base, W.n_cam, camTab);
     for (int i = tid; i < 18 * T.n_kf; i += LONG_THREADS) Y[i] = 0.0;
     const int gl = T.gl, ob = P.lmk_ob[gl], oe = ob + T.n_obs;
     // 0 free (eliminated here), 1 constant, 2 kept in the reduced system by a prior (layout_reduced_plan: keep_landmark). A kept track
@@ -155,7 +136,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_lin(DevPtrs P, LongArgs A
         } else {
             s[0] = P.s_lmk[3 * (long long)gl]; s[1] = P.s_lmk[3 * (long long)gl + 1]; s[2] = P.s_lmk[3 * (long long)gl + 2];
         }
-        long_damped_inverse(P, H, s, st.radius, Mi);
+        damped_inverse(P, H, s, st.radius, Mi);
     }
     li_vec(Mi, g, gam);   // (zero unless the track is eliminated here)
     if (tid == 0) {
@@ -240,7 +221,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_back(DevPtrs P, LongArgs 
     const int tid = threadIdx.x;
     double* camTab = (double*)smem;
     double* red = camTab + MAX_WIN_CAM * 17;
-    long_stage_cams(P, W, camTab);
+    stage_cams(P, W.cam_base, W.n_cam, camTab);
     const int gl = T.gl, ob = P.lmk_ob[gl], oe = ob + T.n_obs;
     // 0 free, 1 constant, 2 kept in the reduced system by a prior: its step is part of the reduced solution (k_solve counted |step|^2
     // there), so no H_ll, no t and no inverse are formed; |candidate|^2 is counted here, as k_backsub does for the kept landmarks of
@@ -294,7 +275,7 @@ __global__ __launch_bounds__(LONG_THREADS) void k_long_back(DevPtrs P, LongArgs 
         double Mi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         if (lfree) {
             const double s[3] = {P.s_lmk[3 * (long long)gl], P.s_lmk[3 * (long long)gl + 1], P.s_lmk[3 * (long long)gl + 2]};
-            long_damped_inverse(P, acc, s, st.radius, Mi);
+            damped_inverse(P, acc, s, st.radius, Mi);
         }
         // delta_l = -M^-1 t = -Li^T (Li t)
         double ut[3], vt[3];
