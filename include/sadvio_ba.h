@@ -435,6 +435,12 @@ int sadvio_ba_marginalize(sadvio_ba_handle *h, int32_t w, const sadvio_marg_requ
  * route. calls - unpivoted - fell_back = calls that pivoted without a try (no earlier prior, or the noise-floor cut). */
 int sadvio_ba_marg_stats(sadvio_ba_handle *h, int32_t *calls, int32_t *unpivoted, int32_t *fell_back);
 
+/* Whether the last sadvio_ba_solve of this handle ran the single-round instantiations of its tile kernels: 1 or 0 in
+ * *taken. They serve submissions whose every tile holds one landmark round per wave and that need neither the robust loss, a prior
+ * that keeps landmarks, nor IMU workgroups; SADVIO_NO_ONE_ROUND=1 (read when the handle is created) keeps the looping kernels. The
+ * arithmetic is the same either way. */
+int sadvio_ba_one_round(sadvio_ba_handle *h, int32_t *taken);
+
 /* The handle's prior: read-back on request (any pointer may be NULL; J has room for n_full * n, r0 for n_full doubles),
  * upload of a prior kept elsewhere (e.g. restored from a dump; n_full = 0 clears it), and its shape. */
 typedef struct sadvio_prior_info {

@@ -447,6 +447,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.sadvio_ba_marginalize_relative_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, C.c_int32, _dp, _dp, _dp, _ip, _ip]
     lib.sadvio_ba_get_prior.argtypes = [C.c_void_p, C.POINTER(PriorInfoC), _dp, _dp]
     lib.sadvio_ba_marg_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if hasattr(lib, "sadvio_ba_one_round"):
+        lib.sadvio_ba_one_round.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.sadvio_ba_set_prior.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
     lib.sadvio_ba_linearize.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp]
     lib.sadvio_ba_vi_init.argtypes = [C.c_void_p, C.POINTER(ViInitProblemC), C.POINTER(SolveOptions), C.POINTER(SolveSummary),
@@ -684,6 +686,12 @@ class Backend:
         v = [C.c_int32(0) for _ in range(3)]
         self._check(self.lib.sadvio_ba_marg_stats(self.h, *[C.byref(x) for x in v]), "marg_stats")
         return {"calls": v[0].value, "unpivoted": v[1].value, "fell_back": v[2].value}
+
+    def one_round(self) -> bool:
+        """Whether the last solve ran the single-round instantiations of the tile kernels (sadvio_ba_one_round)."""
+        v = C.c_int32()
+        self._check(self.lib.sadvio_ba_one_round(self.h, C.byref(v)), "one_round")
+        return bool(v.value)
 
     def get_prior(self, readback: bool = True):
         """The handle's prior (sadvio_ba_get_prior): {"valid", "n_full", "n", "form"[, "J", "r0"]}."""

@@ -196,6 +196,12 @@ int sadvio_ba_marg_stats(sadvio_ba_handle* h, int32_t* calls, int32_t* unpivoted
     return SADVIO_OK;
 }
 
+int sadvio_ba_one_round(sadvio_ba_handle* h, int32_t* taken) {
+    if (!h || !taken) return SADVIO_E_INVALID_ARG;
+    *taken = h->last_one_round ? 1 : 0;
+    return SADVIO_OK;
+}
+
 int sadvio_ba_get_prior(sadvio_ba_handle* h, sadvio_prior_info* info, double* J, double* r0) {
     if (!h) return SADVIO_E_INVALID_ARG;
     return read_prior(h, info, J, r0);

@@ -267,7 +267,7 @@ struct EnvCfg {
     int cov_cross_stage = -1;   // covariance_cross: doubles of a block row k_cov_cross stages in LDS (tests: both sides of the limit); -1 not set: COVX_STAGE_MAX
     int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range): LongCfg::from_create applies it
     double jacobi_tol = 1e-14;
-    bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false;
+    bool marg_pivoted = false, marg_unpivoted = false, pchol_strict = false, no_lpt = false, no_pre = false, no_fork = false, no_bcr = false, imu_items = false, contig_tiles = false, c16_old_tail = false, no_one_round = false;
     void read() {
         auto on = [](const char* k) { return getenv(k) != nullptr; };
         auto num = [](const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; };
@@ -282,6 +282,7 @@ struct EnvCfg {
         marg_pivoted = on("SADVIO_MARG_PIVOTED"); marg_unpivoted = on("SADVIO_MARG_UNPIVOTED"); pchol_strict = on("SADVIO_PCHOL_STRICT");
         no_lpt = on("SADVIO_NO_LPT"); no_pre = on("SADVIO_NO_PRE"); no_fork = on("SADVIO_NO_FORK");
         no_bcr = on("SADVIO_NO_BCR");
+        { const char* e = getenv("SADVIO_NO_ONE_ROUND"); no_one_round = e && atoi(e) != 0; }   // A/B: single-round tiles on the kernels that loop over landmark rounds
         contig_tiles = on("SADVIO_CONTIG_TILES");   // A/B: single-round tiles as runs of consecutive landmarks (no packing, tile_pack.h)
         c16_old_tail = on("SADVIO_C16_OLD_TAIL");   // A/B: k_solve's in-LDS solve with both barriers of its last block column (chol16.h)
         imu_items = on("SADVIO_IMU_ITEMS");   // A/B: the IMU pairs' entries through k_solve's item loop (the pre-0.5 path) on one device too
@@ -367,6 +368,7 @@ struct sadvio_ba_handle {
     DevBuf<int> d_lmk_red, d_kept_obs, d_dp_ints;
     DevBuf<double> d_dp_data;
     int last_slots = 0;
+    bool last_one_round = false;   // the last solve's SolvePlan::one_round (sadvio_ba_one_round)
     // device buffers
     DevBuf<WinDev> d_win;
     DevBuf<Tile> d_tiles;

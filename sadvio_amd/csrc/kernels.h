@@ -150,7 +150,10 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_pre_packets(const Tile* __res
 // IMU = true (windows with IMU factors): the workgroups behind the tiles linearise one IMU factor pair each (imu_pair_lin_wg,
 // one wave; its 500 registers leave one workgroup per CU, which is what a single window runs at anyway).
 template <bool COST_ONLY> __device__ __forceinline__ void pose_factor_eval(const DevPtrs& P, int slot, int idx, int ln);   // below
-template <int FACTOR, bool RARE, bool IMU>
+// ONE = true (SolvePlan::one_round: every tile of the submission runs a single landmark round, LayoutPlan::single_round): the loop over the
+// rounds is left after the first, so nothing is carried around it - 152 VGPRs instead of 231 and 14 spilled SGPRs instead of 58 in
+// k_build<0, false, false, .>, the same arithmetic (docs/KERNEL_HISTORY.md "A record from k_build to k_backsub").
+template <int FACTOR, bool RARE, bool IMU, bool ONE = false>
 __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P, int slot, int max_tile_kf, int strip_doubles, int Rp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (IMU && (int)blockIdx.x >= P.n_tiles) {
@@ -549,6 +552,7 @@ __global__ __launch_bounds__(BUILD_THREADS, IMU ? 1 : 2) void k_build(DevPtrs P,
         }
         wave_lds_fence();  // the strip is reused by the next round
     }
+        if (ONE) break;   // single-round tiles: there is no next round
         }
     if (gemm_mode && wv * lpw < nl) {
         // the wave's Y E^T sum goes to the tile (ds_add_f64: the 4 waves add to the same entries)
@@ -1777,7 +1781,8 @@ __device__ __forceinline__ void zero_s_slice(const DevPtrs& P, const Tile& T, in
 // ---- K7: back-substitution + candidate cost -------------------------------------------------------
 // IMU = true (windows with IMU factors): the workgroups behind the tiles evaluate the cost of one IMU factor pair each at the
 // candidate (imu_pair_cost: one wave, beside the tiles instead of behind them on the stream).
-template <int FACTOR, bool RARE, bool IMU>
+// ONE = true: as in k_build, the tiles' single landmark round without the loop around it.
+template <int FACTOR, bool RARE, bool IMU, bool ONE = false>
 __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, int max_tile_kf) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (IMU && (int)blockIdx.x >= P.n_tiles) {
@@ -1979,6 +1984,7 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_backsub(DevPtrs P, int slot, 
             cc += RARE ? huber_rho(P.o.huber_a, r[0] * r[0] + r[1] * r[1], sc_unused) : r[0] * r[0] + r[1] * r[1];
             }
         }
+        if (ONE) break;   // single-round tiles: there is no next round
     }
     sn = wave_sum(sn); cn = wave_sum(cn); mcc = wave_sum(mcc); cc = wave_sum(cc);
     __shared__ double s_part[BUILD_WAVES * 4];

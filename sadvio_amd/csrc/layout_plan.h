@@ -132,6 +132,7 @@ struct LayoutPlan {
     int lm_ksub = 1, lm_max_cam = 1, lm_n_sub = 0;
     int lm_sub_per_item = 8;              // sub-blocks per work item of k_lm_pass (8 = the whole tile: MAX tile = 512 landmarks)
     bool pre_ok = false;                  // few enough tiles for the first-round packets
+    bool single_round = false;            // every tile holds at most BUILD_WAVES * (64 / G) landmarks: each wave of k_build / k_backsub runs one landmark round
     // layout_reduced_plan
     std::vector<int> lmk_red, kept, dp_ints, sp_list;
     std::vector<unsigned char> lmk_const_red;      // lmk_const with 2 = kept in the reduced system
@@ -682,6 +683,8 @@ inline void layout_chunks(const LayoutIn& in, LayoutPlan& P) {
     if (P.long_slot.empty()) P.long_slot.push_back(0);
     // first-round packets of the latency kernels (k_pre_packets): few-tile submissions only, the single-window / small-batch regime
     P.pre_ok = !P.tiles.empty() && P.tiles.size() <= PRE_MAX_TILES && !in.no_pre;
+    P.single_round = !P.tiles.empty();
+    for (const Tile& t : P.tiles) P.single_round = P.single_round && t.n_lmk <= BUILD_WAVES * (64 / t.G);
 }
 
 // Layout of the reduced systems of all windows: [free key-frames (dpf each) | prior-kept landmarks (3 each) | lines (6 each)].

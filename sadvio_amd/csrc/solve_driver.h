@@ -137,18 +137,21 @@ struct BigPlan {
     }
 };
 
-// The eight instantiations of a tile kernel template <FT, RARE, WITH_IMU>, indexed [pix][rare][with_imu] (FT 0 is the pixel factor)
-#define SADVIO_TILE_VARIANTS(K) {{{K<1, false, false>, K<1, false, true>}, {K<1, true, false>, K<1, true, true>}}, \
-                                 {{K<0, false, false>, K<0, false, true>}, {K<0, true, false>, K<0, true, true>}}}
+// The instantiations of a tile kernel template <FT, RARE, WITH_IMU, ONE>, indexed [one][pix][rare][with_imu] (FT 0 is the pixel factor). Only the plain
+// variants exist with ONE (plan_solve never asks for another: those entries repeat the kernel without it).
+#define SADVIO_TILE_VARIANTS(K) {{{{K<1, false, false>, K<1, false, true>}, {K<1, true, false>, K<1, true, true>}}, \
+                                  {{K<0, false, false>, K<0, false, true>}, {K<0, true, false>, K<0, true, true>}}}, \
+                                 {{{K<1, false, false, true>, K<1, false, true>}, {K<1, true, false>, K<1, true, true>}}, \
+                                  {{K<0, false, false, true>, K<0, false, true>}, {K<0, true, false>, K<0, true, true>}}}}
 using BuildFn = decltype(&k_build<0, false, false>);
 using BacksubFn = decltype(&k_backsub<0, false, false>);
-BuildFn build_variant(bool pix, bool rare, bool with_imu) {
-    static const BuildFn t[2][2][2] = SADVIO_TILE_VARIANTS(k_build);
-    return t[pix][rare][with_imu];
+BuildFn build_variant(bool pix, bool rare, bool with_imu, bool one) {
+    static const BuildFn t[2][2][2][2] = SADVIO_TILE_VARIANTS(k_build);
+    return t[one][pix][rare][with_imu];
 }
-BacksubFn backsub_variant(bool pix, bool rare, bool with_imu) {
-    static const BacksubFn t[2][2][2] = SADVIO_TILE_VARIANTS(k_backsub);
-    return t[pix][rare][with_imu];
+BacksubFn backsub_variant(bool pix, bool rare, bool with_imu, bool one) {
+    static const BacksubFn t[2][2][2][2] = SADVIO_TILE_VARIANTS(k_backsub);
+    return t[one][pix][rare][with_imu];
 }
 #undef SADVIO_TILE_VARIANTS
 
@@ -160,6 +163,7 @@ struct SolvePlan {
     int mtk, Rp, strip_doubles;
     int n_kf_tot, n_pf, n_lo, dp_max_nf, dp_max_n, reset_blocks, table_blocks, max_win_tiles, lm_n_sub, lm_sub_obs, n_big;
     bool pix, rare, with_imu, use_lm, extras, fork;
+    bool one_round;        // the tile kernels are the ONE instantiations (k_build / k_backsub without the loop over landmark rounds)
     bool coll_band;        // sharded: only the band of the one window's S travels (coll_buf = the packed copy)
     size_t lds_build, lds_back, lds_solve, lds_bobs, lds_pass0, lds_pass, lds_long_lin, lds_long_back;
     BuildFn k_build;
@@ -364,8 +368,11 @@ int plan_solve(sadvio_ba_handle* h, const SolveOpts& o, SolvePlan& plan, std::ve
     bool with_imu = have_pf && n_tiles <= 3 * 256;
     if (h->env.pf_wg >= 0) with_imu = have_pf && h->env.pf_wg != 0;
     plan.with_imu = with_imu;
-    plan.k_build = build_variant(pix, rare, with_imu);
-    plan.k_backsub = backsub_variant(pix, rare, with_imu);
+    // Single-round tiles (a single window, a small batch) on the plain kernels: the instantiations without the loop over landmark rounds.
+    // SADVIO_NO_ONE_ROUND=1 keeps the looping kernels (A/B, tests); it reaches the graph key through this field.
+    const bool one = plan.one_round = h->plan.single_round && !rare && !with_imu && !h->env.no_one_round;
+    plan.k_build = build_variant(pix, rare, with_imu, one);
+    plan.k_backsub = backsub_variant(pix, rare, with_imu, one);
     plan.k_build_kept = pix ? k_build_kept<0> : k_build_kept<1>;
     if (h->plan.n_long > 0) {
         plan.lg.n_long = h->plan.n_long; plan.lg.max_kf = h->plan.long_max_kf;
@@ -663,7 +670,7 @@ int solve_summaries(sadvio_ba_handle* h, const SolveOpts& o, const SolvePlan& pl
     const int n_win = plan.P.n_win;
     h->fin.assign(h->h_final, h->h_final + n_win);
     h->deltas_cached = false;
-    h->last_slots = plan.slots;
+    h->last_slots = plan.slots; h->last_one_round = plan.one_round;
     h->cov_huber_a = o.huber_a; h->cov_use_lm = plan.use_lm;
     h->solved = true;
     int rc = SADVIO_OK;
