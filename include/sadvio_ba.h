@@ -751,6 +751,24 @@ typedef struct sadvio_cov_request {
  * the call was refused before (N_p >= 2047), so no window served before changes a bit; 1, every bandable window takes it (tests,
  * A/B timing); 0, never (the 2047-column refusal included). In sadvio_ba_get_kernel_times the route shows as the classes cov_band
  * (forward sweep), cov_band_sel (backward sweep), cov_band_pairs and cov_band_gather in place of cov_invert.
+ * The border route: long windows with loop closures. One far coupling (a landmark seen again hundreds of key-frames later, one
+ * SADVIO_SPARSE_RELATIVE_POSE factor between distant key-frames) makes hb about the number of free key-frames, and the window is no
+ * longer bandable. A CLOSURE EDGE is a coupled pair of free key-frames more than hb_lim apart (hb_lim = 19 at d = 6, 7 at d = 15: the
+ * band route's limit); the BORDER is a vertex cover of the closure edges, built greedily (the key-frame that covers the most
+ * uncovered edges, the lowest index on a tie). The window is BORDERABLE when it has no dense prior, no landmarks kept in the reduced
+ * system and no lines, the border has 0 < m <= 96 columns, and the core (the other free key-frames, natural order, n_b columns, band
+ * bw' <= (hb_lim + 1) d by construction) has n_b > bw'. With the columns ordered [core | border], S = [B C; C^T D]: the band of
+ * B^-1 comes from the band route's two sweeps on B, W = B^-1 C from band substitution, T = D - C^T W is factored densely with the
+ * same three pivot tests (the pivots of B followed by those of T are the pivots of S in this order), and
+ *     Sigma_DD = T^-1,  Sigma_BD = -W T^-1,  Sigma_BB(i, j) = B^-1(i, j) + (W T^-1 W^T)(i, j)
+ * are formed inside the core's band and on the border's rows and columns, which is every block a landmark block reads. Pair blocks
+ * of two core key-frames outside the band come from band substitution on B plus the same correction. pair(a, b) and pair(b, a)^T
+ * are equal to the bit, and a pair's bits do not depend on the other blocks asked for. Environment variable SADVIO_COV_BORDER, read
+ * when the handle is created: unset, a borderable window takes the route only where the call was refused before (N_p >= 2047 and
+ * not bandable), so no window served before changes a bit; 1, every borderable window takes it, in front of the band route (tests,
+ * A/B timing); 0, never. SADVIO_COV_BORDER_HB lowers hb_lim (tests). In sadvio_ba_get_kernel_times the route adds the classes
+ * cov_border_split, cov_border_solve, cov_border_schur and cov_border_apply to the band route's. sadvio_ba_covariance_cross does
+ * not take this route: it keeps refusing a window of 2047 columns or more that is not bandable.
  * The square-root assembly. A landmark millimetres from a camera centre puts 1e12 and more into H_pp beside entries of S of 1e10;
  * S = H_pp - sum_l H_pl H_ll^-1 H_lp then loses its digits to the subtraction (5e-4 of relative error in a key-frame block at 1 mm)
  * and comes out indefinite at 0.1 mm. The second assembly forms the same S and landmark blocks without that difference: per
@@ -788,6 +806,9 @@ int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_reques
  *   SADVIO_COV_ROUTE_BAND   a window that sadvio_ba_covariance sends down its band route (see there and SADVIO_COV_BAND: by default
  *                           a bandable window of 2047 columns or more), item by item through the single call's steps. Same bits as
  *                           the single call.
+ *   SADVIO_COV_ROUTE_BORDER a window that sadvio_ba_covariance sends down its border route (see there and SADVIO_COV_BORDER: by
+ *                           default a borderable window of 2047 columns or more that is not bandable), item by item through the
+ *                           single call's steps. Same bits as the single call.
  * The environment variable SADVIO_COV_BATCH_LDS=0 (read when the handle is created) sends every item with N_p > 0 down the DENSE
  * route. The LDS and NONE items are processed in groups of windows whose work arrays stay under 1 GiB
  * (SADVIO_COV_BATCH_SCRATCH_MB overrides the figure; a window larger than the budget is a group of its own); the grouping does not
@@ -817,6 +838,7 @@ int sadvio_ba_covariance(sadvio_ba_handle *h, int32_t w, const sadvio_cov_reques
 #define SADVIO_COV_ROUTE_LDS   1
 #define SADVIO_COV_ROUTE_DENSE 2
 #define SADVIO_COV_ROUTE_BAND  3
+#define SADVIO_COV_ROUTE_BORDER 4
 
 typedef struct sadvio_cov_batch_item {
     int32_t w;               /* in: window of the batch */

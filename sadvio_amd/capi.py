@@ -133,7 +133,7 @@ class CovCrossRequestC(C.Structure):
     _fields_ = [("n", C.c_int32), ("kf", _ip), ("lmk", _ip), ("cam", _ip), ("meas", _dp)]
 
 
-COV_ROUTE_NONE, COV_ROUTE_LDS, COV_ROUTE_DENSE, COV_ROUTE_BAND = 0, 1, 2, 3   # SADVIO_COV_ROUTE_*
+COV_ROUTE_NONE, COV_ROUTE_LDS, COV_ROUTE_DENSE, COV_ROUTE_BAND, COV_ROUTE_BORDER = 0, 1, 2, 3, 4   # SADVIO_COV_ROUTE_*
 CROSS_OK, CROSS_LMK_SINGULAR, CROSS_PROJ_INVALID = 0, 1, 2                    # SADVIO_CROSS_*
 PRIOR_RESIDENT = -1
 # SADVIO_EIG_CUT_*: the C ABI's default (a zero-initialised request) is the reference's absolute 1e-12; this harness and the

@@ -25,6 +25,7 @@
 #include "long_kernels.h"
 #include "viinit_kernels.h"
 #include "nofov_kernels.h"
+#include "cov_border_plan.h"
 
 using namespace sadvio;
 
@@ -204,6 +205,14 @@ struct CovScratch {
     // gathered blocks; the in-band pair table of k_cov_schur | the gather table | the pivot flag
     DevBuf<double> Lb, Linv, X, gout;
     DevBuf<int> pair_tab, gtab, xcol, bflag;
+    // the border route (cov_border_kernels.h): the compacted band of B and of B^-1 | C, D | W, Z, T^-1 | [core | border] -> natural column;
+    // the windows' plans (cov_border_plan.h), made by the first covariance call after a solve (border_known[w]) and dropped by the next
+    // solve: every change of the layout passes a solve before a covariance call is served again
+    DevBuf<double> bSb, bSigc, bCt, bDm, bW, bZ, bTinv;
+    DevBuf<int> bperm;
+    std::vector<int> h_bperm;
+    std::vector<CovBorderPlan> border_plan;
+    std::vector<char> border_known;
     std::vector<int> h_pair_tab, h_gtab, h_xcol;
     // the square-root assembly (cov_kernels.h: k_cov_assemble_sqrt): J_p and Q1 rows and the entry of every observation | the
     // key-frame -> landmark lists (cov_kf_lists.h)
@@ -264,6 +273,8 @@ struct EnvCfg {
     int cov_batch_lds = 1, cov_batch_scratch_mb = 1024;   // sadvio_ba_covariance_batch: the in-LDS inverse (0: every item down the dense route, A/B) | scratch budget of one group
     int cov_band = -1;   // covariance, the band route (cov_band_kernels.h): -1 not set: only where the call was refused before (N_p >= 2047) | 1: every bandable window | 0: never
     int cov_sqrt = -1;   // covariance, the square-root assembly (cov_kernels.h): -1 not set: only after the pivot tests refused the plain form | 1: from the start | 0: never
+    int cov_border = -1; // covariance, the border route (cov_border_kernels.h): -1 not set: only where the call was refused before (N_p >= 2047) | 1: every borderable window that is not plainly bandable | 0: never
+    int cov_border_hb = 0;   // ... its hb_lim (cov_border_plan.h), tests: a value in [1, the band kernels' limit) lowers it; 0: not set
     int cov_cross_stage = -1;   // covariance_cross: doubles of a block row k_cov_cross stages in LDS (tests: both sides of the limit); -1 not set: COVX_STAGE_MAX
     int long_min_env = 0;   // SADVIO_LONG_MIN as read (0: not set or out of range): LongCfg::from_create applies it
     double jacobi_tol = 1e-14;
@@ -276,6 +287,7 @@ struct EnvCfg {
         cov_batch_lds = num("SADVIO_COV_BATCH_LDS", 1); cov_batch_scratch_mb = num("SADVIO_COV_BATCH_SCRATCH_MB", 1024);
         cov_band = num("SADVIO_COV_BAND", -1); cov_sqrt = num("SADVIO_COV_SQRT", -1);
         cov_cross_stage = num("SADVIO_COV_CROSS_STAGE", -1);
+        cov_border = num("SADVIO_COV_BORDER", -1); cov_border_hb = std::max(num("SADVIO_COV_BORDER_HB", 0), 0);
         long_min_env = num("SADVIO_LONG_MIN", 0);
         if (long_min_env < 2 || long_min_env > MAX_LMK_OBS + 1) long_min_env = 0;
         if (const char* e = getenv("SADVIO_JACOBI_TOL")) jacobi_tol = atof(e);

@@ -61,10 +61,10 @@ int covb_check(sadvio_ba_handle* h, int n_item, const sadvio_cov_batch_item* ite
     return SADVIO_OK;
 }
 
-// Does item I go through the single call's steps (cov_driver.h: cov_steps)? The DENSE and BAND routes; under SADVIO_COV_SQRT=1 a
+// Does item I go through the single call's steps (cov_driver.h: cov_steps)? The DENSE, BAND and BORDER routes; under SADVIO_COV_SQRT=1 a
 // NONE item too, for the landmark-block formula of the square-root assembly.
 bool covb_single(const sadvio_ba_handle* h, const sadvio_cov_batch_item& I) {
-    return I.route == SADVIO_COV_ROUTE_DENSE || I.route == SADVIO_COV_ROUTE_BAND || (I.route == SADVIO_COV_ROUTE_NONE && h->env.cov_sqrt == 1);
+    return I.route == SADVIO_COV_ROUTE_DENSE || I.route == SADVIO_COV_ROUTE_BAND || I.route == SADVIO_COV_ROUTE_BORDER || (I.route == SADVIO_COV_ROUTE_NONE && h->env.cov_sqrt == 1);
 }
 
 // 2. The route of every item; one unit per window that does not take the dense route
@@ -78,6 +78,7 @@ void covb_routes(sadvio_ba_handle* h, int n_item, sadvio_cov_batch_item* items, 
         const bool lds = h->env.cov_batch_lds != 0 && h->env.cov_sqrt != 1;   // (the square-root assembly has no group kernels: its items go one by one)
         I.route = d.Np == 0 ? SADVIO_COV_ROUTE_NONE : (d.Np <= COVB_CAP && lds ? SADVIO_COV_ROUTE_LDS : SADVIO_COV_ROUTE_DENSE);
         if (cov_band_route(h, I.w)) I.route = SADVIO_COV_ROUTE_BAND;   // (cov_driver.h: by default only a window the dense route refuses)
+        if (cov_border_route(h, I.w)) I.route = SADVIO_COV_ROUTE_BORDER;   // (cov_driver.h: by default only a window that is refused otherwise)
         if (covb_single(h, I)) continue;
         const CovRoutes R = cov_routes(h, I.w, &I.rq, I.lmk_cov);
         if (of_win[I.w] < 0) {

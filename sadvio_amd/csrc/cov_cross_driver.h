@@ -18,7 +18,7 @@ struct CovCrossOut { double* cross; double* innov; double* maha2; int32_t* statu
 // 1. State and arguments: cov_check's refusals with its texts, then the candidates. Host work only.
 int covx_check(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, const CovCrossOut& O) {
     const sadvio_cov_request none{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
-    if (int rc = cov_check(h, w, rq ? &none : nullptr)) return rc;
+    if (int rc = cov_check(h, w, rq ? &none : nullptr, false)) return rc;   // (the border route has no block rows yet: such a window keeps its refusal)
     const WinDev& d = h->plan.wins[w].d;
     if (rq->n < 0 || (rq->n > 0 && (!rq->kf || !rq->lmk)) || ((rq->cam == nullptr) != (rq->meas == nullptr))) { h->err = "covariance: request out of range"; return SADVIO_E_INVALID_ARG; }
     if ((O.innov || O.maha2) && !rq->cam) { h->err = "covariance_cross: innovation outputs without a candidate camera and measurement"; return SADVIO_E_INVALID_ARG; }
@@ -118,7 +118,7 @@ int covx_run(sadvio_ba_handle* h, int w, const sadvio_cov_cross_request* rq, dou
     // Sigma_ll of every landmark is needed exactly when an innovation is formed
     static const double want_lmk = 0.0;
     const sadvio_cov_request all{0, nullptr, 0, nullptr, nullptr, -1, nullptr};
-    return cov_steps(h, w, cov_routes(h, w, &all, rq->cam ? &want_lmk : nullptr), [=](const CovRoutes& R) { return covx_cross(h, w, rq, R, O); });
+    return cov_steps(h, w, cov_routes(h, w, &all, rq->cam ? &want_lmk : nullptr, false), [=](const CovRoutes& R) { return covx_cross(h, w, rq, R, O); });
 }
 
 }  // namespace

@@ -1,7 +1,9 @@
 // cov_driver.h — the host side of sadvio_ba_covariance as named steps
 //   cov_check -> cov_routes -> cov_assemble -> cov_invert -> cov_landmarks -> cov_read_back
 // Sigma_pp is formed densely (cov_invert) or, for a block-banded S, inside its band only (cov_invert_band, cov_band_kernels.h: the
-// BAND route; cov_band_route says when). On the band route k_cov_schur runs over the table of in-band key-frame pairs, no kernel
+// BAND route; cov_band_route says when) or, for a window that loop closures keep from being banded, inside the band of its core and
+// on the rows of a small border (cov_invert_border, cov_border_kernels.h: the BORDER route; cov_border_route says when; its
+// read-back is the band route's). On the band route k_cov_schur runs over the table of in-band key-frame pairs, no kernel
 // reads an entry of Sigma outside the band, pair blocks outside the band come from band substitution, and the host receives the
 // blocks asked for and nothing else.
 // S and the landmark blocks have two assemblies: the plain one and the square-root one, which survives landmarks millimetres from a
@@ -21,6 +23,7 @@
 #include <climits>
 #include "ba_handle.h"
 #include "cov_band_kernels.h"
+#include "cov_border_kernels.h"
 #include "cov_kernels.h"
 #include "cov_kf_lists.h"
 #include "cov_long_kernels.h"
@@ -40,6 +43,8 @@ struct CovRoutes {
     int n_lmk_out = 0;      // landmark blocks written
     bool band = false;      // the band route; then hb / bw / nb: block half-bandwidth, (hb + 1) * dpf, block column of the sweeps
     int hb = 0, bw = 0, nb = 0, dpf = 6;
+    const CovBorderPlan* border = nullptr;   // the border route (then band is false): hb / bw are the core's hb' / bw'
+    bool banded() const { return band || border != nullptr; }
     bool sqrt = false;      // the square-root assembly instead of the plain one (cov_assemble)
     int n_long = 0, long_first = 0, long_max_kf = 0;   // long tracks of the window, its first on the long list, LongArgs::max_kf (k_cov_long, k_cov_lmk_long)
 };
@@ -61,6 +66,46 @@ bool cov_band_route(const sadvio_ba_handle* h, int w, int* hb_out = nullptr, int
     return h->env.cov_band > 0 || d.Np + 1 > PCH_MAXN;
 }
 
+// The border route's plan of window w (cov_border_plan.h), made once per solve from the couplings window_bandwidth counts
+const CovBorderPlan& cov_border_plan_of(sadvio_ba_handle* h, int w) {
+    CovScratch& V = h->cv;
+    const size_t n_win = h->plan.wins.size();
+    if (V.border_known.size() != n_win) { V.border_known.assign(n_win, 0); V.border_plan.resize(n_win); }
+    CovBorderPlan& P = V.border_plan[w];
+    if (V.border_known[w]) return P;
+    const WinDev& d = h->plan.wins[w].d;
+    const LayoutPlan& L = h->plan;
+    CovBorderCouplings Cp;
+    Cp.n_free = d.n_free_kf;
+    std::vector<int> f;
+    for (int l = 0; l < d.n_lmk; l++) {   // (long tracks included: the observation lists hold every observation)
+        f.clear();
+        for (int o = L.lmk_ob[d.lmk_base + l]; o < L.lmk_oe[d.lmk_base + l]; o++) f.push_back(L.kf_fidx[L.obs_kf[o]]);
+        Cp.add_landmark(f.data(), (int)f.size());
+    }
+    for (const ImuDev& q : h->imus_per_win[w]) Cp.add_pair(L.kf_fidx[q.kf_i], L.kf_fidx[q.kf_j]);
+    if (w < (int)h->sparse_per_win.size())
+        for (const sadvio_sparse_prior& sp : h->sparse_per_win[w])
+            if (sp.type == SADVIO_SPARSE_RELATIVE_POSE) Cp.add_pair(L.kf_fidx[d.kf_base + sp.kf], L.kf_fidx[d.kf_base + sp.kf_b]);
+    int hb_lim = cov_border_hb_max(d.dpf);
+    if (h->env.cov_border_hb > 0) hb_lim = std::min(hb_lim, h->env.cov_border_hb);   // (tests; only ever lowers it)
+    const bool fills = d.n_red > 0 || d.dp_n_full > 0 || d.line_end > d.line_begin || d.Np != d.n_free_kf * d.dpf;
+    cov_border_plan(Cp, d.dpf, cov_band_nb(d.dpf), hb_lim, fills, P);
+    V.border_known[w] = 1;
+    return P;
+}
+
+// Does window w take the border route? Borderable (cov_border_plan.h) and, SADVIO_COV_BORDER unset: only a window that is refused
+// otherwise (N_p >= 2047 and not on the band route); 1: every borderable window (a window without a closure edge is not borderable:
+// it keeps the band route or the dense one); 0: never. The plan, or null.
+const CovBorderPlan* cov_border_route(sadvio_ba_handle* h, int w) {
+    const WinDev& d = h->plan.wins[w].d;
+    if (h->env.cov_border == 0 || d.Np <= 0 || h->world > 1) return nullptr;
+    if (h->env.cov_border < 0 && !(d.Np + 1 > PCH_MAXN && !cov_band_route(h, w))) return nullptr;
+    const CovBorderPlan& P = cov_border_plan_of(h, w);
+    return P.ok() ? &P : nullptr;
+}
+
 // An invalid argument of the call named `call` ("covariance" | "covariance_batch"): its text, its code
 int cov_invalid(sadvio_ba_handle* h, const char* call, const char* what) {
     h->err = std::string(call) + what;
@@ -69,8 +114,8 @@ int cov_invalid(sadvio_ba_handle* h, const char* call, const char* what) {
 
 // 1. Request rq on window w, for sadvio_ba_covariance and for every item of sadvio_ba_covariance_batch: the window, then the
 // request's counts, pointers and indices. through_lm: is a batch solved by the throughput kernels served (cov_batch_driver.h says why
-// the batch call accepts one)?
-int cov_check_request(sadvio_ba_handle* h, const char* call, int w, const sadvio_cov_request* rq, bool through_lm) {
+// the batch call accepts one)? border_ok: does the caller serve the border route (sadvio_ba_covariance_cross does not)?
+int cov_check_request(sadvio_ba_handle* h, const char* call, int w, const sadvio_cov_request* rq, bool through_lm, bool border_ok = true) {
     if (w < 0 || w >= (int)h->plan.wins.size()) return cov_invalid(h, call, ": window out of range");
     if (!rq) return cov_invalid(h, call, ": null request");
     const WinDev& d = h->plan.wins[w].d;
@@ -84,18 +129,18 @@ int cov_check_request(sadvio_ba_handle* h, const char* call, int w, const sadvio
         if (rq->pair_a[i] < 0 || rq->pair_a[i] >= d.n_kf || rq->pair_b[i] < 0 || rq->pair_b[i] >= d.n_kf) return cov_invalid(h, call, ": key-frame index of a pair out of range");
     for (int i = 0; i < rq->n_lmk; i++)
         if (rq->lmk[i] < 0 || rq->lmk[i] >= d.n_lmk) return cov_invalid(h, call, ": landmark index out of range");
-    if (d.Np + 1 > PCH_MAXN && !cov_band_route(h, w)) return cov_invalid(h, call, ": the reduced system has 2047 columns or more");
+    if (d.Np + 1 > PCH_MAXN && !cov_band_route(h, w) && !(border_ok && cov_border_route(h, w))) return cov_invalid(h, call, ": the reduced system has 2047 columns or more");
     return SADVIO_OK;
 }
 
 // 1. State and arguments. Host work only.
-int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq) {
+int cov_check(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, bool border_ok = true) {
     if (h->world > 1) return cov_invalid(h, "covariance", ": the window is sharded over several GPUs (each rank holds a landmark partition only)");
     if (int rc = entry_state(h, "covariance", NOT_DEFERRED | NEED_SOLVED)) return rc;
-    return cov_check_request(h, "covariance", w, rq, false);
+    return cov_check_request(h, "covariance", w, rq, false, border_ok);
 }
 
-CovRoutes cov_routes(const sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov) {
+CovRoutes cov_routes(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const double* lmk_cov, bool border_ok = true) {
     const WinDev& d = h->plan.wins[w].d;
     CovRoutes R;
     R.cur = h->fin[w].s.cur;
@@ -108,6 +153,8 @@ CovRoutes cov_routes(const sadvio_ba_handle* h, int w, const sadvio_cov_request*
     R.G = d.n_free_kf <= 8 ? 16 : 64;
     R.band = cov_band_route(h, w, &R.hb, &R.bw);
     R.nb = cov_band_nb(d.dpf); R.dpf = d.dpf;
+    R.border = border_ok ? cov_border_route(h, w) : nullptr;
+    if (R.border) { R.band = false; R.hb = R.border->hb_core; R.bw = (R.hb + 1) * d.dpf; }
     R.long_first = h->plan.wins[w].long_begin; R.n_long = h->plan.wins[w].long_end - R.long_first; R.long_max_kf = h->plan.long_max_kf;
     return R;
 }
@@ -119,7 +166,7 @@ CovDev cov_dev(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     C.ptab = V.ptab.p; C.hll = V.hll.p; C.hinv = V.hinv.p; C.status = V.status.p; C.ent_n = V.ent_n.p;
     C.ent_col = V.ent_col.p; C.ent_w = V.ent_w.p; C.ent_hpp = V.ent_hpp.p;
     C.S = V.S.p; C.Sig = V.Sig.p; C.lout = V.lout.p;
-    C.pair_tab = R.band ? V.pair_tab.p : nullptr;
+    C.pair_tab = R.banded() ? V.pair_tab.p : nullptr;
     C.is_long = R.n_long > 0 ? V.is_long.p : nullptr;
     return C;
 }
@@ -133,13 +180,15 @@ LongArgs cov_long_args(const sadvio_ba_handle* h) {
 }
 
 // On the band route every pair of free key-frames that observe one long track lies inside the band: window_bandwidth counts the
-// track. (Asserted below unless NDEBUG is defined; k_cov_lmk_long reads Sigma_pp at those pairs only.)
+// track. On the border route every such pair lies inside the core's band or has a border member: the planner counts the track.
+// (Asserted below unless NDEBUG is defined; k_cov_lmk_long reads Sigma_pp at those pairs only.)
 [[maybe_unused]] bool cov_long_in_band(const sadvio_ba_handle* h, int w, const CovRoutes& R) {
     for (int i = R.long_first; i < R.long_first + R.n_long; i++) {
         const int* rec = &h->plan.long_rec[(size_t)LONG_REC * i];
         int lo = INT_MAX, hi = -1;
         for (int k = 0; k < rec[3]; k++) {
-            const int f = h->plan.kf_fidx[h->plan.long_kf[rec[2] + k]];
+            int f = h->plan.kf_fidx[h->plan.long_kf[rec[2] + k]];
+            if (f >= 0 && R.border) f = R.border->core_of[f];   // (-1: a border key-frame)
             if (f >= 0) { lo = std::min(lo, f); hi = std::max(hi, f); }
         }
         if (hi - lo > R.hb) return false;
@@ -151,7 +200,7 @@ LongArgs cov_long_args(const sadvio_ba_handle* h) {
 // k_cov_tables and the tile assembly, in front of k_cov_schur(_sqrt). Q: the square-root assembly's tables (R.sqrt), else unused.
 int cov_assemble_long(sadvio_ba_handle* h, const CovRoutes& R, const DevPtrs& P, const CovDev& C, const CovSqrtDev& Q) {
     if (R.n_long == 0) return SADVIO_OK;
-    assert(!R.band || cov_long_in_band(h, C.w, R));
+    assert(!R.banded() || cov_long_in_band(h, C.w, R));
     HIP_TRY(hipMemsetAsync(C.is_long, 0, sizeof(int) * (size_t)h->plan.wins[C.w].d.n_lmk, h->stream));
     auto k = R.sqrt ? (R.pix ? k_cov_long<0, true> : k_cov_long<1, true>) : (R.pix ? k_cov_long<0, false> : k_cov_long<1, false>);
     ScopedTimer t(h, "k_cov_long");
@@ -160,13 +209,21 @@ int cov_assemble_long(sadvio_ba_handle* h, const CovRoutes& R, const DevPtrs& P,
 }
 
 // The band route's workgroups of k_cov_schur(_sqrt): the in-band pairs (a, b), a >= b, a - b <= hb, as a table on the device —
-// nothing else of S can be non-zero. n_schur: how many.
+// nothing else of S can be non-zero. On the border route: the pairs inside the core's band (compacted index) and every pair with a
+// border member. n_schur: how many.
 int cov_pair_table(sadvio_ba_handle* h, const WinDev& d, const CovRoutes& R, int& n_schur) {
     CovScratch& V = h->cv;
     std::vector<int>& tab = V.h_pair_tab;
     tab.clear();
-    for (int a = 0; a < d.n_free_kf; a++)
-        for (int b = std::max(0, a - R.hb); b <= a; b++) { tab.push_back(a); tab.push_back(b); }
+    if (R.border) {
+        const std::vector<int>& core = R.border->core_of;
+        for (int a = 0; a < d.n_free_kf; a++)
+            for (int b = 0; b <= a; b++)
+                if (core[a] < 0 || core[b] < 0 || core[a] - core[b] <= R.hb) { tab.push_back(a); tab.push_back(b); }
+    } else {
+        for (int a = 0; a < d.n_free_kf; a++)
+            for (int b = std::max(0, a - R.hb); b <= a; b++) { tab.push_back(a); tab.push_back(b); }
+    }
     n_schur = (int)tab.size() / 2;
     HIP_TRY(V.pair_tab.alloc(tab.size()));
     HIP_TRY(hipMemcpyAsync(V.pair_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
@@ -196,7 +253,7 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     so.huber_a = h->cov_huber_a;
     const DevPtrs P = make_ptrs(h, so, h->last_slots + 2);
     int n_schur = d.n_free_kf * (d.n_free_kf + 1) / 2;
-    if (R.band && R.Np > 0)
+    if (R.banded() && R.Np > 0)
         if (int rc = cov_pair_table(h, d, R, n_schur)) return rc;
     CovSqrtDev Q{};
     if (R.sqrt) {
@@ -219,13 +276,13 @@ int cov_assemble(sadvio_ba_handle* h, int w, const CovRoutes& R) {
     if (int rc = cov_assemble_long(h, R, P, C, Q)) return rc;
     if (R.Np == 0) { HIP_TRY(hipGetLastError()); return SADVIO_OK; }
     if (d.n_free_kf > 0) {   // (band route, long tracks: a class of its own inside the assembly's span, for the profile)
-        ScopedTimer ts(h, R.band || R.n_long > 0 ? (R.sqrt ? "k_cov_schur_sqrt" : "k_cov_schur") : nullptr);
+        ScopedTimer ts(h, R.banded() || R.n_long > 0 ? (R.sqrt ? "k_cov_schur_sqrt" : "k_cov_schur") : nullptr);
         if (R.sqrt) hipLaunchKernelGGL(k_cov_schur_sqrt, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C, Q);
         else hipLaunchKernelGGL(k_cov_schur, dim3(n_schur), dim3(COV_SCHUR_THREADS), 0, h->stream, P, C);
     }
     if (R.kept) hipLaunchKernelGGL(R.pix ? k_cov_kept<0> : k_cov_kept<1>, dim3(1), dim3(64), 0, h->stream, P, C);
     {
-        ScopedTimer tf(h, R.band ? "k_cov_factors" : nullptr);
+        ScopedTimer tf(h, R.banded() ? "k_cov_factors" : nullptr);
         hipLaunchKernelGGL(k_cov_factors, dim3(1), dim3(64), 0, h->stream, P, C);
     }
     if (R.dense) hipLaunchKernelGGL(k_cov_dense, dim3((unsigned)(((long long)d.dp_n * d.dp_n + 255) / 256)), dim3(256), 0, h->stream, P, C);
@@ -264,9 +321,66 @@ int cov_invert_band(sadvio_ba_handle* h, const CovRoutes& R) {
     return SADVIO_OK;
 }
 
+// The border route's two views of its buffers: the core as the band kernels take it (compacted: n = n_b, S and Sigma the compacted
+// images), and the whole of it as cov_border_kernels.h's take it. The pivot tests keep S's figures (tau and safe_rel of N_p).
+CovBand cov_border_band_dev(sadvio_ba_handle* h, const CovRoutes& R) {
+    CovScratch& V = h->cv;
+    CovBand B = cov_band_dev(h, R);
+    B.n = R.border->n_core() * R.dpf;
+    B.S = V.bSb.p; B.Sig = V.bSigc.p;
+    return B;
+}
+CovBorder cov_border_dev(sadvio_ba_handle* h, const CovRoutes& R) {
+    CovScratch& V = h->cv;
+    const CovBand Bc = cov_border_band_dev(h, R);
+    CovBorder B{};
+    B.n = R.Np; B.nc = Bc.n; B.m = R.Np - Bc.n; B.bw = Bc.bw; B.M = Bc.M; B.dpf = R.dpf; B.tau = Bc.tau; B.safe_rel = Bc.safe_rel;
+    B.perm = V.bperm.p; B.S = V.S.p; B.Sig = V.Sig.p; B.Sb = V.bSb.p; B.Sigc = V.bSigc.p; B.Lb = V.Lb.p;
+    B.Ct = V.bCt.p; B.Dm = V.bDm.p; B.W = V.bW.p; B.Z = V.bZ.p; B.Tinv = V.bTinv.p; B.flag = V.bflag.p;
+    return B;
+}
+
+// 3 (border route). Split S into [B C; C^T D] by the plan; the band route's two sweeps on B; W = B^-1 C; the Schur complement T on
+// the border, factored with every pivot tested; the corrections into Sigma at its natural positions. Six launches whatever N_p; no
+// host wait: a failed pivot of B or of T sets V.bflag, which cov_read_back_band reads behind the call's one wait.
+int cov_invert_border(sadvio_ba_handle* h, const CovRoutes& R) {
+    CovScratch& V = h->cv;
+    const CovBorderPlan& P = *R.border;
+    const int dpf = R.dpf, nc = P.n_core() * dpf, m = (int)P.border.size() * dpf, M = R.bw + R.nb;
+    HIP_TRY(V.Lb.alloc((size_t)nc * M)); HIP_TRY(V.Linv.alloc((size_t)nc * R.nb)); HIP_TRY(V.bflag.alloc(2));
+    HIP_TRY(V.bSb.alloc((size_t)nc * nc)); HIP_TRY(V.bSigc.alloc((size_t)nc * nc)); HIP_TRY(V.bCt.alloc((size_t)m * nc)); HIP_TRY(V.bDm.alloc((size_t)m * m));
+    HIP_TRY(V.bW.alloc((size_t)m * nc)); HIP_TRY(V.bZ.alloc((size_t)m * nc)); HIP_TRY(V.bTinv.alloc((size_t)m * m)); HIP_TRY(V.bperm.alloc((size_t)R.Np));
+    V.h_bperm.resize((size_t)R.Np);
+    for (size_t p = 0; p < P.order.size(); p++)
+        for (int q = 0; q < dpf; q++) V.h_bperm[p * dpf + q] = P.order[p] * dpf + q;
+    HIP_TRY(hipMemcpyAsync(V.bperm.p, V.h_bperm.data(), sizeof(int) * (size_t)R.Np, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(V.bflag.p, 0, sizeof(int) * 2, h->stream));
+    const CovBand Bc = cov_border_band_dev(h, R);
+    const CovBorder B = cov_border_dev(h, R);
+    const size_t lds = covband_lds_bytes(M, R.nb);
+    auto kc = R.nb == 6 ? k_cov_band_chol<6> : k_cov_band_chol<5>;
+    auto ks = R.nb == 6 ? k_cov_band_sel<6> : k_cov_band_sel<5>;
+    HIP_TRY(hipFuncSetAttribute((const void*)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)covband_lds_bytes(COVBAND_MAXW, R.nb)));
+    HIP_TRY(hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)covband_lds_bytes(COVBAND_MAXW, R.nb)));
+    HIP_TRY(hipFuncSetAttribute((const void*)k_cov_border_schur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)covborder_lds_bytes(COV_BORDER_MAXM)));
+    {
+        const long long total = (long long)nc * R.bw + (long long)m * nc + (long long)m * m;
+        ScopedTimer t(h, "cov_border_split");
+        hipLaunchKernelGGL(k_cov_border_split, dim3((unsigned)((total + COVBAND_THREADS - 1) / COVBAND_THREADS)), dim3(COVBAND_THREADS), 0, h->stream, B);
+    }
+    { ScopedTimer t(h, "cov_band"); hipLaunchKernelGGL(kc, dim3(1), dim3(COVBAND_THREADS), lds, h->stream, Bc); }
+    { ScopedTimer t(h, "cov_band_sel"); hipLaunchKernelGGL(ks, dim3(1), dim3(COVBAND_THREADS), lds, h->stream, Bc); }
+    { ScopedTimer t(h, "cov_border_solve"); hipLaunchKernelGGL(k_cov_border_solve, dim3((unsigned)P.border.size()), dim3(COVBAND_THREADS), 0, h->stream, B); }
+    { ScopedTimer t(h, "cov_border_schur"); hipLaunchKernelGGL(k_cov_border_schur, dim3(1), dim3(COVBAND_THREADS), covborder_lds_bytes(m), h->stream, B); }
+    { ScopedTimer t(h, "cov_border_apply"); hipLaunchKernelGGL(k_cov_border_apply, dim3((unsigned)P.n_core() + 1), dim3(COVBAND_THREADS), 0, h->stream, B, R.hb); }
+    HIP_TRY(hipGetLastError());
+    return SADVIO_OK;
+}
+
 int cov_invert(sadvio_ba_handle* h, const CovRoutes& R, bool& usable) {
     usable = true;
     if (R.Np == 0) return SADVIO_OK;
+    if (R.border) return cov_invert_border(h, R);
     if (R.band) return cov_invert_band(h, R);
     CovScratch& V = h->cv;
     MargScratch& M = h->mg;
@@ -351,10 +465,12 @@ void cov_pick_landmarks(const sadvio_cov_request* rq, const WinDev& d, const dou
     if (n_lmk_singular) *n_lmk_singular = n_sing;
 }
 
-// 5 (band route). The columns of the pair blocks outside the band by substitution with L's band, one workgroup per distinct column
+// 5 (band route, border route). The columns of the pair blocks outside the band by substitution with L's band, one workgroup per distinct column
 // key-frame: the canonical block is (a, b), a > b in free index, and (b, a) is read as its transpose, so pair(a, b) and
 // pair(b, a)^T agree to the bit and a pair's bits do not depend on what else was asked for. The blocks asked for are gathered on the
-// device; one wait; SADVIO_E_NOT_USABLE with the outputs untouched when a pivot failed its test.
+// device; one wait; SADVIO_E_NOT_USABLE with the outputs untouched when a pivot failed its test. On the border route a block with a
+// border key-frame is read where k_cov_border_apply wrote it, the band is the core's in compacted index, and a block of two core
+// key-frames outside it is the column of B^-1 plus the Z W^T term (k_cov_border_gather).
 int cov_read_back_band(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, const CovRoutes& R, double* kf_cov, double* pair_cov, double* lmk_cov,
                        int32_t* n_lmk_singular) {
     const WinDev& d = h->plan.wins[w].d;
@@ -369,25 +485,27 @@ int cov_read_back_band(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq,
         const int fa = h->plan.kf_fidx[d.kf_base + ka], fb = h->plan.kf_fidx[d.kf_base + kb];
         int* T = &tab[4 * (size_t)e];
         if (fa < 0 || fb < 0) { T[0] = COVBAND_G_ZERO; continue; }
-        if (std::abs(fa - fb) <= R.hb) { T[0] = COVBAND_G_SIG; T[1] = fa * dpf; T[2] = fb * dpf; continue; }
-        const int lo = std::min(fa, fb), hi = std::max(fa, fb);
+        const int ca = R.border ? R.border->core_of[fa] : fa, cb = R.border ? R.border->core_of[fb] : fb;   // index in the band (-1: a border key-frame)
+        if (ca < 0 || cb < 0 || std::abs(ca - cb) <= R.hb) { T[0] = COVBAND_G_SIG; T[1] = fa * dpf; T[2] = fb * dpf; continue; }
+        const int lo = std::min(ca, cb), hi = std::max(ca, cb);
         if (x_of[lo] < 0) { x_of[lo] = (int)xcol.size(); xcol.push_back(lo * dpf); }
-        T[0] = fa > fb ? COVBAND_G_COL : COVBAND_G_COLT; T[1] = hi * dpf; T[3] = x_of[lo];
+        T[0] = ca > cb ? COVBAND_G_COL : COVBAND_G_COLT; T[1] = hi * dpf; T[2] = lo * dpf; T[3] = x_of[lo];
     }
-    const CovBand B = cov_band_dev(h, R);
+    const CovBand B = R.border ? cov_border_band_dev(h, R) : cov_band_dev(h, R);
     std::vector<double>& out = V.h_sig; std::vector<double>& lo = V.h_lout;
     if (nblk > 0) {
         HIP_TRY(V.gtab.alloc(tab.size())); HIP_TRY(V.gout.alloc((size_t)nblk * bs));
         HIP_TRY(hipMemcpyAsync(V.gtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, h->stream));
         if (!xcol.empty()) {
-            HIP_TRY(V.xcol.alloc(xcol.size())); HIP_TRY(V.X.alloc(xcol.size() * (size_t)dpf * n));
+            HIP_TRY(V.xcol.alloc(xcol.size())); HIP_TRY(V.X.alloc(xcol.size() * (size_t)dpf * B.n));
             HIP_TRY(hipMemcpyAsync(V.xcol.p, xcol.data(), sizeof(int) * xcol.size(), hipMemcpyHostToDevice, h->stream));
             ScopedTimer t(h, "cov_band_pairs");
             hipLaunchKernelGGL(k_cov_band_cols, dim3((unsigned)xcol.size()), dim3(COVBAND_THREADS), 0, h->stream, B, (const int*)V.xcol.p, V.X.p);
         }
         {
             ScopedTimer t(h, "cov_band_gather");
-            hipLaunchKernelGGL(k_cov_band_gather, dim3(nblk), dim3(COVBAND_THREADS), 0, h->stream, B, (const int*)V.gtab.p, (const double*)V.X.p, V.gout.p);
+            if (R.border) hipLaunchKernelGGL(k_cov_border_gather, dim3(nblk), dim3(COVBAND_THREADS), 0, h->stream, cov_border_dev(h, R), (const int*)V.gtab.p, (const double*)V.X.p, V.gout.p);
+            else hipLaunchKernelGGL(k_cov_band_gather, dim3(nblk), dim3(COVBAND_THREADS), 0, h->stream, B, (const int*)V.gtab.p, (const double*)V.X.p, V.gout.p);
         }
         HIP_TRY(hipGetLastError());
         out.resize((size_t)nblk * bs);
@@ -418,7 +536,7 @@ int cov_read_back(sadvio_ba_handle* h, int w, const sadvio_cov_request* rq, cons
     const WinDev& d = h->plan.wins[w].d;
     CovScratch& V = h->cv;
     const int n = R.Np, dpf = d.dpf;
-    if (R.band) return cov_read_back_band(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
+    if (R.banded()) return cov_read_back_band(h, w, rq, R, kf_cov, pair_cov, lmk_cov, n_lmk_singular);
     std::vector<double>& sig = V.h_sig; std::vector<double>& lo = V.h_lout;
     const bool want_pp = n > 0 && ((kf_cov && rq->n_kf > 0) || (pair_cov && rq->n_pair > 0));
     if (want_pp) { sig.resize((size_t)n * n); HIP_TRY(hipMemcpyAsync(sig.data(), V.Sig.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, h->stream)); }

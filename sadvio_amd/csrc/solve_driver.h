@@ -672,6 +672,7 @@ int solve_summaries(sadvio_ba_handle* h, const SolveOpts& o, const SolvePlan& pl
     h->deltas_cached = false;
     h->last_slots = plan.slots; h->last_one_round = plan.one_round;
     h->cov_huber_a = o.huber_a; h->cov_use_lm = plan.use_lm;
+    h->cv.border_known.clear();   // (CovScratch: the border route's plans live from solve to solve)
     h->solved = true;
     int rc = SADVIO_OK;
     for (int w = 0; w < n_win; w++) {
